@@ -10,6 +10,11 @@ x T=16 frames x d = D = 2048, depth 6 + 6 GPT-2 layers, 3806 classes, 64 clips p
 resident in HBM, train mode with the reference's dropout rates (0.1, classifier 0.2, DropPath linspace(0,0.1)).
 One step = forward + 3-term loss + backward (+ bucketed gradient all-reduce for N > 1) + fused Nesterov-SGD update.
 Weak scaling: per-GPU batch fixed.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up (--warmup W steps), times --steps K steps and prints the headline line (`value`, `ms_per_step` ...).
+--full adds every side measurement (roofline, power, forward latency, parity precisions, other widths and batches, reference loop,
+CPU baseline; for N > 1 the sharded leg and the communication report).  --dump-outputs DIR writes what the last timed step computed
+as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -77,6 +82,15 @@ def parse():
     ap.add_argument("--no-ek100", action="store_true", help="skip the side measurement at the EK100 widths of expts/01 (d = 1024)")
     ap.add_argument("--no-separate-update", action="store_true", help="N = 1: skip the leg with the per-bucket update kernel (profiling runs: one kernel mix)")
     ap.add_argument("--no-small-batch", action="store_true", help="skip the side measurement at the reference's per-GPU batch of 16 clips")
+    ap.add_argument("--full", action="store_true",
+                    help="run every side measurement after the headline (N = 1: separate-update leg, reference row set, instrumented step "
+                         "and roofline, power, forward latency, parity precisions, EK100 widths, small batch, reference loop, CPU baseline; "
+                         "N > 1: sharded leg, communication report, instrumented step); the --no-* switches above apply within it.  "
+                         "Without it a run sets up, warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy: its loss and loss terms "
+                         "(float64) and a fixed, seeded sample of the parameters and momentum it left (float32; under --no-optimizer the "
+                         "gradient averaged over the ranks instead of the momentum), so that two builds can be compared output for output")
     args = ap.parse_args()
     if args.comm_dtype is None:
         args.comm_dtype = "bf16" if args.precision == "bf16" else "fp32"
@@ -918,6 +932,38 @@ class SideLegGuard:
             print(line, flush=True)
 
 
+DUMP_SAMPLE = 16384     # elements per parameter tensor in --dump-outputs (all of a smaller one): <= 147 tensors in every config, < 20 MB
+
+
+def dump_outputs(out_dir: str, trainer, loss, parts, optimized: bool):
+    """--dump-outputs: the last timed step's loss and loss terms (what Trainer.step returns) and the state it left -- parameters and
+    momentum (without the optimizer: the rank-averaged gradient) -- as a sample of each parameter tensor, in module order, whose indices are seeded
+    by the parameter's name: the same arguments give the same file contents up to the kernels' own rounding."""
+    import re
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([float(loss)], dtype=np.float64))
+    for k, v in parts.items():
+        np.save(os.path.join(out_dir, "loss_" + re.sub(r"[^\w.-]", "_", k) + ".npy"), np.array([float(v)], dtype=np.float64))
+    flat = trainer.flat
+    # without the optimizer: the gradient it would apply -- summed over the ranks (the bf16 payload has a buffer of its own), times 1 / N
+    state, scale = (trainer.opt.buf, 1.0) if optimized else trainer.reducer.grad_for_optimizer()
+    offset = {id(p): o for p, o in zip(flat.params, flat.offsets)}
+    ps, ss = [], []
+    with torch.no_grad():
+        for name, p in trainer.model.named_parameters():
+            if id(p) not in offset:
+                continue
+            n = p.numel()
+            idx = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(n, DUMP_SAMPLE, replace=False))
+            ix = torch.from_numpy(idx).to(p.device)
+            ps.append(p.detach().reshape(-1)[ix].float().cpu())
+            ss.append(state[offset[id(p)]:offset[id(p)] + n][ix].float().cpu() * scale)
+    np.save(os.path.join(out_dir, "params_sample.npy"), torch.cat(ps).numpy())
+    np.save(os.path.join(out_dir, "momentum_sample.npy" if optimized else "grads_sample.npy"), torch.cat(ss).numpy())
+
+
 def timed_steps(trainer, feats, tgt, sub, sync_all, warm: int, n: int, device, world: int) -> float:
     """ms per step (max over ranks) of `n` steps after `warm` untimed ones"""
     for _ in range(warm):
@@ -987,7 +1033,7 @@ def main():
         pg_timeout = timedelta(seconds=args.collective_timeout)
         if backend != "nccl":
             dist.init_process_group(backend=backend, timeout=pg_timeout)
-        elif not args.no_comm_report:
+        elif args.full and not args.no_comm_report:
             # which algorithm / protocol RCCL picks for the bucket sizes is decided inside the library: have it say so, into a
             # per-process file (INIT + TUNING lines only) that rank 0 summarises after the timed region
             rccl_log = f"/tmp/afft_rccl_{os.getpid()}.log"
@@ -1042,7 +1088,7 @@ def main():
     sync_all()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss, _ = trainer.step(feats, tgt, sub, optimize=not args.no_optimizer)
+        loss, parts = trainer.step(feats, tgt, sub, optimize=not args.no_optimizer)
     sync_all()
     elapsed = time.perf_counter() - t0
     if world > 1:
@@ -1057,6 +1103,10 @@ def main():
             print(json.dumps({"error": "the loss of the timed region is not finite: measurement void", "final_loss": repr(loss_val), "n_gpus": world,
                               "ms_per_step_void": round(elapsed / args.steps * 1e3, 3)}), flush=True)
         raise SystemExit(3)
+    if args.dump_outputs:
+        trainer.sync_masters()      # sharded update: whole masters and momentum on every rank (a collective; else a no-op)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, trainer, loss, parts, not args.no_optimizer)
     if captured:
         trainer.release_graph()
     ms_per_step = elapsed / args.steps * 1e3
@@ -1095,6 +1145,9 @@ def main():
     }
     if args.fallback_note:
         result["fallback_after"] = args.fallback_note      # this line comes from the all-reduce-only child started after that failure
+    if not args.full:
+        finish(result, rank, world, None)
+        return
     # (a rehearsal over gloo moves the buckets through the host: minutes, and gloo raises on a timeout instead of aborting the process)
     budget = args.side_leg_budget if args.side_leg_budget is not None else (100.0 if (backend == "nccl" and not share) else 1500.0)
     guard = SideLegGuard(result, rank, budget) if world > 1 else None
@@ -1298,11 +1351,16 @@ def main():
             except Exception as ex:  # noqa: BLE001
                 result["cpu_baseline"] = {"value": None, "error": repr(ex)}
 
+    finish(result, rank, world, guard)
+
+
+def finish(result: dict, rank: int, world: int, guard):
+    """rank 0 prints THE line; N > 1 leaves the process group"""
     if rank == 0:
         if guard is not None:
             guard.final(json.dumps(result))
         else:
-            print(json.dumps(result))
+            print(json.dumps(result), flush=True)
     if world > 1:
         try:
             dist.destroy_process_group()

@@ -1,16 +1,13 @@
 """Build-container tests of the drop-in claim: after afft_amd.install_as_models() the reference's import paths and Hydra
-`_target_` strings resolve to this package, and every model configuration the reference ships (conf/model/**.yaml, read from
-/root/reference when it is present -- the GPU box does not have it) instantiates with the yaml's own keyword arguments."""
+`_target_` strings resolve to this package, and every combination of the model configurations the reference ships
+(conf/model: fuser, mapping, CMFP) instantiates through those paths, built by afft_amd.config.make_model_cfg with the
+reference's `_target_` strings and keyword arguments."""
 import importlib
 import itertools
-import os
-import re
 import sys
 
 import pytest
 import torch
-
-CONF = "/root/reference/conf/model"
 
 
 @pytest.fixture()
@@ -39,48 +36,28 @@ def test_reference_import_paths_resolve_here(installed):
     from common.runner import Runner                                        # noqa: F401
 
 
-def _load(rel):
-    import yaml
-    with open(os.path.join(CONF, rel)) as f:
-        return yaml.safe_load(f)
-
-
-def _resolve(node, root):
-    """${a.b.c} interpolation against `root` (what OmegaConf does for the reference)"""
-    if isinstance(node, dict):
-        return {k: _resolve(v, root) for k, v in node.items()}
-    if isinstance(node, list):
-        return [_resolve(v, root) for v in node]
-    if isinstance(node, str):
-        m = re.fullmatch(r"\$\{([\w.]+)\}", node)
-        if m:
-            cur = root
-            for part in m.group(1).split("."):
-                cur = cur[part]
-            return _resolve(cur, root)
-    return node
-
+# The reference's conf/model choices, by file name, and the names afft_amd.config.make_model_cfg gives the same configurations
+# (its restatement of common.yaml + fuser/*, mapping/*, future_predictor/*, CMFP/* with the same `_target_` strings and values)
+FUSERS = {"SA-Fuser": "sa", "CA-Fuser": "ca", "SA-Fuser_wo_token": "cm", "T-SA-Fuser": "tsa", "MATT": "matt"}
+MAPPINGS = {"linear": "linear", "gatedlinear": "gated", "nonlinear": "nonlinear"}
+CMFPS = {"cmfp_early": "early", "scorefusion": "score", "individual": "individual"}
 
 COMBOS = [(f, m, "cmfp_early") for f, m in itertools.product(["SA-Fuser", "CA-Fuser", "SA-Fuser_wo_token", "T-SA-Fuser"],
                                                                ["linear", "gatedlinear", "nonlinear"])] + \
          [("MATT", "linear", "scorefusion"), ("SA-Fuser", "linear", "individual")]
 
 
-@pytest.mark.skipif(not os.path.isdir(CONF), reason="reference conf/ not present (GPU box)")
 @pytest.mark.parametrize("fuser,mapping,cmfp", COMBOS)
 def test_reference_yaml_configs_instantiate(installed, fuser, mapping, cmfp):
-    from afft_amd._hydra_compat import to_attr
+    from afft_amd.config import make_model_cfg
     modal_dims = {"rgb": 64, "objects": 24, "audio": 64, "flow": 64}
     late = cmfp != "cmfp_early"
-    common = _load("common.yaml")
-    common.update(backbones={m: _load("backbone/identity.yaml") for m in modal_dims}, fp_inter_dim=128, fp_layers=2, fp_heads=2,
-                  modality_cls=late, fusion_cls=not late, share_classifiers=not late)
-    model = dict(modal_dims=modal_dims, modal_feature_order=["rgb", "objects", "audio", "poses", "flow"], common_dim=64,
-                 dropout=0.2, common=common, mapping=_load(f"mapping/{mapping}.yaml"), fuser=_load(f"fuser/{fuser}.yaml"),
-                 future_predictor=_load("future_predictor/base_future_predictor.yaml"), CMFP=_load(f"CMFP/{cmfp}.yaml"))
+    # the yaml's own values where make_model_cfg defaults to the bench's: no shared predictor, LayerNorm in the gated / non-linear mapping
+    cfg = make_model_cfg(modal_dims, 64, 128, fuser=FUSERS[fuser], fp_layers=2, fp_heads=2, dropout=0.2, T=4,
+                         modal_encoding=(fuser == "T-SA-Fuser"), cmfp=CMFPS[cmfp], mapping=MAPPINGS[mapping],
+                         mapping_layernorm=(mapping != "linear"), share_predictors=False, share_classifiers=not late)
     if fuser == "T-SA-Fuser":
-        model["fuser"]["temporal_sequence_length"] = 4
-    cfg = to_attr(_resolve(model, {"model": model}))
+        cfg.fuser["temporal_sequence_length"] = 4
     for section in ("fuser", "mapping", "future_predictor", "CMFP"):
         assert cfg[section]["_target_"].startswith("models."), section
     from models.base_model import BaseModel        # the reference's import path (train.py:22)

@@ -1273,7 +1273,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
-           "--config", "ek100", "--batch", "8", "--no-parity-mode", "--no-cpu-baseline", "--no-roofline"]
+           "--config", "ek100", "--batch", "8", "--no-parity-mode", "--no-cpu-baseline", "--no-roofline", "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1305,7 +1305,7 @@ def test_bench_launches_itself_for_two_ranks():
     env = dict(os.environ, AFFT_BENCH_BACKEND="gloo", AFFT_BENCH_SHARE_GPU="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR", "LOCAL_WORLD_SIZE", "GROUP_RANK"):
         env.pop(k, None)
-    common = ["--steps", "2", "--warmup", "1", "--config", "ek100", "--batch", "8", "--no-parity-mode", "--no-cpu-baseline"]
+    common = ["--steps", "2", "--warmup", "1", "--config", "ek100", "--batch", "8", "--no-parity-mode", "--no-cpu-baseline", "--full"]
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--no-roofline", "--no-comm-report"] + common,
                        cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -1328,6 +1328,40 @@ def test_bench_launches_itself_for_two_ranks():
     assert bad.returncode != 0
 
 
+def test_bench_plain_run_is_the_headline_and_dumps_outputs(tmp_path):
+    """`python bench.py --gpus 1` without --full: the headline line alone (no side measurement) over exactly --steps timed steps,
+    and with --dump-outputs the last timed step's loss (the line's final_loss), its terms and the parameter / momentum samples as
+    finite float64 / float32 .npy files, under 64 MB in all."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR", "LOCAL_WORLD_SIZE", "GROUP_RANK"):
+        env.pop(k, None)
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--config", "ek100",
+                        "--batch", "8", "--dump-outputs", str(out)], cwd=root, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "bf16" and d["higher_is_better"] is True and d["unit"] == "clips/s"
+    assert abs(d["value"] - 8 * 1e3 / d["ms_per_step"]) / d["value"] < 1e-3
+    side = {"separate_update", "reference_row_set", "roofline", "hbm_kernels", "power", "fwd_p50_ms", "parity_mode", "ek100", "small_batch",
+            "reference_loop", "cpu_baseline", "comm"}
+    assert not side & set(d), side & set(d)
+    files = {f.name: np.load(f) for f in out.iterdir()}
+    assert {"loss.npy", "params_sample.npy", "momentum_sample.npy"} <= set(files) and any(k.startswith("loss_") for k in files)
+    assert sum(f.stat().st_size for f in out.iterdir()) < 64 << 20
+    for k, v in files.items():
+        assert v.dtype == (np.float64 if k.startswith("loss") else np.float32) and v.size > 0 and np.isfinite(v).all(), k
+    assert abs(float(files["loss.npy"][0]) - d["final_loss"]) < 1e-4 * max(1.0, abs(d["final_loss"]))
+    assert files["params_sample.npy"].shape == files["momentum_sample.npy"].shape and np.abs(files["momentum_sample.npy"]).max() > 0
+
+
 @pytest.mark.parametrize("fail", ["sharded", "sharded_hang", "headline_sharded"])
 def test_bench_two_ranks_headline_survives_a_failing_side_leg(fail):
     """The first 8-GPU contact must not be losable (VERDICT r5 #3b).  Rehearsed on this box (two gloo ranks on cuda:0) with the test
@@ -1344,7 +1378,7 @@ def test_bench_two_ranks_headline_survives_a_failing_side_leg(fail):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR", "LOCAL_WORLD_SIZE", "GROUP_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--config", "ek100", "--batch", "8",
-           "--no-parity-mode", "--no-cpu-baseline", "--no-roofline", "--no-comm-report"]
+           "--no-parity-mode", "--no-cpu-baseline", "--no-roofline", "--no-comm-report", "--full"]
     if fail == "sharded_hang":
         cmd += ["--side-leg-budget", "8"]
     if fail == "headline_sharded":

@@ -355,6 +355,64 @@ def test_bench_comm_report_runs_on_two_ranks(tmp_path):
     assert abs(rep["loss_delta_bf16_vs_fp32_payload"]) < 0.05 * abs(rep["loss_after_4_steps"]["fp32"])
 
 
+def test_bench_dump_outputs_is_seeded_and_bounded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs with the test double: the loss and its terms as float64, parameters and momentum (gradients without
+    the optimizer) as float32 samples of one size that hold the trainer's values at indices seeded by the parameter's name, the
+    same file contents from two identical runs, and the cap on the sample size holds for every bench configuration (the tensor
+    count does not depend on the widths)."""
+    import zlib
+    import numpy as np
+    import bench
+    import cpu_ops
+    import afft_amd
+    from afft_amd import config as CFG
+    from afft_amd.models.base_model import BaseModel
+    from afft_amd.parallel import Trainer
+    monkeypatch.setitem(CFG.BASELINE_CONFIGS, "tiny", dict(modal_dims={"rgb": 64, "flow": 64}, common_dim=64, fp_inter_dim=64, fuser="sa", T=4))
+    losses, trainers, saved = {}, {}, afft_amd.runtime.precision()
+    with cpu_ops.installed():
+        afft_amd.set_precision("fp32")
+        try:
+            for run, optimize in (("a", True), ("b", True), ("g", False)):
+                model, c = bench.build_model("tiny", "cpu", drop=0.0)
+                model.eval()
+                feats, tgt, sub = bench.make_inputs(c, 4, c["T"], 0, "cpu")
+                tr = Trainer(model, WTS, bucket_elems=1 << 16)
+                for _ in range(2):
+                    loss, parts = tr.step(feats, tgt, sub, optimize=optimize)
+                losses[run], trainers[run] = float(loss), tr
+                bench.dump_outputs(str(tmp_path / run), tr, loss, parts, optimize)
+        finally:
+            afft_amd.set_precision(saved)
+    a, b, g = ({f.name: np.load(f) for f in (tmp_path / r).iterdir()} for r in "abg")
+    assert set(a) == {"loss.npy", "params_sample.npy", "momentum_sample.npy"} | {f"loss_{k}.npy" for k in parts}
+    assert set(g) == set(a) - {"momentum_sample.npy"} | {"grads_sample.npy"}
+    for k, v in a.items():
+        assert v.dtype == (np.float64 if k.startswith("loss") else np.float32) and np.isfinite(v).all(), k
+        assert np.array_equal(v, b[k]), k
+    n = sum(min(p.numel(), bench.DUMP_SAMPLE) for p in model.parameters() if p.requires_grad)
+    assert a["params_sample.npy"].shape == a["momentum_sample.npy"].shape == g["grads_sample.npy"].shape == (n,)
+    assert float(a["loss.npy"][0]) == losses["a"] and float(g["loss.npy"][0]) == losses["g"] and np.abs(g["grads_sample.npy"]).max() > 0
+    for dump, key, tr, state in ((a, "momentum_sample.npy", trainers["a"], trainers["a"].opt.buf),
+                                 (g, "grads_sample.npy", trainers["g"], trainers["g"].flat.flat_g)):
+        offset = {id(p): o for p, o in zip(tr.flat.params, tr.flat.offsets)}
+        pos, sampled = 0, 0
+        for name, p in tr.model.named_parameters():
+            k = p.numel()
+            idx = np.arange(k)
+            if k > bench.DUMP_SAMPLE:
+                idx, sampled = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(k, bench.DUMP_SAMPLE, replace=False)), sampled + 1
+            m = len(idx)
+            assert np.array_equal(dump["params_sample.npy"][pos:pos + m], p.detach().reshape(-1).numpy()[idx]), name
+            assert np.array_equal(dump[key][pos:pos + m], state[offset[id(p)]:offset[id(p)] + k].numpy()[idx]), (key, name)
+            pos += m
+        assert pos == n and sampled >= 1
+    for name, cc in CFG.BASELINE_CONFIGS.items():
+        small = CFG.make_model_cfg({m: 8 for m in cc["modal_dims"]}, 8, 8, fuser=cc["fuser"], T=cc["T"], modal_encoding=(cc["fuser"] == "tsa"))
+        tensors = sum(p.requires_grad for p in BaseModel(small, num_classes={"action": 5}, class_mappings={}).parameters())
+        assert tensors * bench.DUMP_SAMPLE * 4 * 2 < 64 << 20, name
+
+
 # ----------------------------------------------------------------------------- a dead / hung rank cannot hang the caller
 @pytest.mark.parametrize("mode", ["die", "hang"])
 def test_launcher_reports_a_dead_or_hung_rank(mode, capfd):

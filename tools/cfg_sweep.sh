@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."
 for cfg in ${CFGS:-cfg2 ek100 cfg4 cfg5 cfg2_cm cfg2_tsa}; do
   echo -n "$cfg  "
-  timeout 300 python bench.py --config $cfg --steps 30 --warmup 8 --no-roofline --no-cpu-baseline "$@" 2>&1 | tail -1 | python -c "
+  timeout 300 python bench.py --full --config $cfg --steps 30 --warmup 8 --no-roofline --no-cpu-baseline "$@" 2>&1 | tail -1 | python -c "
 import sys, json
 l = sys.stdin.read().strip()
 try:

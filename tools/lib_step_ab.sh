@@ -2,7 +2,7 @@
 # Step time of the bench workload with two builds of the library, alternating processes on ONE box (processes on one box repeat to ~0.2 %).
 # usage (GPU box): bash tools/lib_step_ab.sh <other lib path> [rounds] [extra bench flags]
 other=$1; rounds=${2:-3}; shift 2
-flags="--steps 30 --warmup 8 --no-cpu-baseline --no-roofline --no-parity-mode --no-reference-loop --no-power --no-ek100 --no-small-batch --no-separate-update $*"
+flags="--full --steps 30 --warmup 8 --no-cpu-baseline --no-roofline --no-parity-mode --no-reference-loop --no-power --no-ek100 --no-small-batch --no-separate-update $*"
 for r in $(seq 1 $rounds); do
   for lib in product $other; do
     if [ $lib = product ]; then unset AFFT_LIB; else export AFFT_LIB=$lib; fi

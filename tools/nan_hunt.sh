@@ -1,5 +1,5 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT && mkdir -p gpurun_out
-F="--no-cpu-baseline --no-parity-mode --no-reference-loop --no-power --no-ek100 --no-roofline --steps 30 --warmup 8"
+F="--full --no-cpu-baseline --no-parity-mode --no-reference-loop --no-power --no-ek100 --no-roofline --steps 30 --warmup 8"
 for i in $(seq ${N:-6}); do
   for lib in ${LIBS:-product g2off}; do
     if [ $lib = product ]; then unset AFFT_LIB; else export AFFT_LIB=$PWD/afft_amd/lib/libafft_hip_$lib.so; fi

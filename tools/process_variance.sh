@@ -3,7 +3,7 @@
 # (round 6: sequential bench.py processes on one box give ~11.7 or ~14.7 ms for the same build.)
 # usage (GPU box): bash tools/process_variance.sh [n]  -> gpurun_out/r06_process_variance.txt + gpurun_out/pv_<i>.json
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT && mkdir -p gpurun_out
-F="--no-cpu-baseline --no-parity-mode --no-reference-loop --no-ek100 --steps 30 --warmup 8"
+F="--full --no-cpu-baseline --no-parity-mode --no-reference-loop --no-ek100 --steps 30 --warmup 8"
 out=gpurun_out/r06_process_variance.txt; : > $out
 for i in $(seq ${1:-8}); do
   timeout 300 python bench.py $F 2>/dev/null > gpurun_out/pv_$i.json
