@@ -15,6 +15,7 @@ F32, BF16, F16 = 0, 1, 2      # F16: fp16 planes / images of the "fp16x2" precis
 GEMM_WS_HEADER = 4096
 ACT_NONE, ACT_GELU_ERF, ACT_GELU_TANH, ACT_DGELU_ERF, ACT_DGELU_TANH, ACT_RELU, ACT_SIGMOID_GATE = 0, 1, 2, 3, 4, 5, 6
 MASK_NONE, MASK_DIAG, MASK_CAUSAL, MASK_BLOCKCAUSAL = 0, 1, 2, 3
+ADAM_DECOUPLED = 1            # afft_adam / afft_adam_runs flags: AdamW's decoupled weight decay
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 
@@ -186,6 +187,8 @@ _SIGS = {
     "afft_sgd_nesterov_runs": ([vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, i32, vp], C.c_int),
     "afft_sgd_nesterov2": ([vp, vp, i32, vp, vp, vp, vp, i64, f32, f32, f32, f32, vp, i32, vp, vp], C.c_int),
     "afft_sgd_nesterov_runs2": ([vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, i32, vp, vp], C.c_int),
+    "afft_adam": ([vp, vp, i32, vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, vp, vp, i32, vp, vp], C.c_int),
+    "afft_adam_runs": ([vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, f32, f32, vp, i32, vp, vp], C.c_int),
     "afft_sumsq": ([vp, i32, i64, f32, vp, vp, i64, vp], C.c_int),
     "afft_group_sum": ([vp, i32, i32, i64, f32, vp, vp], C.c_int),
     "afft_set_dropout_salt": ([vp], C.c_int),

@@ -481,6 +481,35 @@ def sgd_nesterov_runs(p: Tensor, g: Tensor, buf: Tensor, runs: Tensor, lr: float
                                             int(first), _p(ok), _stream()), "sgd_nesterov_runs")
 
 
+def adam(p: Tensor, g: Tensor, m: Tensor, v: Tensor, lr: float, beta1: float, beta2: float, eps: float, wd: float, gscale: float,
+         step: Tensor, decoupled: bool, p_bf16: Optional[Tensor] = None, gscale_dev: Optional[Tensor] = None,
+         p_f16: Optional[Tensor] = None, p_f8: Optional[Tensor] = None, ok: Optional[Tensor] = None):
+    """Adam (decoupled=False) / AdamW (decoupled=True) over a flat slice: p, exp_avg m and exp_avg_sq v fp32, g fp32 or bf16.
+    step (device float): the number of steps taken before this one (the kernel never writes it); ok, images and gscale_dev as
+    in sgd_nesterov"""
+    assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()
+    assert p.dtype == m.dtype == v.dtype == step.dtype == torch.float32 and m.numel() == v.numel() == g.numel() == p.numel()
+    if p_bf16 is not None:
+        assert p_bf16.dtype == torch.bfloat16 and p_bf16.numel() == p.numel() and p_bf16.is_contiguous()
+    if p_f16 is not None:
+        assert p_f16.dtype == torch.float16 and p_f16.numel() == p.numel() and p_f16.is_contiguous()
+    if p_f8 is not None:
+        assert p_f8.dtype == torch.uint8 and p_f8.numel() == p.numel() and p_f8.is_contiguous()
+    L.check(L.lib().afft_adam(_p(p), _p(g), _dt(g), _p(m), _p(v), _p(p_bf16), _p(p_f16), _p(p_f8), p.numel(), lr, beta1, beta2, eps,
+                              wd, gscale, _p(gscale_dev), _p(step), L.ADAM_DECOUPLED if decoupled else 0, _p(ok), _stream()), "adam")
+
+
+def adam_runs(p: Tensor, g: Tensor, m: Tensor, v: Tensor, runs: Tensor, lr: float, beta1: float, beta2: float, eps: float, wd: float,
+              gscale: float, step: Tensor, decoupled: bool, p_bf16: Optional[Tensor] = None, p_f16: Optional[Tensor] = None,
+              p_f8: Optional[Tensor] = None, ok: Optional[Tensor] = None):
+    """the same update over the runs {start, length} (int64 [nruns, 2] on the device) of whole flat buffers"""
+    assert runs.dtype == torch.int64 and runs.dim() == 2 and runs.shape[1] == 2 and runs.is_contiguous()
+    assert p.dtype == g.dtype == m.dtype == v.dtype == step.dtype == torch.float32
+    assert g.numel() == m.numel() == v.numel() == p.numel()
+    L.check(L.lib().afft_adam_runs(_p(p), _p(g), _p(m), _p(v), _p(p_bf16), _p(p_f16), _p(p_f8), _p(runs), runs.shape[0], lr, beta1,
+                                   beta2, eps, wd, gscale, _p(step), L.ADAM_DECOUPLED if decoupled else 0, _p(ok), _stream()), "adam_runs")
+
+
 def pack_weight(w: Tensor, dst: Tensor) -> Tensor:
     """fp32 weight [rows, cols] (row stride free; rows % 16 == 0, cols % 32 == 0) -> its fragment-packed bf16 image `dst`
     (rows * cols elements, contiguous): include/afft_hip.h afft_pack_weight"""

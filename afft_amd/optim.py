@@ -1,5 +1,5 @@
-"""``afft_amd.optim.SGD``: the flat-buffer fused SGD of ``afft_amd.parallel`` behind the ``torch.optim.Optimizer`` interface, so
-that the reference's own training loop reaches the fast path unchanged.
+"""``afft_amd.optim.SGD`` / ``Adam`` / ``AdamW``: the flat-buffer fused optimizers of ``afft_amd.parallel`` behind the
+``torch.optim.Optimizer`` interface, so that the reference's own training loop reaches the fast path unchanged.
 
 The reference builds its optimizer with ``hydra.utils.instantiate(cfg.opt.optimizer, param_groups)`` over the 151 per-parameter
 groups of ``prepare_params`` (train.py:189-225, :352; conf/opt/optimizer/sgd.yaml: ``_target_: torch.optim.SGD``, momentum 0.9,
@@ -8,7 +8,9 @@ groups of ``prepare_params`` (train.py:189-225, :352; conf/opt/optimizer/sgd.yam
     loss, metrics = runner(data, mixup_fn, mixup_backbone)
     optimizer.zero_grad(); loss.backward(); [clip_grad_norm_]; optimizer.step(); lr_scheduler.step()
 
-Selecting this class is one Hydra override, no file of the reference changes: ``opt.optimizer._target_=afft_amd.optim.SGD``.
+Selecting this class is one Hydra override, no file of the reference changes: ``opt.optimizer._target_=afft_amd.optim.SGD``
+(``opt/optimizer=adamW opt.optimizer._target_=afft_amd.optim.AdamW`` for conf/opt/optimizer/adamW.yaml; Adam / AdamW never run in
+the weight-gradient GEMM epilogues: their update is the per-bucket one below).
 
 What the five calls become here:
 
@@ -44,14 +46,14 @@ import torch
 import torch.distributed as dist
 
 from . import ops, runtime as rt
-from .parallel import FlatParams, FusedSGD, GradReducer, _FusedEpilogue
+from .parallel import FlatParams, FusedAdam, FusedSGD, GradReducer, _FusedEpilogue
 
 Tensor = torch.Tensor
 
-_ENGINES: List["weakref.ref"] = []     # live SGD instances (parallel.DistributedDataParallel looks its optimizer up here)
+_ENGINES: List["weakref.ref"] = []     # live SGD / Adam / AdamW instances (parallel.DistributedDataParallel looks its optimizer up here)
 
 
-def engines_for(module: torch.nn.Module) -> List["SGD"]:
+def engines_for(module: torch.nn.Module) -> List["_FlatOptimizer"]:
     """the afft optimizers whose parameters all belong to `module`"""
     ids = {id(p) for p in module.parameters()}
     out = []
@@ -64,37 +66,22 @@ def engines_for(module: torch.nn.Module) -> List["SGD"]:
     return out
 
 
-class SGD(torch.optim.Optimizer, _FusedEpilogue):
-    """torch.optim.SGD(params, lr, momentum, dampening=0, weight_decay, nesterov) on the flat fused path (module docstring).
-    Extra keyword arguments: comm_dtype ('fp32' | 'bf16' gradient payload), comm_algo ('allreduce' | 'rs_ag' | 'sharded': the
-    update of the GEMM weights in 1 / N slices with an all-gather of their 16-bit images, parallel.GradReducer), bucket_elems,
-    group, in_backward (update inside the backward pass; default on), grad_clip (clip by global norm inside step(), on the
-    device, instead of the loop's clip_grad_norm_ call)."""
+class _FlatOptimizer(torch.optim.Optimizer, _FusedEpilogue):
+    """The flat-buffer machinery behind the ``torch.optim.Optimizer`` interface (module docstring), shared by SGD and Adam / AdamW.
+    A subclass builds its engine (parallel.FusedSGD / FusedAdam: self.opt) in `_make_engine`, names the flat-shaped state buffers
+    the sharded update has to gather in `_state_buffers`, and publishes them as torch's per-parameter state in `_publish_state`."""
 
-    def __init__(self, params, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
-                 nesterov: bool = False, *, maximize: bool = False, foreach=None, differentiable: bool = False, fused=None,
-                 comm_dtype: Optional[str] = None, comm_algo: Optional[str] = None, bucket_elems: int = 32 * 1024 * 1024,
-                 group=None, in_backward: Optional[bool] = None, grad_clip: Optional[float] = None):
-        if lr < 0.0 or momentum < 0.0 or weight_decay < 0.0:
-            raise ValueError("afft_amd.optim.SGD: negative lr / momentum / weight_decay")
-        if nesterov and (momentum <= 0 or dampening != 0):
-            raise ValueError("Nesterov momentum requires a momentum and zero dampening")      # torch's own check
-        if maximize or differentiable:
-            raise NotImplementedError("afft_amd.optim.SGD: maximize / differentiable are not supported")
-        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov)
-        super().__init__(params, defaults)
-        g0 = self.param_groups[0]
-        for g in self.param_groups:
-            if g["dampening"] != 0:
-                raise NotImplementedError("afft_amd.optim.SGD: dampening != 0 is not supported (the reference never sets it)")
-            if g["momentum"] != g0["momentum"] or g["nesterov"] != g0["nesterov"]:
-                raise NotImplementedError("afft_amd.optim.SGD: momentum / nesterov must be the same in every group "
-                                          "(train.py:189-225 varies lr and weight_decay only)")
+    @property
+    def _what(self) -> str:
+        return f"afft_amd.optim.{type(self).__name__}"
+
+    def _setup(self, comm_dtype: Optional[str], comm_algo: Optional[str], bucket_elems: int, group, in_backward: Optional[bool],
+               grad_clip: Optional[float]):
         plist = [p for g in self.param_groups for p in g["params"]]
         algo = comm_algo or os.environ.get("AFFT_COMM_ALGO", "allreduce")
         self.flat = FlatParams(plist, sharded_layout=(algo == "sharded"))
         if len(self.flat.params) != len(plist):
-            raise ValueError("afft_amd.optim.SGD: every parameter must require grad and appear once (train.py:219-224 drops the "
+            raise ValueError(f"{self._what}: every parameter must require grad and appear once (train.py:219-224 drops the "
                              "lr = 0 groups and clears requires_grad on their parameters)")
         own_comm = rt.grad_mode() == "sink"       # autograd mode: whoever wraps the model (torch DDP) reduces
         self.reducer = GradReducer(self.flat, group=group, bucket_elems=bucket_elems,
@@ -102,7 +89,7 @@ class SGD(torch.optim.Optimizer, _FusedEpilogue):
                                    comm_algo=algo)
         if not own_comm:
             self.reducer.comm = False
-        self.opt = FusedSGD(self.flat, lr, g0["momentum"], weight_decay, nesterov=bool(g0["nesterov"]))
+        self.opt = self._make_engine()
         self.grad_clip = grad_clip
         if in_backward is None:
             in_backward = os.environ.get("AFFT_OPT_IN_BACKWARD", "1") != "0"
@@ -113,10 +100,25 @@ class SGD(torch.optim.Optimizer, _FusedEpilogue):
         self._saved_runs = None
         self._names: Dict[int, str] = {id(p): g.get("name", "?") for g in self.param_groups for p in g["params"]}
         self._group_of: List[dict] = self._groups_in_flat_order()
-        self.reducer.opt_buf = self.opt.buf
+        bufs = self._state_buffers()
+        self.reducer.opt_buf = bufs[0] if len(bufs) == 1 else bufs
         if self.reducer.world > 1 and self.reducer.comm:
             self.sync_parameters(group)
         _ENGINES.append(weakref.ref(self))
+
+    def _make_engine(self):
+        raise NotImplementedError
+
+    def _state_buffers(self) -> tuple:
+        """the optimizer's state buffers shaped like flat_p (all-gathered by sync_masters under the sharded update)"""
+        raise NotImplementedError
+
+    def _state_scalars(self) -> tuple:
+        """device tensors of optimizer state besides those buffers (broadcast by sync_parameters)"""
+        return ()
+
+    def _publish_state(self):
+        raise NotImplementedError
 
     # ------------------------------------------------------------------ helpers
     def _groups_in_flat_order(self) -> List[dict]:
@@ -125,12 +127,12 @@ class SGD(torch.optim.Optimizer, _FusedEpilogue):
         return [gmap[id(p)] for p in self.flat.params]
 
     def sync_masters(self):
-        """sharded update (comm_algo = 'sharded'): whole fp32 masters and momentum on every rank (a collective: EVERY rank calls it;
-        parallel.DistributedDataParallel does at the first evaluation forward after training steps)"""
+        """sharded update (comm_algo = 'sharded'): whole fp32 masters and optimizer state on every rank (a collective: EVERY rank
+        calls it; parallel.DistributedDataParallel does at the first evaluation forward after training steps)"""
         self.reducer.sync_masters()
 
     def state_dict(self):
-        self.reducer.assert_masters_fresh("afft_amd.optim.SGD.state_dict()")      # never a collective: rank 0 alone saves (train.py:403-411)
+        self.reducer.assert_masters_fresh(f"{self._what}.state_dict()")      # never a collective: rank 0 alone saves (train.py:403-411)
         return super().state_dict()
 
     def _name_of(self, p: Tensor) -> str:
@@ -141,13 +143,14 @@ class SGD(torch.optim.Optimizer, _FusedEpilogue):
         self.opt.set_hyper([(float(g["lr"]), float(g["weight_decay"])) for g in self._group_of])
 
     def sync_parameters(self, group=None, src: int = 0):
-        """every replica starts from rank `src`'s parameters, momentum and step count (what torch DDP's constructor does for the
-        parameters, train.py:364-368); the bf16 images are re-derived from the received values"""
+        """every replica starts from rank `src`'s parameters, optimizer state and step count (what torch DDP's constructor does for
+        the parameters, train.py:364-368); the bf16 images are re-derived from the received values"""
         if not (dist.is_available() and dist.is_initialized()):
             return
         root = dist.get_global_rank(group, src) if group is not None else src
         dist.broadcast(self.flat.flat_p, src=root, group=group)
-        dist.broadcast(self.opt.buf, src=root, group=group)
+        for t in self._state_buffers() + self._state_scalars():
+            dist.broadcast(t, src=root, group=group)
         steps = torch.tensor([self.opt.steps], dtype=torch.int64, device=self.flat.flat_p.device)
         dist.broadcast(steps, src=root, group=group)
         self.opt.steps = int(steps)
@@ -171,7 +174,7 @@ class SGD(torch.optim.Optimizer, _FusedEpilogue):
             self.reducer.sync_masters()      # a replicated whole-buffer update follows (every rank takes this branch): not from stale masters
         self._fuse_now = inb and self._fused is not None and self._can_fuse()
         rt.SINK.fused = self._fused_desc if self._fuse_now else None
-        rt.SINK.step_ok = self.reducer.step_ok = self.opt.ok      # parallel.FusedSGD.ok: a non-finite loss makes the step a no-op (all ranks agree)
+        rt.SINK.step_ok = self.reducer.step_ok = self.opt.ok      # parallel._FlatUpdate.ok: a non-finite loss makes the step a no-op (all ranks agree)
         self._saved_runs, self.opt.runs = self.opt.runs, (self.opt.runs if self._fuse_now else None)
         self.reducer.begin_step()
         self._armed = True
@@ -222,7 +225,7 @@ class SGD(torch.optim.Optimizer, _FusedEpilogue):
     def step(self, closure=None):
         loss = None
         if closure is not None:
-            raise NotImplementedError("afft_amd.optim.SGD.step: closures are not supported (the update runs inside backward())")
+            raise NotImplementedError(f"{self._what}.step: closures are not supported (the update runs inside backward())")
         if self._armed:
             done = getattr(self, "_finished_in_backward", False)
             try:
@@ -250,6 +253,47 @@ class SGD(torch.optim.Optimizer, _FusedEpilogue):
             self.opt.step(self.flat.flat_g, 1.0, grad_clip=self.grad_clip)
         self._publish_state()
         return loss
+
+    def add_param_group(self, param_group):
+        if hasattr(self, "flat"):
+            raise NotImplementedError(f"{self._what}: parameter groups are fixed at construction (flat buffers)")
+        super().add_param_group(param_group)
+
+
+class SGD(_FlatOptimizer):
+    """torch.optim.SGD(params, lr, momentum, dampening=0, weight_decay, nesterov) on the flat fused path (module docstring).
+    Extra keyword arguments: comm_dtype ('fp32' | 'bf16' gradient payload), comm_algo ('allreduce' | 'rs_ag' | 'sharded': the
+    update of the GEMM weights in 1 / N slices with an all-gather of their 16-bit images, parallel.GradReducer), bucket_elems,
+    group, in_backward (update inside the backward pass; default on), grad_clip (clip by global norm inside step(), on the
+    device, instead of the loop's clip_grad_norm_ call)."""
+
+    def __init__(self, params, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
+                 nesterov: bool = False, *, maximize: bool = False, foreach=None, differentiable: bool = False, fused=None,
+                 comm_dtype: Optional[str] = None, comm_algo: Optional[str] = None, bucket_elems: int = 32 * 1024 * 1024,
+                 group=None, in_backward: Optional[bool] = None, grad_clip: Optional[float] = None):
+        if lr < 0.0 or momentum < 0.0 or weight_decay < 0.0:
+            raise ValueError("afft_amd.optim.SGD: negative lr / momentum / weight_decay")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")      # torch's own check
+        if maximize or differentiable:
+            raise NotImplementedError("afft_amd.optim.SGD: maximize / differentiable are not supported")
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov)
+        super().__init__(params, defaults)
+        g0 = self.param_groups[0]
+        for g in self.param_groups:
+            if g["dampening"] != 0:
+                raise NotImplementedError("afft_amd.optim.SGD: dampening != 0 is not supported (the reference never sets it)")
+            if g["momentum"] != g0["momentum"] or g["nesterov"] != g0["nesterov"]:
+                raise NotImplementedError("afft_amd.optim.SGD: momentum / nesterov must be the same in every group "
+                                          "(train.py:189-225 varies lr and weight_decay only)")
+        self._setup(comm_dtype, comm_algo, bucket_elems, group, in_backward, grad_clip)
+
+    def _make_engine(self):
+        g0 = self.param_groups[0]
+        return FusedSGD(self.flat, self.defaults["lr"], g0["momentum"], self.defaults["weight_decay"], nesterov=bool(g0["nesterov"]))
+
+    def _state_buffers(self) -> tuple:
+        return (self.opt.buf,)
 
     # ------------------------------------------------------------------ optimizer state <-> flat momentum buffer
     def _publish_state(self):
@@ -279,7 +323,140 @@ class SGD(torch.optim.Optimizer, _FusedEpilogue):
         # the parameters themselves are loaded by the caller (model.load_state_dict writes through the flat views in place)
         self.flat.refresh_images()
 
-    def add_param_group(self, param_group):
-        if hasattr(self, "flat"):
-            raise NotImplementedError("afft_amd.optim.SGD: parameter groups are fixed at construction (flat buffers)")
-        super().add_param_group(param_group)
+
+class Adam(_FlatOptimizer):
+    """torch.optim.Adam(params, lr, betas, eps, weight_decay, decoupled_weight_decay) on the flat path (module docstring), with the
+    extra keyword arguments of SGD (comm_dtype, comm_algo, bucket_elems, group, in_backward, grad_clip).  decoupled_weight_decay=True
+    is AdamW (as in torch).  lr and weight_decay may differ per group (schedulers drive them); betas and eps must be the same in
+    every group.  Never fused into the weight-gradient GEMM epilogues: on one GPU the update runs per bucket on the side stream
+    inside backward.  state[p] holds 'exp_avg' and 'exp_avg_sq' (views of the flat moment buffers) and 'step' (the device step
+    counter, shared); state_dict() writes 'step' per parameter as a CPU float32 tensor, so the checkpoint loads into
+    torch.optim.Adam / AdamW and theirs into this class."""
+
+    _DECOUPLED = False
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: Optional[float] = None,
+                 amsgrad: bool = False, *, foreach=None, maximize: bool = False, capturable: bool = False, differentiable: bool = False,
+                 fused=None, decoupled_weight_decay: Optional[bool] = None, comm_dtype: Optional[str] = None,
+                 comm_algo: Optional[str] = None, bucket_elems: int = 32 * 1024 * 1024, group=None, in_backward: Optional[bool] = None,
+                 grad_clip: Optional[float] = None):
+        decoupled = self._DECOUPLED if decoupled_weight_decay is None else bool(decoupled_weight_decay)
+        if weight_decay is None:
+            weight_decay = 1e-2 if decoupled else 0.0
+        if isinstance(lr, Tensor) or any(isinstance(b, Tensor) for b in betas):
+            raise NotImplementedError(f"{self._what}: a tensor lr / betas is not supported")
+        if lr < 0.0 or eps < 0.0 or weight_decay < 0.0 or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"{self._what}: invalid lr / betas / eps / weight_decay")
+        defaults = dict(lr=lr, betas=(float(betas[0]), float(betas[1])), eps=eps, weight_decay=weight_decay, amsgrad=amsgrad,
+                        maximize=maximize, foreach=foreach, capturable=capturable, differentiable=differentiable, fused=fused,
+                        decoupled_weight_decay=decoupled)
+        super().__init__(params, defaults)
+        self._constants(self.param_groups)
+        self._setup(comm_dtype, comm_algo, bucket_elems, group, in_backward, grad_clip)
+
+    def _constants(self, groups) -> tuple:
+        """(betas, eps, decoupled) of the groups: the same in every group, the options the kernels do not have absent"""
+        g0 = groups[0]
+        for g in groups:
+            if "betas" not in g or "eps" not in g:
+                raise ValueError(f"{self._what}: parameter group without betas / eps (not an Adam / AdamW configuration)")
+            for k in ("amsgrad", "maximize", "capturable", "differentiable"):
+                if g.get(k, False):
+                    raise NotImplementedError(f"{self._what}: {k}=True is not supported")
+            if isinstance(g["lr"], Tensor):
+                raise NotImplementedError(f"{self._what}: a tensor lr is not supported")
+            if (tuple(g["betas"]) != tuple(g0["betas"]) or g["eps"] != g0["eps"]
+                    or bool(g.get("decoupled_weight_decay", False)) != bool(g0.get("decoupled_weight_decay", False))):
+                raise NotImplementedError(f"{self._what}: betas / eps / decoupled_weight_decay must be the same in every group "
+                                          "(train.py:189-225 varies lr and weight_decay only)")
+        return (float(g0["betas"][0]), float(g0["betas"][1])), float(g0["eps"]), bool(g0.get("decoupled_weight_decay", False))
+
+    def _make_engine(self):
+        betas, eps, decoupled = self._constants(self.param_groups)
+        return FusedAdam(self.flat, self.defaults["lr"], betas, eps, self.defaults["weight_decay"], decoupled=decoupled)
+
+    def _state_buffers(self) -> tuple:
+        return (self.opt.exp_avg, self.opt.exp_avg_sq)
+
+    def _state_scalars(self) -> tuple:
+        return (self.opt.step_t,)
+
+    def _can_fuse(self) -> bool:
+        return False      # no GEMM-epilogue form of the Adam update
+
+    def _sync_hyper(self):
+        super()._sync_hyper()
+        self.opt.betas, self.opt.eps, self.opt.decoupled = self._constants(self.param_groups)
+
+    # ------------------------------------------------------------------ optimizer state <-> flat moment buffers
+    def _publish_state(self):
+        if getattr(self, "_state_published", False):
+            return
+        for p, o in zip(self.flat.params, self.flat.offsets):
+            n = p.numel()
+            st = self.state[p]
+            st["step"] = self.opt.step_t
+            st["exp_avg"] = self.opt.exp_avg[o:o + n].view(p.shape)
+            st["exp_avg_sq"] = self.opt.exp_avg_sq[o:o + n].view(p.shape)
+        self._state_published = True
+
+    def state_dict(self):
+        sd = super().state_dict()
+        if sd["state"]:
+            step = self.opt.step_t.detach().to("cpu", torch.float32)      # the one device read: at save time only
+            sd["state"] = {i: dict(st, step=step.clone()) for i, st in sd["state"].items()}
+        return sd
+
+    def load_state_dict(self, state_dict):
+        """a checkpoint of this class or of torch.optim.Adam / AdamW; the per-parameter steps must be equal (the flat update keeps
+        one counter)"""
+        saved = list(state_dict["state"].values())
+        if any("exp_avg" not in st or "exp_avg_sq" not in st or "step" not in st for st in saved):
+            raise ValueError(f"{self._what}.load_state_dict: not an Adam / AdamW checkpoint (per-parameter state without "
+                             "exp_avg / exp_avg_sq / step)")
+        self._constants(state_dict["param_groups"])
+        steps = {float(st["step"]) for st in saved}
+        nparams = sum(len(g["params"]) for g in state_dict["param_groups"])
+        if len(steps) > 1 or (saved and len(saved) != nparams):
+            raise ValueError(f"{self._what}.load_state_dict: the parameters have taken different numbers of steps "
+                             f"({sorted(steps) + ([0.0] if saved and len(saved) != nparams else [])}); the flat update keeps one step counter")
+        super().load_state_dict(state_dict)
+        self._group_of = self._groups_in_flat_order()
+        t = steps.pop() if steps else 0.0
+        with torch.no_grad():
+            for p, o in zip(self.flat.params, self.flat.offsets):
+                st = self.state.get(p, {})
+                n = p.numel()
+                for key, buf in (("exp_avg", self.opt.exp_avg), ("exp_avg_sq", self.opt.exp_avg_sq)):
+                    view = buf[o:o + n].view(p.shape)
+                    src = st.get(key)
+                    if src is None:
+                        view.zero_()
+                    elif src.data_ptr() != view.data_ptr():
+                        view.copy_(src)
+            self.opt.step_t.fill_(t)
+        self.opt.steps = int(t)
+        self._state_published = False
+        if saved:
+            self._publish_state()
+        else:
+            self.state.clear()
+            self._state_published = False
+        # the parameters themselves are loaded by the caller (model.load_state_dict writes through the flat views in place)
+        self.flat.refresh_images()
+
+
+class AdamW(Adam):
+    """torch.optim.AdamW(params, lr, betas, eps, weight_decay=1e-2) on the flat path: Adam with decoupled weight decay
+    (p *= 1 - lr * weight_decay before the moment update), the class conf/opt/optimizer/adamW.yaml selects.  Select it with
+    ``opt/optimizer=adamW opt.optimizer._target_=afft_amd.optim.AdamW``."""
+
+    _DECOUPLED = True
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
+                 amsgrad: bool = False, *, maximize: bool = False, foreach=None, capturable: bool = False,
+                 differentiable: bool = False, fused=None, **kwargs):
+        if "decoupled_weight_decay" in kwargs:
+            raise TypeError("AdamW.__init__() got an unexpected keyword argument 'decoupled_weight_decay'")
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, foreach=foreach, maximize=maximize, capturable=capturable,
+                         differentiable=differentiable, fused=fused, decoupled_weight_decay=True, **kwargs)

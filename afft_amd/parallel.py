@@ -219,7 +219,8 @@ class GradReducer:
         if cur > start:
             self.buckets.append((start, cur))
         self.masters_stale = False            # sharded: fp32 masters / momentum of the other ranks' slices are behind (sync_masters)
-        self.opt_buf: Optional[Tensor] = None  # sharded: the optimizer's momentum buffer (set by whoever owns the optimizer), for sync_masters
+        self.opt_buf = None                   # sharded: the optimizer's state buffer (SGD momentum) or a tuple of them (Adam's two
+                                              # moments), shaped like flat_p, set by whoever owns the optimizer: for sync_masters
         self.bucket_of = [min(b, len(self.buckets) - 1) for b in self.bucket_of]
         self._pidx = flat.index_of()
         self.expected: Optional[List[int]] = None     # ready-callbacks per bucket per step (learned on step 1)
@@ -297,7 +298,7 @@ class GradReducer:
         self.masters_stale = True           # (the momentum of the other ranks' slices at least)
 
     def sync_masters(self):
-        """Sharded update: bring the fp32 masters and the momentum of the other ranks' slices up to date (all-gather of every
+        """Sharded update: bring the fp32 masters and the optimizer state (opt_buf) of the other ranks' slices up to date (all-gather of every
         sharded bucket) -- before a checkpoint / state_dict(), or before anything else reads the fp32 values of a GEMM weight.
         A collective: every rank calls it."""
         if not self.masters_stale:
@@ -306,13 +307,14 @@ class GradReducer:
             torch.cuda.current_stream().wait_stream(self.side_stream)
             if self.opt_stream is not None:
                 torch.cuda.current_stream().wait_stream(self.opt_stream)
+        bufs = () if self.opt_buf is None else tuple(self.opt_buf) if isinstance(self.opt_buf, (tuple, list)) else (self.opt_buf,)
         with torch.no_grad():
             for (s, e) in self.buckets:
                 if e <= self.flat.split and (e - s) % self.world == 0:
                     ss, se = self.shard_of(s, e)
                     dist.all_gather_into_tensor(self.flat.flat_p[s:e], self.flat.flat_p[ss:se], group=self.group)
-                    if self.opt_buf is not None:
-                        dist.all_gather_into_tensor(self.opt_buf[s:e], self.opt_buf[ss:se], group=self.group)
+                    for buf in bufs:
+                        dist.all_gather_into_tensor(buf[s:e], buf[ss:se], group=self.group)
         self.masters_stale = False
 
     def assert_masters_fresh(self, what: str):
@@ -440,22 +442,19 @@ class GradReducer:
         return self.flat.flat_g, 1.0 / self.world
 
 
-class FusedSGD:
-    """Momentum SGD over the flat buffers (conf/opt/optimizer/sgd.yaml + expts/01: lr 1e-3, momentum 0.9, nesterov, wd 1e-6):
-    one kernel launch per contiguous slice instead of 151 parameter groups; the same kernel writes the bf16 weight images of
-    the slice.  `hyper` (optional, one (lr, weight_decay) per parameter of `flat`, set_hyper) carries the per-module values
-    train.py:189-225 allows: parameters are then updated class by class, one launch per distinct (lr, wd) and bucket."""
+class _FlatUpdate:
+    """What the fused optimizers over the flat buffers (FusedSGD, FusedAdam) share: the "step is finite" flag, the per-parameter
+    (lr, weight_decay) classes, the {start, length} runs of a class and the walk of a flat range -- parameters cut at a shard
+    edge included.  A subclass provides `_update` (one launch over a flat slice) and `_update_runs` (one launch over runs)."""
 
-    def __init__(self, flat: FlatParams, lr: float = 1e-3, momentum: float = 0.9, weight_decay: float = 1e-6,
-                 nesterov: bool = True):
-        self.flat, self.lr, self.momentum, self.wd, self.nesterov = flat, lr, momentum, weight_decay, nesterov
-        self.buf = torch.zeros_like(flat.flat_p)
+    def __init__(self, flat: FlatParams, lr: float, weight_decay: float):
+        self.flat, self.lr, self.wd = flat, lr, weight_decay
         # "the step is finite" (device float; None = no guard): the loss reduction of a step writes isfinite(loss) here when the
         # owner has put it into runtime.SINK.step_ok, and every update kernel of that step -- bucket kernels and weight-gradient
-        # epilogues alike -- leaves parameters, momentum and images untouched when it reads 0.  The reference raises 'The loss is
-        # NaN!' before backward (common/runner.py:209); with lazy metrics that error surfaces a step later, and this keeps the
-        # state it finds as the reference would have left it.  N > 1: the ranks take the MIN of their flags before the first update
-        # of the step (GradReducer._agree_ok), so a batch that is poisoned on one rank is skipped by all.
+        # epilogues alike -- leaves parameters, optimizer state and images untouched when it reads 0.  The reference raises 'The
+        # loss is NaN!' before backward (common/runner.py:209); with lazy metrics that error surfaces a step later, and this keeps
+        # the state it finds as the reference would have left it.  N > 1: the ranks take the MIN of their flags before the first
+        # update of the step (GradReducer._agree_ok), so a batch that is poisoned on one rank is skipped by all.
         self.ok: Optional[Tensor] = torch.ones((), dtype=torch.float32, device=flat.flat_p.device)
         self.steps = 0
         self.runs: Optional[Dict[tuple, Tensor]] = None    # per bucket (s, e): the runs NOT updated in a GEMM epilogue
@@ -463,9 +462,11 @@ class FusedSGD:
         self.hyper: Optional[List[tuple]] = None           # per parameter (lr, wd); None = self.lr / self.wd for all
         self._class_runs: Dict[tuple, Tensor] = {}
 
-    def flags(self) -> int:
-        """AFFT_SGD_* flag word of the update kernels (include/afft_hip.h)"""
-        return (1 if self.steps == 0 else 0) | (0 if self.nesterov else 2)
+    def _update(self, s: int, e: int, grad: Tensor, lr: float, wd: float, gscale: float, gscale_dev: Optional[Tensor]):
+        raise NotImplementedError
+
+    def _update_runs(self, runs: Tensor, lr: float, wd: float, gscale: float):
+        raise NotImplementedError
 
     def set_hyper(self, hyper: Optional[List[tuple]]):
         """one (lr, weight_decay) per parameter of the flat buffers, or None; collapses to the scalar form when all agree"""
@@ -515,13 +516,10 @@ class FusedSGD:
                 runs = self.runs.get((s, e))
                 if runs is not None:
                     if runs.shape[0]:
-                        ops.sgd_nesterov_runs(self.flat.flat_p, self.flat.flat_g, self.buf, runs, self.lr, self.momentum, self.wd,
-                                              gscale, self.flags(), p_bf16=self.flat.flat_p16, p_f16=self.flat.flat_h16, p_f8=self.flat.flat_p8, ok=self.ok)
+                        self._update_runs(runs, self.lr, self.wd, gscale)
                     self.flat.refresh_packed(s, e, skip=self.skip)
                     return
-            p16 = self.flat.flat_p16[s:e] if self.flat.flat_p16 is not None else None
-            ops.sgd_nesterov(self.flat.flat_p[s:e], grad, self.buf[s:e], self.lr, self.momentum, self.wd, gscale,
-                             self.flags(), p_bf16=p16, gscale_dev=gscale_dev, p_f16=self.flat.h16(s, e), p_f8=self.flat.p8(s, e), ok=self.ok)
+            self._update(s, e, grad, self.lr, self.wd, gscale, gscale_dev)
             self.flat.refresh_packed(s, e)
             return
         # per-parameter (lr, wd): the parameters of the range class by class.  [s, e) may cut a parameter at either end (the
@@ -537,10 +535,8 @@ class FusedSGD:
                 runs = self._runs_of(s, e, tuple(idx), fused)
                 if runs.shape[0]:
                     # the runs kernel addresses the whole flat buffers: hand it the gradient at its flat position
-                    g_full = flat.flat_g if grad.data_ptr() == flat.flat_g[s:e].data_ptr() else None
-                    if g_full is not None:
-                        ops.sgd_nesterov_runs(flat.flat_p, g_full, self.buf, runs, lr, self.momentum, wd, gscale, self.flags(),
-                                              p_bf16=flat.flat_p16, p_f16=flat.flat_h16, p_f8=flat.flat_p8, ok=self.ok)
+                    if grad.data_ptr() == flat.flat_g[s:e].data_ptr():
+                        self._update_runs(runs, lr, wd, gscale)
                         continue
                 elif fused:
                     continue
@@ -549,9 +545,7 @@ class FusedSGD:
                 if fused and id(p) in self.skip:
                     continue
                 lo, hi = max(o, s), min(o + _align(p.numel()), e)
-                p16 = flat.flat_p16[lo:hi] if flat.flat_p16 is not None else None
-                ops.sgd_nesterov(flat.flat_p[lo:hi], grad[lo - s:hi - s], self.buf[lo:hi], lr, self.momentum, wd, gscale,
-                                 self.flags(), p_bf16=p16, gscale_dev=gscale_dev, p_f16=flat.h16(lo, hi), p_f8=flat.p8(lo, hi), ok=self.ok)
+                self._update(lo, hi, grad[lo - s:hi - s], lr, wd, gscale, gscale_dev)
         self.flat.refresh_packed(s, e, skip=(self.skip if fused else ()))
 
     def end_step(self):
@@ -564,7 +558,7 @@ class FusedSGD:
         is left in self.last_grad_norm (device scalar)."""
         g = self.flat.flat_g if grad is None else grad
         coef = None
-        if grad_clip is not None and g.is_cuda:
+        if grad_clip is not None:
             ss = torch.zeros(1, dtype=torch.float32, device=g.device)
             coef = torch.empty(1, dtype=torch.float32, device=g.device)
             self.last_grad_norm = torch.empty(1, dtype=torch.float32, device=g.device)
@@ -572,6 +566,67 @@ class FusedSGD:
             ops.clip_coef(ss, grad_clip, coef, self.last_grad_norm)
         self.step_range(0, self.flat.total, g, gscale, coef)
         self.end_step()
+
+
+class FusedSGD(_FlatUpdate):
+    """Momentum SGD over the flat buffers (conf/opt/optimizer/sgd.yaml + expts/01: lr 1e-3, momentum 0.9, nesterov, wd 1e-6):
+    one kernel launch per contiguous slice instead of 151 parameter groups; the same kernel writes the bf16 weight images of
+    the slice.  `hyper` (optional, one (lr, weight_decay) per parameter of `flat`, set_hyper) carries the per-module values
+    train.py:189-225 allows: parameters are then updated class by class, one launch per distinct (lr, wd) and bucket."""
+
+    def __init__(self, flat: FlatParams, lr: float = 1e-3, momentum: float = 0.9, weight_decay: float = 1e-6,
+                 nesterov: bool = True):
+        super().__init__(flat, lr, weight_decay)
+        self.momentum, self.nesterov = momentum, nesterov
+        self.buf = torch.zeros_like(flat.flat_p)
+
+    def flags(self) -> int:
+        """AFFT_SGD_* flag word of the update kernels (include/afft_hip.h)"""
+        return (1 if self.steps == 0 else 0) | (0 if self.nesterov else 2)
+
+    def _update(self, s, e, grad, lr, wd, gscale, gscale_dev):
+        flat = self.flat
+        p16 = flat.flat_p16[s:e] if flat.flat_p16 is not None else None
+        ops.sgd_nesterov(flat.flat_p[s:e], grad, self.buf[s:e], lr, self.momentum, wd, gscale, self.flags(), p_bf16=p16,
+                         gscale_dev=gscale_dev, p_f16=flat.h16(s, e), p_f8=flat.p8(s, e), ok=self.ok)
+
+    def _update_runs(self, runs, lr, wd, gscale):
+        flat = self.flat
+        ops.sgd_nesterov_runs(flat.flat_p, flat.flat_g, self.buf, runs, lr, self.momentum, wd, gscale, self.flags(),
+                              p_bf16=flat.flat_p16, p_f16=flat.flat_h16, p_f8=flat.flat_p8, ok=self.ok)
+
+
+class FusedAdam(_FlatUpdate):
+    """Adam / AdamW (conf/opt/optimizer/adam.yaml, adamW.yaml: torch.optim.Adam / AdamW, amsgrad off) over the flat buffers, with
+    the interface of FusedSGD: exp_avg and exp_avg_sq are fp32 buffers of the shape of flat_p, the kernels write the 16-bit images of
+    what they update.  The step count the bias corrections use lives on the device (`step_t`, float): the kernels read it, end_step()
+    advances it by `ok` on the stream behind the step's last update -- a skipped (non-finite) step leaves it, and nothing waits for
+    the host.  Never fused into a GEMM epilogue (`runs` stays None): the update runs per bucket inside backward, or in step()."""
+
+    def __init__(self, flat: FlatParams, lr: float = 1e-3, betas: tuple = (0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 1e-2, decoupled: bool = True):
+        super().__init__(flat, lr, weight_decay)
+        self.betas, self.eps, self.decoupled = (float(betas[0]), float(betas[1])), float(eps), bool(decoupled)
+        self.exp_avg = torch.zeros_like(flat.flat_p)
+        self.exp_avg_sq = torch.zeros_like(flat.flat_p)
+        self.step_t = torch.zeros((), dtype=torch.float32, device=flat.flat_p.device)
+
+    def _update(self, s, e, grad, lr, wd, gscale, gscale_dev):
+        flat = self.flat
+        p16 = flat.flat_p16[s:e] if flat.flat_p16 is not None else None
+        ops.adam(flat.flat_p[s:e], grad, self.exp_avg[s:e], self.exp_avg_sq[s:e], lr, self.betas[0], self.betas[1], self.eps, wd,
+                 gscale, self.step_t, self.decoupled, p_bf16=p16, gscale_dev=gscale_dev, p_f16=flat.h16(s, e), p_f8=flat.p8(s, e),
+                 ok=self.ok)
+
+    def _update_runs(self, runs, lr, wd, gscale):
+        flat = self.flat
+        ops.adam_runs(flat.flat_p, flat.flat_g, self.exp_avg, self.exp_avg_sq, runs, lr, self.betas[0], self.betas[1], self.eps, wd,
+                      gscale, self.step_t, self.decoupled, p_bf16=flat.flat_p16, p_f16=flat.flat_h16, p_f8=flat.flat_p8, ok=self.ok)
+
+    def end_step(self):
+        with torch.no_grad():
+            self.step_t.add_(self.ok)
+        super().end_step()
 
 
 class _FusedEpilogue:

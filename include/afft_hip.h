@@ -443,6 +443,23 @@ int afft_sgd_nesterov_runs(float* p, const float* g, float* buf, void* p_bf16, c
                            float mom, float wd, float gscale, int32_t first_step, void* stream);
 int afft_sgd_nesterov_runs2(float* p, const float* g, float* buf, void* p_bf16, void* p_f16, void* p_f8, const int64_t* runs, int32_t nruns,
                             float lr, float mom, float wd, float gscale, int32_t first_step, const float* ok, void* stream);
+/* Adam / AdamW over one flat fp32 parameter buffer (conf/opt/optimizer/adam.yaml, adamW.yaml: torch.optim.Adam / AdamW with
+ * amsgrad = maximize = False), t = *step_dev + 1:
+ *   g = gscale*g (* *gscale_dev: the clipping coefficient of afft_clip_coef) ; Adam: g += wd*p ; AdamW: p *= 1 - lr*wd
+ *   m = b1*m + (1-b1)*g ; v = b2*v + (1-b2)*g*g ; p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+ *   g fp32 or bf16 (bf16 gradient exchange); p_bf16 / p_f16 / p_f8 (each optional, same element offsets as p) receive the
+ *   images of the new p as afft_sgd_nesterov2 writes them.  ok: see afft_sgd_fused_t.ok -- on 0 nothing at all is written.
+ *   1 - beta and the bias corrections are taken of the fp32 betas (as torch's fused Adam does), the latter in double.
+ *   The kernels never write *step_dev: the caller advances it by *ok once per step, behind the step's last update. */
+enum { AFFT_ADAM_DECOUPLED = 1 };   /* AdamW: decoupled weight decay */
+int afft_adam(float* p, const void* g, int32_t g_dtype, float* m, float* v, void* p_bf16, void* p_f16, void* p_f8,
+              int64_t n, float lr, float beta1, float beta2, float eps, float wd, float gscale, const float* gscale_dev,
+              const float* step_dev, int32_t flags, const float* ok, void* stream);
+/* The same update over the runs {start, length} of ONE set of flat buffers (as afft_sgd_nesterov_runs2; fp32 gradient): one
+ * launch for the parameters of one (lr, weight_decay) class of a gradient bucket. */
+int afft_adam_runs(float* p, const float* g, float* m, float* v, void* p_bf16, void* p_f16, void* p_f8,
+                   const int64_t* runs, int32_t nruns, float lr, float beta1, float beta2, float eps, float wd,
+                   float gscale, const float* step_dev, int32_t flags, const float* ok, void* stream);
 /* Gradient clipping by global norm (train.py:254-260, torch.nn.utils.clip_grad_norm_), without a host sync:
  *   afft_sumsq: *out += scale * sum x[i]^2 over a flat fp32/bf16 buffer (scale = gscale^2 of the optimizer), ordered
  *   through the stream's workspace (see afft_mse) - the clipping coefficient is bit-reproducible;
