@@ -33,8 +33,9 @@
 
 using namespace afft_gemm_detail;
 
+thread_local int afft_gemm_detail::g_launched_variant = 0;
+
 int afft_gemm_launch_pp(int a_ks, int b_ks, afft_gemm_detail::GemmFast& g, hipStream_t stream, int x3);
-bool afft_gemm_pp2_takes(int M, int N, int K, int x3);      // gemm_pp.hip: the launch runs gemm_bf16_pp2_kernel (whole tiles, even K-tile count; plain bf16 or the NT fp16 + fp8 forward; K = the caller's K)
 int afft_gemm_launch_bd(int rows160, int packed, afft_gemm_detail::GemmFast& g, hipStream_t stream);
 #ifdef AFFT_EXPERIMENT_Q4      // tools/experiments/gemm_q4.hip (tools/experiments/build_q4.sh): the four-quadrant kernel, variant 11
 int afft_gemm_launch_q4(afft_gemm_detail::GemmFast& g, hipStream_t stream);
@@ -430,6 +431,7 @@ int launch_fast(GemmFast& g, hipStream_t stream) {
       auto k2 = gemm_bf16_g2_kernel<A_KS, B_KS, SPLITK, X3 == 2>;
       static std::atomic<uint64_t> attr2_done{0};
       if (int rc = afft_ensure_dynamic_lds(reinterpret_cast<const void*>(k2), lds, &attr2_done)) return rc;
+      g_launched_variant = 12;
       hipLaunchKernelGGL(k2, dim3(g.tiles_m * g.tiles_n, g.splitk), dim3(256), lds, stream, g);
       AFFT_LAUNCH_CHECK();
       return 0;
@@ -438,6 +440,7 @@ int launch_fast(GemmFast& g, hipStream_t stream) {
   auto kern = gemm_bf16_kernel<WM, WN, STAGES, A_KS, B_KS, SPLITK, X3>;
   static std::atomic<uint64_t> attr_done{0};
   if (int rc = afft_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, &attr_done)) return rc;
+  g_launched_variant = STAGES == 4 ? 4 : 1;
   hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n, g.splitk), dim3(64 * WM * WN), lds, stream, g);
   AFFT_LAUNCH_CHECK();
   return 0;
@@ -492,12 +495,10 @@ int launch_layout(GemmFast& g, hipStream_t stream, const afft_gemm_t* d) {
   }
   if (hipEventCreate(&t.a) != hipSuccess || hipEventCreate(&t.b) != hipSuccess) { (void)hipGetLastError(); return launch_layout_impl<A_KS, B_KS>(g, stream, d); }
   (void)hipEventRecord(t.a, stream);
+  g_launched_variant = 0;
   const int rc = launch_layout_impl<A_KS, B_KS>(g, stream, d);
   (void)hipEventRecord(t.b, stream);
-  int variant = choose_variant(g.e.M, g.e.N, g.K, A_KS, B_KS);
-  if (!A_KS && !B_KS && d->b_packed && !d->split3 && g_variant == 0 && g.ldb == d->K && bd_packed_wins(g.e.M, g.e.N, g.K)) variant = 10;
-  if (variant == 3 && afft_gemm_pp2_takes(g.e.M, g.e.N, d->K, d->split3)) variant = 13;      // the steady-state 256x256 kernel (gemm_bf16_pp2_kernel)
-  t.r = afft_gemm_trace_rec_t{g.e.M, g.e.N, d->K, A_KS, B_KS, variant, g.splitk, d->split3, d->sgd != nullptr, 0.f};
+  t.r = afft_gemm_trace_rec_t{g.e.M, g.e.N, d->K, A_KS, B_KS, g_launched_variant, g.splitk, d->split3, d->sgd != nullptr, 0.f};
   std::lock_guard<std::mutex> lk(g_trace_mu);
   if (g_trace) g_trace->push_back(t);
   return rc;

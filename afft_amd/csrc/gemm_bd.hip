@@ -277,6 +277,7 @@ int launch_bd(GemmFast& g, hipStream_t stream) {
   auto kern = gemm_bf16_bd_kernel<NI, PA, PB, PACKED>;
   static std::atomic<uint64_t> attr_done{0};
   if (int rc = afft_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, &attr_done)) return rc;
+  g_launched_variant = (NI == 10 ? 8 : 7) + (PACKED ? 2 : 0);      // 7 / 8 row-major B, 9 / 10 fragment-packed B
   hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n), dim3(256), lds, stream, g);
   AFFT_LAUNCH_CHECK();
   return 0;

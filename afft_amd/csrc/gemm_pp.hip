@@ -728,6 +728,7 @@ int launch_pp2(GemmFast& g, hipStream_t stream) {
   auto kern = gemm_bf16_pp2_kernel<A_KS, B_KS, X3>;
   static std::atomic<uint64_t> attr_done{0};
   if (int rc = afft_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, &attr_done)) return rc;
+  g_launched_variant = 13;
   hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n), dim3(512), lds, stream, g);
   AFFT_LAUNCH_CHECK();
   return 0;
@@ -742,6 +743,7 @@ int launch_pp(GemmFast& g, hipStream_t stream) {
   static std::atomic<uint64_t> attr_done{0};
   if (int rc = afft_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, &attr_done)) return rc;
   const int grid = g.tiles_m * g.tiles_n;
+  g_launched_variant = 3;
 #ifdef AFFT_PP_STAMP
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, g, g_pp_stamp);
 #else
@@ -757,13 +759,6 @@ int launch_pp(GemmFast& g, hipStream_t stream) {
 #ifdef AFFT_PP_STAMP
 extern "C" void afft_debug_pp_stamp(void* p) { g_pp_stamp = (unsigned long long*)p; }
 #endif
-
-bool afft_gemm_pp2_takes(int M, int N, int K, int x3) {      // K: the caller's K (one segment)
-  if (x3 == 3) { const int ns = K / BK; return AFFT_PP2 && M % 256 == 0 && N % 256 == 0 && ns % 4 == 0 && ns >= 4; }
-  if (x3 == 1 || x3 == 2) { const int ns = K / BK; return AFFT_PP2 && M % 256 == 0 && N % 256 == 0 && ns % 2 == 0 && ns >= 2; }
-  if (x3 == 4) { const int ns = K / BK; return AFFT_PP2 && M % 256 == 0 && N % 256 == 0 && ns % 2 == 0 && ns >= 4; }
-  return x3 == 0 && pp2_shape(M, N, K);
-}
 
 int afft_gemm_launch_pp(int a_ks, int b_ks, afft_gemm_detail::GemmFast& g, hipStream_t stream, int x3) {
 #ifndef AFFT_PP_NT_ONLY   // development switch: build only the plain NT instantiation (compile time)

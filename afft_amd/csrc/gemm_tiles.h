@@ -42,6 +42,10 @@ struct GemmFast {
   EpiParams e;
 };
 
+// the trace variant (afft_gemm_trace_rec_t.variant) of the kernel the last fast-path launch of this thread ran: written by the
+// launcher that launches (gemm.hip launch_fast, gemm_pp.hip launch_pp / launch_pp2, gemm_bd.hip launch_bd), read by the trace hook
+extern thread_local int g_launched_variant;
+
 // global K-tile index -> K offset inside the segment and the operand planes of that segment (wave-uniform SALU work)
 // the MFMA of every bf16-path kernel: 16-bit operands by the instantiation's plane format (X3 = 2: fp16, else bf16)
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;

@@ -4,6 +4,7 @@ Tolerances: fp32 kernels 2e-5 relative-L2 (exact-fp32 MFMA, different summation 
 bf16-operand kernels 1e-2 (bf16 rounding of the inputs is applied to the reference too, so what is
 left is accumulation order + output rounding)."""
 import math
+import zlib
 
 import pytest
 import torch
@@ -1334,6 +1335,336 @@ def test_errors_are_reported():
         ops.gemm(a, torch.zeros(5, 4, device=dev()), a)
 
 
+# ----------------------------------------------------------------------------- every GEMM kernel instantiation, exactly against float64
+# The case table (tests/gemm_cases.py) names for every case the kernel the dispatcher must run; test_gemm_coverage_cpu.py checks that
+# every instantiation the library compiles has a case.  Each case runs on EXACT operands: integers times a power of two, small enough
+# that every partial sum of the kernel's formula is an fp32 number, so the MFMA result does not depend on the summation order and must
+# equal the float64 product bit for bit (fp32 outputs) or that product rounded once (16-bit outputs).  A local failure -- one fragment,
+# one tile, one K pair, one wrong operand plane -- shows in the one element it touches, which a relative-L2 bar cannot promise.
+# Every operand element the kernel is not handed (beyond M, N or K inside the allocation) is NaN, and every output-shaped view sits in a
+# larger buffer whose other bits are a sentinel: a read outside the problem turns an output NaN, a write outside it breaks the sentinel.
+from gemm_cases import CASES as GEMM_TABLE  # noqa: E402
+from gemm_cases import DGELU_ERF, DGELU_TANH, GELU_ERF, GELU_TANH, RELU, SIGMOID_GATE  # noqa: E402
+
+_TDT = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
+_SENTINEL = {torch.float32: (torch.int32, 0x7FC0DEAD), torch.bfloat16: (torch.int16, 0x7DAD), torch.float16: (torch.int16, 0x7DAD),
+             torch.uint8: (torch.uint8, 0xA5)}
+_E4M3_OF_INT = (0xC0, 0xB8, 0x00, 0x38, 0x40)      # e4m3fn codes of -2 .. 2
+_ACT_TOL = {GELU_ERF: 1e-6, GELU_TANH: 1e-6, DGELU_ERF: 1e-6, DGELU_TANH: 4e-6, SIGMOID_GATE: 1e-6}     # test_epilogue_activation_accuracy
+
+
+def _traced_symbol(r):
+    """afft_gemm_trace_rec_t -> the kernel symbol (as nm -C prints it) that the launcher recorded"""
+    b = lambda x: "true" if x else "false"    # noqa: E731
+    a, bb, sk = b(r.a_kstrided), b(r.b_kstrided), b(r.splitk > 1)
+    x3 = 2 if r.split3 == 4 else int(r.split3)      # one fp16 pass runs the two-pass instantiation over one segment
+    if r.variant in (1, 4):
+        return f"gemm_bf16_kernel<2, 2, {2 if r.variant == 1 else 4}, {a}, {bb}, {sk}, {x3}>"
+    if r.variant == 12:
+        return f"gemm_bf16_g2_kernel<{a}, {bb}, {sk}, {b(x3 == 2)}>"
+    if r.variant in (3, 13):
+        return f"gemm_bf16_{'pp' if r.variant == 3 else 'pp2'}_kernel<{a}, {bb}, {x3}>"
+    if r.variant in (7, 8, 9, 10):
+        rows160 = r.variant in (8, 10)
+        return f"gemm_bf16_bd_kernel<{10 if rows160 else 16}, 3, {2 if rows160 else 1}, {b(r.variant >= 9)}>"
+    return f"<trace variant {r.variant}>"
+
+
+def _ints(shape, amp, sh, gen):
+    return torch.randint(-amp, amp + 1, shape, generator=gen, device=dev()).double() * 2.0 ** -sh
+
+
+def _nan_padded(t, dtype, ld=0, col0=0):
+    """t [R, C] (float64, exact in `dtype`) inside a NaN-filled [R + 2, ld] buffer (row pitch ld, by default a little wider than C, a
+    multiple of 8 elements, of 16 for e4m3 byte planes), starting at column col0: the view the GEMM gets; whatever it may read of the
+    rest is NaN"""
+    R, C = t.shape
+    al = 16 if dtype == torch.uint8 else 8
+    ld = ld or (col0 + C + al + (-(col0 + C)) % al)
+    buf = torch.full((R + 2, ld), 0x7F if dtype == torch.uint8 else float("nan"), dtype=dtype, device=dev())
+    v = buf[:R, col0:col0 + C]
+    v.copy_(t.to(dtype))
+    return v
+
+
+class _Fenced:
+    """an output-shaped [M, N] view (planes of them for out_lo) inside a buffer with one row above, one below and spare columns,
+    everything outside the view set to a sentinel bit pattern (or NaN, for operands the epilogue reads)"""
+
+    def __init__(self, M, N, dtype, ldo, col0, planes=1, nan=False):
+        self.buf = torch.empty(planes, M + 2, ldo, dtype=dtype, device=dev())
+        if nan:
+            self.buf.fill_(float("nan"))
+        else:
+            idt, s = _SENTINEL[dtype]
+            self.buf.view(idt).fill_(s)
+        self.mask = torch.zeros(self.buf.shape, dtype=torch.bool, device=dev())
+        self.mask[:, 1:M + 1, col0:col0 + N] = True
+        self.views = [self.buf[p, 1:M + 1, col0:col0 + N] for p in range(planes)]
+        self.v = self.views[0]
+
+    def intact(self):
+        idt, s = _SENTINEL[self.buf.dtype]
+        return bool((self.buf.view(idt)[~self.mask] == s).all())
+
+
+def _act64(act, x, aux):
+    if act == GELU_ERF:
+        return 0.5 * x * (1.0 + torch.erf(x / math.sqrt(2.0)))
+    if act == GELU_TANH:
+        return 0.5 * x * (1.0 + torch.tanh(math.sqrt(2.0 / math.pi) * (x + 0.044715 * x ** 3)))
+    if act == DGELU_ERF:
+        return x * (0.5 * (1.0 + torch.erf(aux / math.sqrt(2.0))) + aux * torch.exp(-0.5 * aux * aux) / math.sqrt(2.0 * math.pi))
+    if act == DGELU_TANH:
+        t = torch.tanh(math.sqrt(2.0 / math.pi) * (aux + 0.044715 * aux ** 3))
+        return x * (0.5 * (1.0 + t) + 0.5 * aux * (1.0 - t * t) * math.sqrt(2.0 / math.pi) * (1.0 + 3 * 0.044715 * aux * aux))
+    if act == RELU:
+        return x.clamp_min(0.0)
+    if act == SIGMOID_GATE:
+        return aux / (1.0 + torch.exp(-x))
+    return x
+
+
+def _operands(c, A, Bm, gen, exact):
+    """the ops.gemm operands of case c for the logical float64 product A [M, K] @ Bm [K, N] -> (a, b, extra ops.gemm arguments,
+    the product the kernel's formula computes on them, the same sum over the magnitudes of its terms)"""
+    from afft_amd import ops
+    a_t, b_t = c.layout[0] == "t", c.layout[1] == "t"
+    At, Bt = (A.t() if a_t else A), (Bm.t() if b_t else Bm)      # stored orientation
+    lda = c.ld if a_t else 0
+    ldb = c.ld if not b_t else 0
+    kw = {}
+    if c.mode in ("bf16", "f32"):
+        dt = torch.float32 if c.mode == "f32" else torch.bfloat16
+        a = _nan_padded(At, dt, lda, col0=c.epi.get("a_off", 0))
+        b = _nan_padded(Bt, dt, ldb)
+        if c.variant == 9:      # the forced packed variant reads B as the fragment-packed image of the weight [N, K]
+            pk = torch.empty(c.N * c.K, dtype=torch.bfloat16, device=dev())
+            ops.pack_weight(Bt.float().contiguous(), pk)
+            b = pk.view(c.N, c.K)
+        elif c.epi.get("packed"):      # b_packed with the row-major weight, unpadded (the B-direct path wants b_cs == K)
+            pk = torch.empty(c.N * c.K, dtype=torch.bfloat16, device=dev())
+            ops.pack_weight(Bt.float().contiguous(), pk)
+            b = _nan_padded(Bt, dt, c.K)
+            kw["b_packed"] = pk
+        return a, b, kw, A @ Bm, A.abs() @ Bm.abs()
+    # split modes: the planes are built here, so the lo planes carry values of their own (dyadic, non-zero) -- a read of the wrong
+    # plane or segment shows.  ops.Split's documented contract is kept: planes padded to 64 with zero tails.
+    f16 = c.mode != "bf16x3"
+    pdt = torch.float16 if f16 else torch.bfloat16
+    lo_sh = c.sh + 4
+
+    def split(X):
+        R, C = X.shape
+        sp = ops.Split.__new__(ops.Split)
+        sp.planes = torch.zeros(2, (R + 63) // 64 * 64, (C + 63) // 64 * 64, dtype=pdt, device=dev())
+        lo = _ints((R, C), 2, lo_sh, gen) if exact else (X - X.to(pdt).double()).to(pdt).double()
+        sp.planes[0, :R, :C] = X.to(pdt)
+        sp.planes[1, :R, :C] = lo.to(pdt)
+        sp.rows, sp.cols, sp.f16 = R, C, f16
+        return sp, sp.planes[0, :R, :C].double(), lo
+
+    if c.mode == "bf16x3":
+        sa, Ahi, Alo = split(At)
+        sb, Bhi, Blo = split(Bt)
+        Ahi, Alo = (Ahi.t(), Alo.t()) if a_t else (Ahi, Alo)
+        Bhi, Blo = (Bhi.t(), Blo.t()) if b_t else (Bhi, Blo)
+        ref = Ahi @ Bhi + Alo @ Bhi + Ahi @ Blo      # the kernel's formula: lo x lo is not computed
+        return sa, sb, kw, ref, Ahi.abs() @ Bhi.abs() + Alo.abs() @ Bhi.abs() + Ahi.abs() @ Blo.abs()
+    b = _nan_padded(Bt, torch.float16)
+    if c.mode == "fp16x2":
+        sa, Ahi, Alo = split(A)
+        return sa, b, kw, (Ahi + Alo) @ Bm, (Ahi.abs() + Alo.abs()) @ Bm.abs()
+    a = _nan_padded(A, torch.float16)
+    if c.mode == "fp16":
+        return a, b, kw, A @ Bm, A.abs() @ Bm.abs()
+    # fp16 + fp8 lo pass: hi A_hi W16 on the fp16 MFMA, then 2^-19 a8 b8 over e4m3 byte planes (here: codes of the integers -2 .. 2)
+    ia, ib = torch.randint(-2, 3, (c.M, c.K), generator=gen, device=dev()), torch.randint(-2, 3, (c.N, c.K), generator=gen, device=dev())
+    codes = torch.tensor(_E4M3_OF_INT, dtype=torch.uint8, device=dev())
+    kw["a8"] = _nan_padded(codes[ia + 2].double(), torch.uint8)
+    kw["b8"] = _nan_padded(codes[ib + 2].double(), torch.uint8)
+    lo = (ia.double() @ ib.double().t()) * 2.0 ** -19
+    return a, b, kw, A @ Bm + lo, A.abs() @ Bm.abs() + (ia.double().abs() @ ib.double().abs().t()) * 2.0 ** -19
+
+
+def _run_traced(c, a, b, out, **kw):
+    from afft_amd import _lib, ops
+    _lib.check(_lib.lib().afft_gemm_trace_begin(8))
+    try:
+        ops.gemm(a, b, out, a_t=c.layout[0] == "t", b_t=c.layout[1] == "t", **kw)
+    finally:
+        buf = (_lib.GemmTraceRec * 8)()
+        n = _lib.lib().afft_gemm_trace_end(buf, 8)
+    torch.cuda.synchronize()
+    return [_traced_symbol(buf[i]) for i in range(n)]
+
+
+def _check_kernel(c, ran):
+    if c.fast:
+        assert ran == [c.kernel], f"{c.name}: ran {ran}, the case is written for {c.kernel}"
+    else:
+        assert ran == [], f"{c.name}: the exact-fp32 kernel was expected, the fast path ran {ran}"
+
+
+def _exact_pass(c):
+    ep = c.epi
+    gen = torch.Generator(device=dev()).manual_seed(zlib.crc32(c.name.encode()))
+    M, N, K = c.M, c.N, c.K
+    A, Bm = _ints((M, K), c.amp, c.sh, gen), _ints((K, N), c.amp, c.sh, gen)
+    a, b, kw, prod, absprod = _operands(c, A, Bm, gen, exact=True)
+    # exactness: every term is a multiple of 2^-q and the sum of their magnitudes stays below 2^(24 - q), so every partial sum the
+    # kernel forms, in any order, is an fp32 number
+    q = {"bf16": 2 * c.sh, "f32": 2 * c.sh, "fp16": 2 * c.sh, "bf16x3": 2 * c.sh + 4, "fp16x2": 2 * c.sh + 4, "fp16_lo8": 19}[c.mode]
+    assert float(absprod.max()) * 2.0 ** q < 2.0 ** 24, (c.name, float(absprod.max()))
+    ldo = ep.get("ldo") or (ep.get("col0", 0) + N + 8 + (-(ep.get("col0", 0) + N)) % 8)
+    col0 = ep.get("col0", 0)
+    odt = _TDT[ep.get("out", "f32")]
+    out = _Fenced(M, N, odt, ldo, col0, planes=2 if ep.get("out_lo") else 1)
+    alpha = ep.get("alpha", 1.0)
+    stages = [alpha * prod]
+    v = stages[-1]
+    if ep.get("bias"):
+        bias_buf = torch.full((col0 + N + 8,), float("nan"), device=dev())
+        kw["bias"] = bias_buf[col0:col0 + N]
+        kw["bias"].copy_(_ints((N,), 8, 2, gen))
+        v = v + kw["bias"].double()
+        stages.append(v)
+    pre_ref = v
+    act = ep.get("act", 0)
+    aux = None
+    if act in (DGELU_ERF, DGELU_TANH, SIGMOID_GATE):
+        aux = _Fenced(M, N, torch.float32, ldo, col0, nan=True)
+        aux.v.copy_(_ints((M, N), 12, 2, gen))
+        kw["aux"] = aux.v
+    exact_act = act in (0, RELU)      # after any other activation the result is compared within its bound, not bitwise
+    if act:
+        kw["act"] = act
+        v = _act64(act, v, None if aux is None else aux.v.double())
+        if exact_act:
+            stages.append(v)
+    rs = None
+    if ep.get("rowscale"):
+        rs_buf = torch.full((M + 8,), float("nan"), device=dev())
+        rs = rs_buf[:M]
+        rs.copy_(_ints((M,), 2, 1, gen).abs() + 0.5)
+        kw["rowscale"] = rs
+        v = v * rs.double()[:, None]
+        stages += [v] if exact_act else []
+    if ep.get("residual"):
+        res = _Fenced(M, N, torch.float32, ldo, col0, nan=True)
+        res.v.copy_(_ints((M, N), 8, 2, gen))
+        kw["residual"] = res.v
+        v = v + res.v.double()
+        stages += [v] if exact_act else []
+    if ep.get("accumulate"):
+        out.v.copy_(_ints((M, N), 8, 2, gen))
+        kw["accumulate"] = True
+        v = v + out.v.double()
+        stages += [v] if exact_act else []
+    ref = v
+    for s in stages:
+        assert torch.equal(s, s.float().double()), f"{c.name}: an epilogue stage is not exact in fp32"
+    fences = [out]
+    pre = out2 = lo8 = None
+    if ep.get("pre"):
+        pre = _Fenced(M, N, _TDT[ep["pre"]], ldo, col0)
+        kw["pre"] = pre.v
+        fences.append(pre)
+    if ep.get("out2"):
+        out2 = _Fenced(M, N, _TDT[ep["out2"]], ldo, col0)
+        kw["out2"] = out2.v
+        fences.append(out2)
+    if ep.get("out_lo"):
+        kw["out_lo"] = out.buf[0].numel()
+    if ep.get("out_lo8"):
+        lo8 = _Fenced(M, N, torch.uint8, ldo, col0)
+        kw["out_lo8"] = lo8.v
+        fences.append(lo8)
+    if alpha != 1.0:
+        kw["alpha"] = alpha
+    if odt == torch.float16:
+        assert float(ref.abs().max()) < 65504.0
+    _check_kernel(c, _run_traced(c, a, b, out.v, **kw))
+
+    def same(got, want, what):
+        if not torch.equal(got, want):
+            bad = (got != want).nonzero()
+            i, j = (int(x) for x in bad[0])
+            raise AssertionError(f"{c.name}: {what} differs in {bad.shape[0]} of {got.numel()} elements, first at [{i}, {j}]: "
+                                 f"{float(got[i, j])} instead of {float(want[i, j])}")
+
+    def close(got, what):      # activated output: the activation's own error (scaled by what follows it) + the output rounding
+        tol = _ACT_TOL[act] * (pre_ref.abs().clamp_min(1.0) if act in (GELU_ERF, GELU_TANH) else
+                               aux.v.double().abs().clamp_min(1.0) if act == SIGMOID_GATE else pre_ref.abs())
+        if rs is not None:
+            tol = tol * rs.double()[:, None]
+        tol = tol + 2.0 ** -20 * ref.abs() + (0.0 if got.dtype == torch.float32 else ref.abs() * 2.0 ** (-8 if got.dtype == torch.bfloat16 else -10))
+        err = (got.double() - ref).abs()
+        assert not torch.isnan(got).any() and bool((err <= tol).all()), (c.name, what, float((err - tol).max()))
+
+    for view, what in ((out.v, "out"), (None if out2 is None else out2.v, "out2")):
+        if view is None:
+            continue
+        if exact_act:
+            same(view, ref.float().to(view.dtype), what)
+        else:
+            close(view, what)
+    if pre is not None:
+        same(pre.v, pre_ref.float().to(pre.v.dtype), "pre")
+    if ep.get("out_lo"):
+        r32 = ref.float()
+        same(out.views[1], (r32 - r32.half().float()).half(), "out_lo plane")
+    if lo8 is not None:
+        r32 = ref.float().cpu()
+        want = ((r32 - r32.half().float()) * 2048.0).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).view(torch.uint8)
+        same(lo8.v.cpu(), want, "out_lo8 plane")
+    for f in fences:
+        assert f.intact(), f"{c.name}: a store outside the output view"
+
+
+def _realistic_pass(c):
+    """bf16-rounded normal operands (fp32 for the fp32 kernel), the plain product: elementwise within the rigorous bound of fp32
+    accumulation, 2 K 2^-24 (|A| |B|)_ij (+ one rounding of a 16-bit output), which a dropped K-tile breaks in any single element"""
+    gen = torch.Generator(device=dev()).manual_seed(7 + zlib.crc32(c.name.encode()))
+    A = torch.randn(c.M, c.K, generator=gen, device=dev(), dtype=torch.float64)
+    Bm = torch.randn(c.K, c.N, generator=gen, device=dev(), dtype=torch.float64)
+    if c.mode != "f32":
+        A, Bm = A.to(torch.bfloat16).double(), Bm.to(torch.bfloat16).double()
+    else:
+        A, Bm = A.float().double(), Bm.float().double()
+    a, b, kw, ref, absprod = _operands(c, A, Bm, gen, exact=False)
+    odt = torch.float32 if c.epi.get("out", "f32") == "f16" else _TDT[c.epi.get("out", "f32")]
+    out = torch.full((c.M, c.N), float("nan"), dtype=odt, device=dev())
+    _check_kernel(c, _run_traced(c, a, b, out, **kw))
+    tol = 2.0 * c.K * 2.0 ** -24 * absprod + (0.0 if odt == torch.float32 else 2.0 ** -8 * ref.abs())
+    err = (out.double() - ref).abs()
+    ok = err <= tol
+    if not bool(ok.all()):
+        i, j = (int(x) for x in (~ok).nonzero()[0])
+        raise AssertionError(f"{c.name}: {int((~ok).sum())} elements outside the accumulation bound, first [{i}, {j}]: "
+                             f"{float(out[i, j])} vs {float(ref[i, j])} (bound {float(tol[i, j]):.3g})")
+
+
+@pytest.mark.parametrize("case", GEMM_TABLE, ids=lambda c: c.name)
+def test_gemm_instantiation_exact(case):
+    """One case of tests/gemm_cases.py: the launch ran the case's kernel (GEMM trace), the result on exact operands equals float64
+    (fp32 outputs bitwise; 16-bit outputs and planes = float64 rounded once; activations within their established bounds), nothing
+    outside M x N x K was read or outside the output views written; plain bf16 / fp32 kernels also on realistic operands."""
+    from afft_amd import _lib
+    _lib.check(_lib.lib().afft_set_gemm_variant(case.variant))
+    _lib.check(_lib.lib().afft_set_gemm_splitk(case.splitk))
+    try:
+        _exact_pass(case)
+        if case.mode in ("bf16", "f32") and not case.ld:      # (the 32-bit-walk cases are about addressing: the exact pass covers it)
+            _realistic_pass(case)
+    finally:
+        torch.cuda.synchronize()
+        _lib.check(_lib.lib().afft_set_gemm_variant(0))
+        _lib.check(_lib.lib().afft_set_gemm_splitk(1))
+        if case.ld:
+            torch.cuda.empty_cache()      # the two 4 GiB operands
+
+
 # ----------------------------------------------------------------------------- race net of the LDS-ring GEMM kernels
 def _lds_pressure_mix(stream, bufs, rounds=1):
     """What shares a CU with a 128-KiB GEMM workgroup inside the training step: the SMALL-register kernels of the other stream
@@ -1435,8 +1766,15 @@ def test_lds_ring_kernels_are_bitwise_stable_under_lds_pressure(case):
         first = torch.empty(M, N, dtype=odt, device=dev())
         launch(first)
         torch.cuda.synchronize()
-        ref = ((A.float().t() if a_t else A.float()).double() @ (Bm.float().t() if b_t else Bm.float()).double()).float()
+        La, Lb = (A.float().t() if a_t else A.float()).double(), (Bm.float().t() if b_t else Bm.float()).double()
+        ref64 = La @ Lb
+        ref = ref64.float()
         assert rel_l2(first.float().cpu(), ref.cpu()) < 5e-3
+        if not planes:      # elementwise, within the rigorous bound of fp32 accumulation (+ one rounding of a bf16 output)
+            tol = 2.0 * K * 2.0 ** -24 * (La.abs() @ Lb.abs()) + (2.0 ** -8 * ref64.abs() if odt == torch.bfloat16 else 0.0)
+            over = int(((first.double() - ref64).abs() > tol).sum())
+            assert over == 0, f"{name}: launch 0 has {over} elements outside the accumulation bound"
+            del La, Lb, ref64, tol
         n = 2000
         for i in range(0, n, 4):
             _lds_pressure_mix(side, bufs)

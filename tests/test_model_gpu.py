@@ -638,10 +638,11 @@ def test_full_size_training_is_bitwise_reproducible_and_fused_update_bitwise_equ
         assert torch.equal(f1[i], s1[i]), f"{what}: fused update differs from the separate update"
 
 
-def test_gemm_trace_hook_brackets_every_launch():
+def test_gemm_trace_hook_records_the_kernel_each_launch_ran():
     """afft_gemm_trace_begin / _end (bench.py's roofline source): one record per bf16 fast-path launch, from afft_gemm and from
-    inside a composite call alike, with plausible durations."""
-    import ctypes
+    inside a composite call alike, with plausible durations, and the variant of the kernel that launch ran (set by its launcher):
+    whole 128x128 tiles with an even K-tile count run the steady-state kernel (12, gemm_bf16_g2_kernel), ragged tiles the general
+    128x128 kernel (1)."""
     from afft_amd import _lib, ops
     dev = torch.device("cuda:0")
     a = torch.randn(512, 256, device=dev).to(torch.bfloat16)
@@ -650,13 +651,16 @@ def test_gemm_trace_hook_brackets_every_launch():
     _lib.check(_lib.lib().afft_gemm_trace_begin(16))
     for _ in range(3):
         ops.gemm(a, b, out, b_t=True)
+    ops.gemm(a[:500], b, out[:500], b_t=True)                    # 500 rows: a partial tile row
     ops.gemm(a.float(), b.float(), out.float(), b_t=True)      # exact-fp32 path: not traced
     buf = (_lib.GemmTraceRec * 16)()
     n = _lib.lib().afft_gemm_trace_end(buf, 16)
-    assert n == 3
-    for i in range(n):
+    assert n == 4
+    for i in range(3):
         r = buf[i]
-        assert (r.M, r.N, r.K, r.a_kstrided, r.b_kstrided, r.variant) == (512, 384, 256, 0, 0, 1) and 0.0 < r.ms < 5.0
+        assert (r.M, r.N, r.K, r.a_kstrided, r.b_kstrided, r.variant) == (512, 384, 256, 0, 0, 12) and 0.0 < r.ms < 5.0
+    r = buf[3]
+    assert (r.M, r.N, r.K, r.a_kstrided, r.b_kstrided, r.variant) == (500, 384, 256, 0, 0, 1) and 0.0 < r.ms < 5.0
     assert _lib.lib().afft_gemm_trace_end(buf, 16) < 0       # no trace open
 
 
