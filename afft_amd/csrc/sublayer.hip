@@ -2,6 +2,7 @@
 // launched through the primitive entry points of this library, in the order and with the arguments the call-by-call path
 // (afft_amd/functional.py) uses; weight-gradient GEMMs and bias column sums go to the auxiliary stream behind an event.
 #include "common.h"
+#include <initializer_list>
 
 namespace {
 
@@ -13,6 +14,9 @@ int stream_follows(hipStream_t to, hipStream_t from) { return afft_stream_follow
 int pad64(int n) { return (n + 63) / 64 * 64; }
 
 struct Ws { void* p; int64_t bytes; };
+// GEMM workspace of the main stream, and of the auxiliary stream of a backward (the main one again when the two streams are one)
+template <class S> Ws main_ws(const S* s) { return {s->gemm_ws, s->gemm_ws_bytes}; }
+template <class S> Ws aux_ws(const S* s, bool same_stream) { return same_stream ? main_ws(s) : Ws{s->gemm_ws_aux, s->gemm_ws_aux_bytes}; }
 
 afft_gemm_t gemm_base(int M, int N, int K, Ws ws) {
   afft_gemm_t g = {};
@@ -66,6 +70,34 @@ int zero_row_tail(void* buf, int rows, int64_t width, hipStream_t st) {
 
 bool has_drop(const afft_dropout_t& d) { return d.p > 0.f || d.path_p > 0.f; }
 
+// dya[rows, d] = bf16(dy) with the output dropout replayed, unless the LayerNorm backward downstream handed it over (dya_ready)
+int prepare_dya(const float* dy, void* dya, int rows, int d, const afft_dropout_t& out_drop, int dya_ready, hipStream_t st) {
+  if (dya_ready) return 0;
+  TRY(zero_row_tail(dya, rows, d, st));
+  return afft_cast(dy, d, rows, d, dya, d, AFFT_BF16, nullptr, 0, 0, has_drop(out_drop) ? &out_drop : nullptr, st);
+}
+
+// Side work of the output projection y = x W + b over `rows` rows of x [rows, k_in] (row pitch ldx): the weight gradient, and the bias column sum
+// -- of dya where output dropout is on (dy has not seen the mask), of the fp32 dy otherwise.
+int out_proj_side(const void* dya, const float* dy, bool od, int d, const void* x, int64_t ldx, int k_in, int rows, bool conv1d, float* g_w,
+                  int acc_w, const afft_sgd_fused_t* sgd_w, float* g_b, int acc_b, Ws wsa, hipStream_t aux) {
+  TRY(wgrad(dya, d, d, x, ldx, k_in, rows, conv1d, g_w, acc_w, wsa, aux, sgd_w));
+  if (!g_b) return 0;
+  return od ? afft_colsum(dya, d, AFFT_BF16, rows, d, g_b, acc_b, wsa.p, wsa.bytes, aux)
+            : afft_colsum(dy, d, AFFT_F32, rows, d, g_b, acc_b, wsa.p, wsa.bytes, aux);
+}
+
+// The data-gradient GEMM(s) of a linear layer on `st`, and its side work (weight gradient, bias column sum) on `aux` behind everything
+// enqueued on `st` so far: beside the data gradient -- unless the weight gradient carries a fused update (`fused`), which rewrites the
+// weight's bf16 image: enqueued behind the data-gradient GEMM that reads that image (one event later than the plain form).
+template <class Side>
+int dgrad_beside_or_before(bool fused, Side side, std::initializer_list<afft_gemm_t> dgrads, hipStream_t st, hipStream_t aux) {
+  if (!fused) { TRY(stream_follows(aux, st)); TRY(side()); }
+  for (const afft_gemm_t& g : dgrads) TRY(afft_gemm(&g, st));
+  if (fused) { TRY(stream_follows(aux, st)); TRY(side()); }
+  return 0;
+}
+
 // "fp16x2" forward: A is a two-plane fp16 split (lo plane a_lo elements behind the hi plane), the weight an FP16 image
 void as_f16x2(afft_gemm_t& g, int64_t a_lo) { g.split3 = 2; g.a_lo = a_lo; g.b_lo = 0; g.b_packed = nullptr; }
 // ... or ONE fp16 pass on A's hi plane (AFFT_F16X2_ONE_PASS_* sites)
@@ -88,7 +120,7 @@ extern "C" int afft_attn_sublayer_fwd(const afft_attn_sublayer_t* s, void* strea
   const int R = s->rows, d = s->d;
   const int take = s->take > 1 ? s->take : 1, Ry = R / take;      // rows that leave the sub-layer (token 0 of every `take` rows)
   AFFT_CHECK(take == 1 || (take == s->L && Ry % 64 == 0), "attn_sublayer_fwd: take must be L, with rows / take a multiple of 64");
-  const Ws ws = {s->gemm_ws, s->gemm_ws_bytes};
+  const Ws ws = main_ws(s);
   if (s->f16x2) {
     // fp16 two-pass forward: every activation a GEMM reads is carried as hi + lo fp16 planes written by its producer (LayerNorm,
     // the qkv epilogue, the attention kernel); the bf16 copies (xn_b / qkv_b / ao_b) are what the bf16 backward reads
@@ -151,47 +183,30 @@ extern "C" int afft_attn_sublayer_bwd(const afft_attn_sublayer_t* s, void* strea
   const int R = s->rows, d = s->d;
   const int take = s->take > 1 ? s->take : 1, Ry = R / take;      // see afft_attn_sublayer_fwd: dy / dya are [Ry, d]
   AFFT_CHECK(take == 1 || (take == s->L && Ry % 64 == 0), "attn_sublayer_bwd: take must be L, with rows / take a multiple of 64");
-  const Ws ws = {s->gemm_ws, s->gemm_ws_bytes}, wsa = {aux == st ? s->gemm_ws : s->gemm_ws_aux, aux == st ? s->gemm_ws_bytes : s->gemm_ws_aux_bytes};
-  const bool od = has_drop(s->out_drop);
-  if (!s->dya_ready) {
-    TRY(zero_row_tail(s->dya, Ry, d, st));
-    TRY(afft_cast(s->dy, d, Ry, d, s->dya, d, AFFT_BF16, nullptr, 0, 0, od ? &s->out_drop : nullptr, st));
-  }
+  const Ws ws = main_ws(s), wsa = aux_ws(s, aux == st);
+  TRY(prepare_dya(s->dy, s->dya, Ry, d, s->out_drop, s->dya_ready, st));
   if (take > 1) {      // the projection's data gradient lands on every take-th row of dao: the rows between are zero
     TRY(afft_zero(s->dao, (int64_t)pad64(R) * d * 2, st));      // a kernel, not hipMemsetAsync: see afft_zero
   } else TRY(zero_row_tail(s->dao, R, d, st));
   TRY(zero_row_tail(s->dqkv, R, 3 * d, st));
-  // A weight gradient with a fused update rewrites the weight's bf16 image: it is enqueued BEHIND the data-gradient GEMM that
-  // reads that image (one event later than the plain form, which starts beside it).
-  auto side_proj = [&]() -> int {
-    TRY(stream_follows(aux, st));
-    TRY(wgrad(s->dya, d, d, s->ao, (int64_t)d * take, d, Ry, s->conv1d, s->g_w_proj, s->acc_w_proj, wsa, aux, s->sgd_w_proj));
-    if (s->g_b_proj) {
-      if (od) TRY(afft_colsum(s->dya, d, AFFT_BF16, Ry, d, s->g_b_proj, s->acc_b_proj, wsa.p, wsa.bytes, aux));
-      else TRY(afft_colsum(s->dy, d, AFFT_F32, Ry, d, s->g_b_proj, s->acc_b_proj, wsa.p, wsa.bytes, aux));
-    }
-    return 0;
+  auto side_proj = [&] {
+    return out_proj_side(s->dya, s->dy, has_drop(s->out_drop), d, s->ao, (int64_t)d * take, d, Ry, s->conv1d, s->g_w_proj, s->acc_w_proj,
+                         s->sgd_w_proj, s->g_b_proj, s->acc_b_proj, wsa, aux);
   };
-  if (!s->sgd_w_proj) TRY(side_proj());
   afft_gemm_t g = lin_dgrad(s->dya, d, Ry, d, s->w_proj, s->ldw_proj, d, s->conv1d, ws);
   g.out = s->dao; g.ldo = (int64_t)d * take; g.out_dtype = AFFT_BF16;
-  TRY(afft_gemm(&g, st));
-  if (s->sgd_w_proj) TRY(side_proj());
+  TRY(dgrad_beside_or_before(s->sgd_w_proj, side_proj, {g}, st, aux));
   const char* q = (const char*)s->qkv;
   char* dq = (char*)s->dqkv;
   TRY(afft_attention_bwd(s->dao, d, q, 3 * d, q + 2 * d, 3 * d, q + 4 * d, 3 * d, AFFT_BF16, s->probs, R / s->L, s->L, s->H,
                          d / s->H, s->scale, s->p_attn, s->k_attn, dq, 3 * d, dq + 2 * d, 3 * d, dq + 4 * d, 3 * d, st));
   auto side_qkv = [&]() -> int {
-    TRY(stream_follows(aux, st));
     TRY(wgrad(s->dqkv, 3 * d, 3 * d, s->xn, d, d, R, s->conv1d, s->g_w_qkv, s->acc_w_qkv, wsa, aux, s->sgd_w_qkv));
-    if (s->g_b_qkv) TRY(afft_colsum(s->dqkv, 3 * d, AFFT_BF16, R, 3 * d, s->g_b_qkv, s->acc_b_qkv, wsa.p, wsa.bytes, aux));
-    return 0;
+    return s->g_b_qkv ? afft_colsum(s->dqkv, 3 * d, AFFT_BF16, R, 3 * d, s->g_b_qkv, s->acc_b_qkv, wsa.p, wsa.bytes, aux) : 0;
   };
-  if (!s->sgd_w_qkv) TRY(side_qkv());
   g = lin_dgrad(s->dqkv, 3 * d, R, 3 * d, s->w_qkv, s->ldw_qkv, d, s->conv1d, ws);
   g.out = s->dxn; g.ldo = d; g.out_dtype = AFFT_BF16;
-  TRY(afft_gemm(&g, st));
-  if (s->sgd_w_qkv) TRY(side_qkv());
+  TRY(dgrad_beside_or_before(s->sgd_w_qkv, side_qkv, {g}, st, aux));
   return afft_layernorm_bwd_take(s->dxn, d, AFFT_BF16, s->x, d, s->ln_w, s->mean, s->rstd, R, d, s->dy, d, take, s->dx, d, s->dx_bf16,
                                  s->up_drop, s->g_ln_w, s->g_ln_b, s->acc_ln, s->up_dcol, 0, s->ln_partial, st);
 }
@@ -203,7 +218,7 @@ extern "C" int afft_mlp_sublayer_fwd(const afft_mlp_sublayer_t* s, void* stream_
   AFFT_CHECK(s->rows > 0 && s->d % 64 == 0 && s->hidden % 64 == 0, "mlp_sublayer_fwd: bad geometry");
   AFFT_CHECK(s->gelu == AFFT_ACT_GELU_ERF || s->gelu == AFFT_ACT_GELU_TANH, "mlp_sublayer_fwd: gelu must be GELU_ERF or GELU_TANH");
   const int R = s->rows, d = s->d, hd = s->hidden;
-  const Ws ws = {s->gemm_ws, s->gemm_ws_bytes};
+  const Ws ws = main_ws(s);
   if (s->f16x2) {      // see afft_attn_sublayer_fwd
     const int pr = pad64(R);
     const int64_t lo1 = (int64_t)pr * d, loh = (int64_t)pr * hd;
@@ -259,40 +274,25 @@ extern "C" int afft_mlp_sublayer_bwd(const afft_mlp_sublayer_t* s, void* stream_
   AFFT_CHECK(s && s->x && s->dy && s->dya && s->du && s->dxn && s->dx && s->ln_partial && s->xn && s->u && s->h && s->mean && s->rstd,
              "mlp_sublayer_bwd: null pointer");
   const int R = s->rows, d = s->d, hd = s->hidden;
-  const Ws ws = {s->gemm_ws, s->gemm_ws_bytes}, wsa = {aux == st ? s->gemm_ws : s->gemm_ws_aux, aux == st ? s->gemm_ws_bytes : s->gemm_ws_aux_bytes};
-  const bool od = has_drop(s->out_drop);
-  if (!s->dya_ready) {
-    TRY(zero_row_tail(s->dya, R, d, st));
-    TRY(afft_cast(s->dy, d, R, d, s->dya, d, AFFT_BF16, nullptr, 0, 0, od ? &s->out_drop : nullptr, st));
-  }
+  const Ws ws = main_ws(s), wsa = aux_ws(s, aux == st);
+  TRY(prepare_dya(s->dy, s->dya, R, d, s->out_drop, s->dya_ready, st));
   TRY(zero_row_tail(s->du, R, hd, st));
-  auto side_fc2 = [&]() -> int {      // see afft_attn_sublayer_bwd for the ordering of a fused update
-    TRY(stream_follows(aux, st));
-    TRY(wgrad(s->dya, d, d, s->h, hd, hd, R, s->conv1d, s->g_w2, s->acc_w2, wsa, aux, s->sgd_w2));
-    if (s->g_b2) {
-      if (od) TRY(afft_colsum(s->dya, d, AFFT_BF16, R, d, s->g_b2, s->acc_b2, wsa.p, wsa.bytes, aux));
-      else TRY(afft_colsum(s->dy, d, AFFT_F32, R, d, s->g_b2, s->acc_b2, wsa.p, wsa.bytes, aux));
-    }
-    return 0;
+  auto side_fc2 = [&] {
+    return out_proj_side(s->dya, s->dy, has_drop(s->out_drop), d, s->h, hd, hd, R, s->conv1d, s->g_w2, s->acc_w2, s->sgd_w2, s->g_b2, s->acc_b2,
+                         wsa, aux);
   };
-  if (!s->sgd_w2) TRY(side_fc2());
   afft_gemm_t g = lin_dgrad(s->dya, d, R, d, s->w2, s->ldw2, hd, s->conv1d, ws);
   g.act = s->gelu == AFFT_ACT_GELU_ERF ? AFFT_ACT_DGELU_ERF : AFFT_ACT_DGELU_TANH;
   g.aux = s->u; g.ldaux = hd; g.aux_dtype = AFFT_BF16;
   g.out = s->du; g.ldo = hd; g.out_dtype = AFFT_BF16;
-  TRY(afft_gemm(&g, st));
-  if (s->sgd_w2) TRY(side_fc2());
+  TRY(dgrad_beside_or_before(s->sgd_w2, side_fc2, {g}, st, aux));
   auto side_fc1 = [&]() -> int {
-    TRY(stream_follows(aux, st));
     TRY(wgrad(s->du, hd, hd, s->xn, d, d, R, s->conv1d, s->g_w1, s->acc_w1, wsa, aux, s->sgd_w1));
-    if (s->g_b1) TRY(afft_colsum(s->du, hd, AFFT_BF16, R, hd, s->g_b1, s->acc_b1, wsa.p, wsa.bytes, aux));
-    return 0;
+    return s->g_b1 ? afft_colsum(s->du, hd, AFFT_BF16, R, hd, s->g_b1, s->acc_b1, wsa.p, wsa.bytes, aux) : 0;
   };
-  if (!s->sgd_w1) TRY(side_fc1());
   g = lin_dgrad(s->du, hd, R, hd, s->w1, s->ldw1, d, s->conv1d, ws);
   g.out = s->dxn; g.ldo = d; g.out_dtype = AFFT_BF16;
-  TRY(afft_gemm(&g, st));
-  if (s->sgd_w1) TRY(side_fc1());
+  TRY(dgrad_beside_or_before(s->sgd_w1, side_fc1, {g}, st, aux));
   return afft_layernorm_bwd_take(s->dxn, d, AFFT_BF16, s->x, d, s->ln_w, s->mean, s->rstd, R, d, s->dy, d, 1, s->dx, d, s->dx_bf16, s->up_drop,
                                  s->g_ln_w, s->g_ln_b, s->acc_ln, s->up_dcol, 0, s->ln_partial, st);
 }
@@ -305,7 +305,7 @@ extern "C" int afft_cross_attn_sublayer_fwd(const afft_cross_attn_sublayer_t* s,
   AFFT_CHECK(s->rows > 0 && s->L > 0 && s->rows % s->L == 0 && s->H > 0 && s->d % 64 == 0 && s->d % s->H == 0,
              "cross_attn_sublayer_fwd: bad geometry");
   const int R = s->rows, d = s->d;
-  const Ws ws = {s->gemm_ws, s->gemm_ws_bytes};
+  const Ws ws = main_ws(s);
   void* bufs[6] = {s->xq, s->mkv, s->q, s->k, s->v, s->ao};
   for (void* b : bufs) TRY(zero_row_tail(b, R, d, st));
   TRY(afft_layernorm_fwd(s->x, d, s->nq_w, s->nq_b, s->eps, R, d, s->xq, d, AFFT_BF16, s->mean_q, s->rstd_q, st));
@@ -333,50 +333,33 @@ extern "C" int afft_cross_attn_sublayer_bwd(const afft_cross_attn_sublayer_t* s,
   AFFT_CHECK(s && s->x && s->mem && s->dy && s->dya && s->dao && s->dq && s->dk && s->dv && s->dxq && s->dmkv && s->dx && s->dmem &&
              s->ln_partial && s->ln_partial2, "cross_attn_sublayer_bwd: null pointer");
   const int R = s->rows, d = s->d;
-  const Ws ws = {s->gemm_ws, s->gemm_ws_bytes}, wsa = {aux == st ? s->gemm_ws : s->gemm_ws_aux, aux == st ? s->gemm_ws_bytes : s->gemm_ws_aux_bytes};
-  const bool od = has_drop(s->out_drop);
-  if (!s->dya_ready) {
-    TRY(zero_row_tail(s->dya, R, d, st));
-    TRY(afft_cast(s->dy, d, R, d, s->dya, d, AFFT_BF16, nullptr, 0, 0, od ? &s->out_drop : nullptr, st));
-  }
+  const Ws ws = main_ws(s), wsa = aux_ws(s, aux == st);
+  TRY(prepare_dya(s->dy, s->dya, R, d, s->out_drop, s->dya_ready, st));
   void* bufs[4] = {s->dao, s->dq, s->dk, s->dv};
   for (void* b : bufs) TRY(zero_row_tail(b, R, d, st));
-  auto side_proj = [&]() -> int {      // see afft_attn_sublayer_bwd for the ordering of a fused update
-    TRY(stream_follows(aux, st));
-    TRY(wgrad(s->dya, d, d, s->ao, d, d, R, false, s->g_w_proj, s->acc_w_proj, wsa, aux, s->sgd_w_proj));
-    if (s->g_b_proj) {
-      if (od) TRY(afft_colsum(s->dya, d, AFFT_BF16, R, d, s->g_b_proj, s->acc_b_proj, wsa.p, wsa.bytes, aux));
-      else TRY(afft_colsum(s->dy, d, AFFT_F32, R, d, s->g_b_proj, s->acc_b_proj, wsa.p, wsa.bytes, aux));
-    }
-    return 0;
+  auto side_proj = [&] {
+    return out_proj_side(s->dya, s->dy, has_drop(s->out_drop), d, s->ao, d, d, R, false, s->g_w_proj, s->acc_w_proj, s->sgd_w_proj, s->g_b_proj,
+                         s->acc_b_proj, wsa, aux);
   };
-  if (!s->sgd_w_proj) TRY(side_proj());
   afft_gemm_t g = lin_dgrad(s->dya, d, R, d, s->w_proj, s->ldw, d, false, ws);
   g.out = s->dao; g.ldo = d; g.out_dtype = AFFT_BF16;
-  TRY(afft_gemm(&g, st));
-  if (s->sgd_w_proj) TRY(side_proj());
+  TRY(dgrad_beside_or_before(s->sgd_w_proj, side_proj, {g}, st, aux));
   TRY(afft_attention_bwd(s->dao, d, s->q, d, s->k, d, s->v, d, AFFT_BF16, s->probs, R / s->L, s->L, s->H, d / s->H, s->scale,
                          s->p_attn, s->k_attn, s->dq, d, s->dk, d, s->dv, d, st));
-  const bool fused_qkv = s->sgd_w_q || s->sgd_w_k || s->sgd_w_v;
   auto side_qkv = [&]() -> int {
-    TRY(stream_follows(aux, st));
     TRY(wgrad(s->dq, d, d, s->xq, d, d, R, false, s->g_w_q, s->acc_w_q, wsa, aux, s->sgd_w_q));
     TRY(wgrad(s->dk, d, d, s->mkv, d, d, R, false, s->g_w_k, s->acc_w_k, wsa, aux, s->sgd_w_k));
-    TRY(wgrad(s->dv, d, d, s->mkv, d, d, R, false, s->g_w_v, s->acc_w_v, wsa, aux, s->sgd_w_v));
-    return 0;
+    return wgrad(s->dv, d, d, s->mkv, d, d, R, false, s->g_w_v, s->acc_w_v, wsa, aux, s->sgd_w_v);
   };
-  if (!fused_qkv) TRY(side_qkv());
-  g = lin_dgrad(s->dk, d, R, d, s->w_k, s->ldw, d, false, ws);
-  g.out = s->dmkv; g.ldo = d; g.out_dtype = AFFT_F32;
-  TRY(afft_gemm(&g, st));
-  g = lin_dgrad(s->dv, d, R, d, s->w_v, s->ldw, d, false, ws);
-  g.out = s->dmkv; g.ldo = d; g.out_dtype = AFFT_F32;
-  g.accumulate = 1;
-  TRY(afft_gemm(&g, st));
+  afft_gemm_t gk = lin_dgrad(s->dk, d, R, d, s->w_k, s->ldw, d, false, ws);
+  gk.out = s->dmkv; gk.ldo = d; gk.out_dtype = AFFT_F32;
+  afft_gemm_t gv = lin_dgrad(s->dv, d, R, d, s->w_v, s->ldw, d, false, ws);
+  gv.out = s->dmkv; gv.ldo = d; gv.out_dtype = AFFT_F32;
+  gv.accumulate = 1;
   g = lin_dgrad(s->dq, d, R, d, s->w_q, s->ldw, d, false, ws);
   g.out = s->dxq; g.ldo = d; g.out_dtype = AFFT_BF16;
-  TRY(afft_gemm(&g, st));
-  if (fused_qkv) TRY(side_qkv());
+  // one decision for the three projections: a fused update of any of them puts all three weight gradients behind the three GEMMs
+  TRY(dgrad_beside_or_before(s->sgd_w_q || s->sgd_w_k || s->sgd_w_v, side_qkv, {gk, gv, g}, st, aux));
   TRY(afft_layernorm_bwd(s->dmkv, d, AFFT_F32, s->mem, d, s->nkv_w, s->mean_kv, s->rstd_kv, R, d, nullptr, s->dmem, d, nullptr, nullptr,
                          s->g_nkv_w, s->g_nkv_b, s->acc_nkv, nullptr, 0, s->ln_partial2, st));
   return afft_layernorm_bwd(s->dxq, d, AFFT_BF16, s->x, d, s->nq_w, s->mean_q, s->rstd_q, R, d, s->dy, s->dx, d, s->dx_bf16, s->up_drop,

@@ -442,6 +442,62 @@ def _forget_output():
     _TS.last_out = None
 
 
+class _HandOut(NamedTuple):
+    dxa: Optional[Act]
+    gbu: Optional[Tensor]
+    direct: bool
+    tmp: Optional[Tensor]
+
+
+def _plan_handover(up: Optional[_Up], rows: int, d: int, dev) -> _HandOut:
+    """What a LayerNorm backward (_ln_bwd, or the one that ends a composite backward) emits for the sub-layer `up` that consumes its
+    dx: the bf16 operand dxa and, if that sub-layer has an output bias, its gradient gbu.  None or d % 64 != 0: nothing."""
+    if up is None or d % 64 != 0:
+        return _HandOut(None, None, False, None)
+    _drop_shadow()      # an earlier hand-over that was never picked up
+    dxa = Act(rows, d, dev)
+    gbu, direct, tmp = None, False, None
+    if up.bias is not None:
+        # the upstream sub-layer may still turn the hand-over down (autograd summed other gradients into dy, hooks,
+        # another graph): nothing is committed here that _discard cannot take back
+        if rt.grad_mode() == "sink" and up.bias.grad is not None and not rt.SINK.touched.get(id(up.bias), False):
+            gbu, direct = up.bias.grad, True      # first touch of the step: the kernel writes straight into bias.grad
+            rt.SINK.touched[id(up.bias)] = True
+        else:
+            gbu = tmp = torch.empty_like(up.bias)
+    return _HandOut(dxa, gbu, direct, tmp)
+
+
+def _publish_handover(ho: _HandOut, up: Optional[_Up], dx: Tensor):
+    """... once the kernel that writes dx and the planned pieces has been enqueued: leave them in this thread's shadow slot"""
+    if ho.dxa is not None:
+        sink = rt.grad_mode() == "sink"
+        _TS.shadow = _Shadow(dx.data_ptr(), tuple(dx.shape), dx._version, up.od, up.bias, ho.dxa,
+                             None if sink else ho.gbu, ho.direct, ho.tmp if sink else None)
+
+
+def _grad_slot(p: Optional[Tensor], fresh: list):
+    """(gradient tensor or None, accumulate flag) for parameter p: the sink's buffer, or a fresh tensor (autograd mode)"""
+    if p is None:
+        return None, 0
+    if rt.grad_mode() == "sink":
+        g, acc = rt.SINK.grad_buffer(p)
+        return g, int(acc)
+    g = torch.empty_like(p)
+    fresh.append(g)
+    return g, 0
+
+
+def _ln_grad_slots(w: Optional[Tensor], b: Optional[Tensor], fresh: list):
+    """LayerNorm weight / bias gradient buffers with the ONE accumulate flag the kernel takes for both"""
+    gw, aw = _grad_slot(w, fresh)
+    gb, ab = _grad_slot(b, fresh)
+    if w is not None and b is not None and aw != ab:      # mixed first-touch state: fall back to a zero fill
+        (gw if not aw else gb).zero_()
+        aw = ab = 1
+    return gw, gb, (aw if w is not None else ab)
+
+
 def _ln_bwd(dy: Tensor, x: Tensor, w: Optional[Tensor], b: Optional[Tensor], mean, rstd, dx_in: Optional[Tensor],
             dx_out: Optional[Tensor] = None, up: Optional[_Up] = None):
     """returns (dx, dw, db) with dw/db None in sink mode (accumulated in place).  `up`: the sub-layer that consumes dx
@@ -449,47 +505,21 @@ def _ln_bwd(dy: Tensor, x: Tensor, w: Optional[Tensor], b: Optional[Tensor], mea
     rows, d = x.shape
     if dx_out is None:
         dx_out = torch.empty(rows, d, dtype=torch.float32, device=x.device)
-    sink = rt.grad_mode() == "sink"
+    ho = _plan_handover(up if dx_out.stride(0) == d else None, rows, d, x.device)      # the emitted operand is dense: so must dx be
     extra = {}
-    dxa = gbu = None
-    direct, tmp = False, None
-    if up is not None and d % 64 == 0 and dx_out.stride(0) == d:
-        _drop_shadow()      # an earlier hand-over that was never picked up
-        dxa = Act(rows, d, x.device)
-        extra = dict(dx_bf16=dxa.live, copy_drop=up.od)
-        if up.bias is not None:
-            # the upstream sub-layer may still turn the hand-over down (autograd summed other gradients into dy, hooks,
-            # another graph): nothing is committed here that _discard cannot take back
-            if sink and up.bias.grad is not None and not rt.SINK.touched.get(id(up.bias), False):
-                gbu, direct = up.bias.grad, True
-                rt.SINK.touched[id(up.bias)] = True
-            else:
-                gbu = tmp = torch.empty_like(up.bias)
-            extra.update(dcol=gbu, dcol_accumulate=False)
-    if sink:
-        gw = gb = None
-        acc_w = acc_b = True
-        if w is not None:
-            gw, acc_w = rt.SINK.grad_buffer(w)
-        if b is not None:
-            gb, acc_b = rt.SINK.grad_buffer(b)
-        if w is not None and b is not None and acc_w != acc_b:   # mixed first-touch state: fall back to a zero fill
-            (gw if not acc_w else gb).zero_()
-            acc_w = acc_b = True
-        ops.layernorm_bwd(dy, x, w, mean, rstd, dx_out, dx_in=dx_in, dw=gw, db=gb,
-                          accumulate=acc_w if w is not None else acc_b, **extra)
+    if ho.dxa is not None:
+        extra = dict(dx_bf16=ho.dxa.live, copy_drop=up.od)
+        if ho.gbu is not None:
+            extra.update(dcol=ho.gbu, dcol_accumulate=False)
+    gw, gb, acc = _ln_grad_slots(w, b, [])
+    ops.layernorm_bwd(dy, x, w, mean, rstd, dx_out, dx_in=dx_in, dw=gw, db=gb, accumulate=bool(acc), **extra)
+    if rt.grad_mode() == "sink":
         if w is not None:
             _ready(w)
         if b is not None:
             _ready(b)
         gw = gb = None
-    else:
-        gw = torch.empty_like(w) if w is not None else None
-        gb = torch.empty_like(b) if b is not None else None
-        ops.layernorm_bwd(dy, x, w, mean, rstd, dx_out, dx_in=dx_in, dw=gw, db=gb, accumulate=False, **extra)
-    if dxa is not None:
-        _TS.shadow = _Shadow(dx_out.data_ptr(), tuple(dx_out.shape), dx_out._version, up.od, up.bias, dxa,
-                          None if sink else gbu, direct, tmp if sink else None)
+    _publish_handover(ho, up, dx_out)
     return dx_out, gw, gb
 
 
@@ -549,12 +579,19 @@ def attn_take_ok(x: Tensor, L: int, H: int, pre_ln: bool = True) -> bool:
             and (rt.precision() != "fp16x2" or (L <= 64 and hd % 64 == 0 and hd <= 1024)))
 
 
-def _lo8_ok(conv1d: bool, R: int, *shapes) -> bool:
-    """the fp8 lo pass for a sub-layer: nn.Linear weights and every (N, K) of its GEMMs on the 256x256 kernel (afft_gemm_lo8_ok)"""
+def _lo8_ok(conv1d: bool, *gemms) -> bool:
+    """the fp8 lo pass for a sub-layer: nn.Linear weights and every (rows, N, K) of its GEMMs on the 256x256 kernel (afft_gemm_lo8_ok)"""
     if conv1d or not rt.lo8():
         return False
     lib = L_.lib()
-    return all(lib.afft_gemm_lo8_ok(int(R), int(n), int(k)) for n, k in shapes)
+    return all(lib.afft_gemm_lo8_ok(int(r), int(n), int(k)) for r, n, k in gemms)
+
+
+def _f16x2_flags(conv1d: bool, d: int, gemms, sites) -> int:
+    """the `f16x2` word of an 'fp16x2' composite forward: 1 = two fp16 passes, 2 = the second pass on the block-scaled fp8 MFMA
+    (e4m3 lo planes of the activations, e4m3 weight images: the caller sets those), | the one-pass flags of its sites.
+    gemms: (rows, N, K) of the sub-layer's GEMMs; sites: their names for runtime.one_pass_flags"""
+    return (2 if _lo8_ok(conv1d, *gemms) else 1) | rt.one_pass_flags(conv1d, d, *sites)
 
 
 def _img_h(W: Tensor):
@@ -577,63 +614,20 @@ def _pk(W: Tensor, conv1d: bool, rows: int):
     return None if pk is None else pk.data_ptr()
 
 
+def _fwd_images(f16x2: bool, conv1d: bool, *gemms):
+    """(pointer, leading dimension, packed pointer) per (weight, rows of its GEMM) of a composite forward: the FP16 image ('fp16x2',
+    never packed), else the bf16 image and its fragment-packed copy -- every image first, then every packed copy"""
+    if f16x2:
+        return [_img_h(W) + (None,) for W, _ in gemms]
+    imgs = [_img(W) for W, _ in gemms]
+    return [img + (_pk(W, conv1d, rows),) for img, (W, rows) in zip(imgs, gemms)]
+
+
 def _ptr(t: Optional[Tensor]):
     return None if t is None else t.data_ptr()
 
 
-def _grad_slot(p: Optional[Tensor], fresh: list):
-    """(gradient tensor or None, accumulate flag) for parameter p: the sink's buffer, or a fresh tensor (autograd mode)"""
-    if p is None:
-        return None, 0
-    if rt.grad_mode() == "sink":
-        g, acc = rt.SINK.grad_buffer(p)
-        return g, int(acc)
-    g = torch.empty_like(p)
-    fresh.append(g)
-    return g, 0
-
-
-def _ln_grad_slots(w: Optional[Tensor], b: Optional[Tensor], fresh: list):
-    """LayerNorm weight / bias gradient buffers with ONE accumulate flag (see _ln_bwd for the mixed first-touch case)"""
-    gw, aw = _grad_slot(w, fresh)
-    gb, ab = _grad_slot(b, fresh)
-    if w is not None and b is not None and aw != ab:
-        (gw if not aw else gb).zero_()
-        aw = ab = 1
-    return gw, gb, (aw if w is not None else ab)
-
-
-class _HandOut(NamedTuple):
-    dxa: Optional[Act]
-    gbu: Optional[Tensor]
-    direct: bool
-    tmp: Optional[Tensor]
-
-
-def _plan_handover(up: Optional[_Up], rows: int, d: int, dev) -> _HandOut:
-    """What the LayerNorm backward at the end of a composite backward emits for the sub-layer upstream (cf. _ln_bwd)"""
-    if up is None or d % 64 != 0:
-        return _HandOut(None, None, False, None)
-    _drop_shadow()
-    dxa = Act(rows, d, dev)
-    gbu, direct, tmp = None, False, None
-    if up.bias is not None:
-        if rt.grad_mode() == "sink" and up.bias.grad is not None and not rt.SINK.touched.get(id(up.bias), False):
-            gbu, direct = up.bias.grad, True
-            rt.SINK.touched[id(up.bias)] = True
-        else:
-            gbu = tmp = torch.empty_like(up.bias)
-    return _HandOut(dxa, gbu, direct, tmp)
-
-
-def _publish_handover(ho: _HandOut, up: Optional[_Up], dx: Tensor):
-    if ho.dxa is not None:
-        sink = rt.grad_mode() == "sink"
-        _TS.shadow = _Shadow(dx.data_ptr(), tuple(dx.shape), dx._version, up.od, up.bias, ho.dxa,
-                             None if sink else ho.gbu, ho.direct, ho.tmp if sink else None)
-
-
-def _streams(dev, rows: int = 1 << 30):
+def _streams(dev):
     """(raw main stream, raw auxiliary stream or None, torch auxiliary stream or None)"""
     main = ops._stream()
     if rt.overlap_wgrad():
@@ -678,8 +672,81 @@ def _fuse_updates(s, weights) -> list:
 _TAP = None      # diagnostics (tools/repro_diag.py): called with (kind, tensors) right after a composite backward has been enqueued
 
 
-def _ln_partial(rows: int, d: int, dev) -> Tensor:
-    return torch.empty(L_.lib().afft_layernorm_bwd_nparts(rows) * 3 * d, dtype=torch.float32, device=dev)
+def _fwd_call(s, entry, what: str, dev, drop, y: Tensor, bias):
+    """The shared close of a composite forward: output dropout, workspace, the library call, and who produced y (_note_output)"""
+    od = _out_drop(drop)
+    if od is not None:
+        s.out_drop = od
+    main_raw = ops._stream()
+    _fill_ws(s, dev, main_raw, None)
+    L_.check(entry(C.byref(s), main_raw), what)
+    _note_output(y, od, bias)
+
+
+class _Bwd(NamedTuple):
+    """what _bwd_begin leaves for the sub-layer's own part of a composite backward and for _bwd_finish"""
+    dy: Tensor
+    sh: Optional[_Shadow]
+    fresh: list                   # autograd mode: the gradient tensors made by _grad_slot
+    scratch: Tensor               # bf16 backward scratch: dya first, the sub-layer's own buffers behind it
+    g_bias: Optional[Tensor]      # gradient of the output bias to return to autograd
+    bias_ready: Optional[Tensor]  # the output bias if THIS call produces its gradient (an accepted hand-over has notified already)
+
+
+def _bwd_begin(s, dy: Tensor, drop, bias: Optional[Tensor], bias_field: str, scratch_elems: int) -> _Bwd:
+    """The shared opening of a composite backward: picks up the hand-over for dy (before any allocation) or points the call at the cast
+    slot that leads the scratch buffer, and settles the output-bias gradient (struct fields g_<bias_field> / acc_<bias_field>) either way."""
+    dy = dy.contiguous()
+    od = _out_drop(drop)
+    sh = _take_shadow(dy, od, bias)
+    fresh: list = []
+    scratch = torch.empty(scratch_elems, dtype=torch.bfloat16, device=dy.device)
+    if od is not None:
+        s.out_drop = od
+    s.dy = dy.data_ptr()
+    if sh is not None:
+        s.dya, s.dya_ready = sh.act.buf.data_ptr(), 1
+        return _Bwd(dy, sh, fresh, scratch, _accept_bias(sh), None)
+    s.dya, s.dya_ready = scratch.data_ptr(), 0
+    gb, acc = _grad_slot(bias, fresh)
+    setattr(s, "g_" + bias_field, _ptr(gb))
+    setattr(s, "acc_" + bias_field, acc)
+    return _Bwd(dy, None, fresh, scratch, gb if rt.grad_mode() != "sink" else None, bias)
+
+
+def _bwd_finish(b: _Bwd, s, ctx, saved: Tensor, entry, what: str, ready, grads: tuple, tap=None) -> tuple:
+    """The shared close of a composite backward, once the sub-layer has filled its own fields of `s`: dx and the hand-over for the
+    sub-layer upstream, LayerNorm partials, workspaces, the library call, then the bookkeeping behind it.  ready: the parameters whose
+    gradient the call produces, in notification order; grads: their gradient tensors in the order autograd wants them back;
+    tap: (kind, extra entries) for _TAP.  Returns (dx,) + grads, with None for every gradient the sink holds."""
+    R, d = s.rows, s.d
+    dev = b.dy.device
+    main_raw, aux_raw, aux = _streams(dev)
+    dx = torch.empty(R, d, dtype=torch.float32, device=dev)
+    s.dx = dx.data_ptr()
+    ho = _plan_handover(ctx.up, R, d, dev)
+    if ho.dxa is not None:
+        s.dx_bf16 = ho.dxa.buf.data_ptr()
+        if ctx.up.od is not None:
+            s.up_drop = C.pointer(ctx.up.od)
+        s.up_dcol = _ptr(ho.gbu)
+    partial = ops.ln_partial(R, d, dev)
+    s.ln_partial = partial.data_ptr()
+    _fill_ws(s, dev, main_raw, aux_raw)
+    L_.check(entry(C.byref(s), main_raw, aux_raw), what)
+    if _TAP is not None and tap is not None:
+        _TAP(tap[0], dict(tap[1], scratch=b.scratch, dy=b.dy, dx=dx, R=R, d=d, saved=saved, shadow=b.sh, partial=partial))
+    _keep_for_aux(aux, saved, b.scratch, b.dy, b.sh.act.buf if b.sh is not None else None, *b.fresh)
+    _publish_handover(ho, ctx.up, dx)
+    if rt.grad_mode() == "sink":
+        for p in ready:
+            if p is not None:
+                _ready(p)
+        grads = (None,) * len(grads)
+    join_side(dev)
+    ctx.acts = None
+    flush_ready()
+    return (dx,) + grads
 
 
 def _attn_fwd_c(ctx, x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, L, H, mask, eps, conv1d, scale, drop, probs_out=None, take=0):
@@ -707,32 +774,21 @@ def _attn_fwd_c(ctx, x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, L, H, mask, ep
     s.rows, s.d, s.L, s.H, s.conv1d, s.mask, s.mask_period, s.eps, s.scale = R, d, L, H, int(conv1d), mk, per, eps, scale
     s.take = int(take)
     s.x, s.ln_w, s.ln_b = x.data_ptr(), _ptr(ln_w), _ptr(ln_b)
+    (s.w_qkv, s.ldw_qkv, s.w_qkv_pk), (s.w_proj, s.ldw_proj, s.w_proj_pk) = _fwd_images(f16x2, conv1d, (w_qkv, R), (w_proj, Ry))
     if f16x2:
-        s.f16x2 = 1
-        s.w_qkv, s.ldw_qkv = _img_h(w_qkv)
-        s.w_proj, s.ldw_proj = _img_h(w_proj)
-        if _lo8_ok(conv1d, R, (3 * d, d)) and _lo8_ok(conv1d, Ry, (d, d)):      # second pass on the block-scaled fp8 MFMA: e4m3 lo planes of xn / ao, e4m3 weight images
-            s.f16x2 = 2
+        s.f16x2 = _f16x2_flags(conv1d, d, ((R, 3 * d, d), (Ry, d, d)), ("qkv", "proj", "attn"))
+        if s.f16x2 & 3 == 2:
             s.w_qkv8, s.w_proj8 = rt.weight_f8(w_qkv).data_ptr(), rt.weight_f8(w_proj).data_ptr()
-        s.f16x2 |= rt.one_pass_flags(conv1d, d, "qkv", "proj", "attn")
         base = planes.data_ptr()
         s.xn, s.qkv, s.ao = base, base + 2 * (2 * pr * d), base + 2 * (2 * pr * 4 * d)      # [hi | lo] of xn, then of qkv, then of ao
         if saved is not None:
             s.xn_b, s.qkv_b, s.ao_b = xn.buf.data_ptr(), qkv.buf.data_ptr(), ao.buf.data_ptr()
     else:
-        s.w_qkv, s.ldw_qkv = _img(w_qkv)
-        s.w_proj, s.ldw_proj = _img(w_proj)
-        s.w_qkv_pk, s.w_proj_pk = _pk(w_qkv, conv1d, R), _pk(w_proj, conv1d, Ry)
         s.xn, s.qkv, s.ao = xn.buf.data_ptr(), qkv.buf.data_ptr(), ao.buf.data_ptr()
     s.b_qkv, s.b_proj = _ptr(b_qkv), _ptr(b_proj)
     s.p_attn, s.k_attn = _attn_drop(drop)
-    od = _out_drop(drop)
-    if od is not None:
-        s.out_drop = od
     s.mean, s.rstd, s.probs, s.y = stats[0].data_ptr(), stats[1].data_ptr(), probs.data_ptr(), y.data_ptr()
-    main_raw = ops._stream()
-    _fill_ws(s, dev, main_raw, None)
-    L_.check(L_.lib().afft_attn_sublayer_fwd(C.byref(s), main_raw), "attn_sublayer_fwd")
+    _fwd_call(s, L_.lib().afft_attn_sublayer_fwd, "attn_sublayer_fwd", dev, drop, y, b_proj)
     ctx.save_for_backward(x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, stats[0], stats[1], probs)
     ctx.acts = (xn, qkv, ao, saved)
     ctx.cfg = (L, H, scale, conv1d, True, drop)
@@ -740,7 +796,6 @@ def _attn_fwd_c(ctx, x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, L, H, mask, ep
     ctx.take = int(take)
     ctx.composite = True
     ctx.mark_non_differentiable(probs)
-    _note_output(y, od, b_proj)
     return y, probs
 
 
@@ -749,15 +804,9 @@ def _attn_bwd_c(ctx, dy):
     xn, qkv, ao, saved = ctx.acts
     L, H, scale, conv1d, _, drop = ctx.cfg
     R, d = x.shape
-    dev = x.device
     pr = rt.pad64(R)
-    dy = dy.contiguous()
-    od = _out_drop(drop)
-    sh = _take_shadow(dy, od, b_proj)
-    main_raw, aux_raw, aux = _streams(dev, R)
-    fresh: list = []
-    scratch = torch.empty(pr * 6 * d, dtype=torch.bfloat16, device=dev)      # dya | dao | dqkv | dxn
     s = L_.AttnSublayer()
+    b = _bwd_begin(s, dy, drop, b_proj, "b_proj", pr * 6 * d)      # dya | dao | dqkv | dxn
     s.rows, s.d, s.L, s.H, s.conv1d, s.eps, s.scale = R, d, L, H, int(conv1d), 0.0, scale
     s.take = ctx.take
     s.mask, s.mask_period = ctx.mask
@@ -765,54 +814,22 @@ def _attn_bwd_c(ctx, dy):
     s.w_qkv, s.ldw_qkv = _img(w_qkv)
     s.w_proj, s.ldw_proj = _img(w_proj)
     s.p_attn, s.k_attn = _attn_drop(drop)
-    if od is not None:
-        s.out_drop = od
     s.xn, s.qkv, s.ao = xn.buf.data_ptr(), qkv.buf.data_ptr(), ao.buf.data_ptr()
     s.mean, s.rstd, s.probs = mean.data_ptr(), rstd.data_ptr(), probs.data_ptr()
-    s.dy = dy.data_ptr()
-    base = scratch.data_ptr()
-    if sh is not None:
-        s.dya, s.dya_ready = sh.act.buf.data_ptr(), 1
-        g_bp = _accept_bias(sh)
-    else:
-        s.dya, s.dya_ready = base, 0
-        gb, acc = _grad_slot(b_proj, fresh)
-        s.g_b_proj, s.acc_b_proj = _ptr(gb), acc
-        g_bp = gb if rt.grad_mode() != "sink" else None
+    base = b.scratch.data_ptr()
     s.dao, s.dqkv, s.dxn = base + pr * d * 2, base + pr * 2 * d * 2, base + pr * 5 * d * 2
-    g_wq, s.acc_w_qkv = _grad_slot(w_qkv, fresh)
-    g_bq, s.acc_b_qkv = _grad_slot(b_qkv, fresh)
-    g_wp, s.acc_w_proj = _grad_slot(w_proj, fresh)
-    g_lw, g_lb, s.acc_ln = _ln_grad_slots(ln_w, ln_b, fresh)
+    g_wq, s.acc_w_qkv = _grad_slot(w_qkv, b.fresh)
+    g_bq, s.acc_b_qkv = _grad_slot(b_qkv, b.fresh)
+    g_wp, s.acc_w_proj = _grad_slot(w_proj, b.fresh)
+    g_lw, g_lb, s.acc_ln = _ln_grad_slots(ln_w, ln_b, b.fresh)
     s.g_w_qkv, s.g_b_qkv, s.g_w_proj, s.g_ln_w, s.g_ln_b = _ptr(g_wq), _ptr(g_bq), _ptr(g_wp), _ptr(g_lw), _ptr(g_lb)
     keep = _fuse_updates(s, (("sgd_w_qkv", w_qkv, s.acc_w_qkv), ("sgd_w_proj", w_proj, s.acc_w_proj)))
-    dx = torch.empty(R, d, dtype=torch.float32, device=dev)
-    s.dx = dx.data_ptr()
-    ho = _plan_handover(ctx.up, R, d, dev)
-    if ho.dxa is not None:
-        s.dx_bf16 = ho.dxa.buf.data_ptr()
-        if ctx.up.od is not None:
-            s.up_drop = C.pointer(ctx.up.od)
-        s.up_dcol = _ptr(ho.gbu)
-    partial = _ln_partial(R, d, dev)
-    s.ln_partial = partial.data_ptr()
-    _fill_ws(s, dev, main_raw, aux_raw)
     if _TAP is not None:
         _TAP("attn_bwd_pre", dict(R=R, d=d, w_qkv=w_qkv, w_proj=w_proj))
-    L_.check(L_.lib().afft_attn_sublayer_bwd(C.byref(s), main_raw, aux_raw), "attn_sublayer_bwd")
-    if _TAP is not None:
-        _TAP("attn_bwd", dict(scratch=scratch, dy=dy, dx=dx, R=R, d=d, w_qkv=w_qkv, w_proj=w_proj, saved=saved, shadow=sh, partial=partial, x=x))
-    _keep_for_aux(aux, saved, scratch, dy, sh.act.buf if sh is not None else None, *fresh)
-    _publish_handover(ho, ctx.up, dx)
-    if rt.grad_mode() == "sink":
-        for p in (w_proj, None if sh is not None else b_proj, w_qkv, b_qkv, ln_w, ln_b):
-            if p is not None:
-                _ready(p)
-        g_wq = g_bq = g_wp = g_bp = g_lw = g_lb = None
-    join_side(dev)
-    ctx.acts = None
-    flush_ready()
-    return dx, g_lw, g_lb, g_wq, g_bq, g_wp, g_bp, None, None, None, None, None, None, None, None, None
+    out = _bwd_finish(b, s, ctx, saved, L_.lib().afft_attn_sublayer_bwd, "attn_sublayer_bwd",
+                      ready=(w_proj, b.bias_ready, w_qkv, b_qkv, ln_w, ln_b), grads=(g_lw, g_lb, g_wq, g_bq, g_wp, b.g_bias),
+                      tap=("attn_bwd", dict(w_qkv=w_qkv, w_proj=w_proj, x=x)))
+    return out + (None,) * 9      # L, H, mask, eps, conv1d, pre_ln, scale, drop, probs_out (AttnSublayer.backward adds take)
 
 
 def _mlp_fwd_c(ctx, x, ln_w, ln_b, w1, b1, w2, b2, eps, gelu, conv1d, hidden, drop):
@@ -834,36 +851,24 @@ def _mlp_fwd_c(ctx, x, ln_w, ln_b, w1, b1, w2, b2, eps, gelu, conv1d, hidden, dr
     s.rows, s.d, s.hidden, s.conv1d, s.gelu, s.eps = R, d, hidden, int(conv1d), _GELU[gelu][0], eps
     s.x, s.ln_w, s.ln_b = x.data_ptr(), _ptr(ln_w), _ptr(ln_b)
     # the pre-activation is only read by backward: a forward nobody will differentiate (no_grad) does not store it (84 MB at R = 5120)
+    (s.w1, s.ldw1, s.w1_pk), (s.w2, s.ldw2, s.w2_pk) = _fwd_images(f16x2, conv1d, (w1, R), (w2, R))
     if f16x2:
-        s.f16x2 = 1
-        s.w1, s.ldw1 = _img_h(w1)
-        s.w2, s.ldw2 = _img_h(w2)
-        if _lo8_ok(conv1d, R, (hidden, d), (d, hidden)):
-            s.f16x2 = 2
+        s.f16x2 = _f16x2_flags(conv1d, d, ((R, hidden, d), (R, d, hidden)), ("fc1", "fc2"))
+        if s.f16x2 & 3 == 2:
             s.w1_8, s.w2_8 = rt.weight_f8(w1).data_ptr(), rt.weight_f8(w2).data_ptr()
-        s.f16x2 |= rt.one_pass_flags(conv1d, d, "fc1", "fc2")
         base = planes.data_ptr()
         s.xn, s.h = base, base + 2 * (2 * pr * d)
         if saved is not None:
             s.xn_b, s.u, s.h_b = xn.buf.data_ptr(), u.buf.data_ptr(), h.buf.data_ptr()
     else:
-        s.w1, s.ldw1 = _img(w1)
-        s.w2, s.ldw2 = _img(w2)
-        s.w1_pk, s.w2_pk = _pk(w1, conv1d, R), _pk(w2, conv1d, R)
         s.xn, s.u, s.h = xn.buf.data_ptr(), (u.buf.data_ptr() if grad else None), h.buf.data_ptr()
     s.b1, s.b2 = _ptr(b1), _ptr(b2)
-    od = _out_drop(drop)
-    if od is not None:
-        s.out_drop = od
     s.mean, s.rstd, s.y = stats[0].data_ptr(), stats[1].data_ptr(), y.data_ptr()
-    main_raw = ops._stream()
-    _fill_ws(s, dev, main_raw, None)
-    L_.check(L_.lib().afft_mlp_sublayer_fwd(C.byref(s), main_raw), "mlp_sublayer_fwd")
+    _fwd_call(s, L_.lib().afft_mlp_sublayer_fwd, "mlp_sublayer_fwd", dev, drop, y, b2)
     ctx.save_for_backward(x, ln_w, ln_b, w1, b1, w2, b2, stats[0], stats[1])
     ctx.acts = (xn, u, h, saved)
     ctx.cfg = (gelu, conv1d, hidden, True, drop)
     ctx.composite = True
-    _note_output(y, od, b2)
     return y
 
 
@@ -872,65 +877,27 @@ def _mlp_bwd_c(ctx, dy):
     xn, u, h, saved = ctx.acts
     gelu, conv1d, hidden, _, drop = ctx.cfg
     R, d = x.shape
-    dev = x.device
     pr = rt.pad64(R)
-    dy = dy.contiguous()
-    od = _out_drop(drop)
-    sh = _take_shadow(dy, od, b2)
-    main_raw, aux_raw, aux = _streams(dev, R)
-    fresh: list = []
-    scratch = torch.empty(pr * (2 * d + hidden), dtype=torch.bfloat16, device=dev)    # dya | dxn | du
     s = L_.MLPSublayer()
+    b = _bwd_begin(s, dy, drop, b2, "b2", pr * (2 * d + hidden))      # dya | dxn | du
     s.rows, s.d, s.hidden, s.conv1d, s.gelu = R, d, hidden, int(conv1d), _GELU[gelu][0]
     s.x, s.ln_w = x.data_ptr(), _ptr(ln_w)
     s.w1, s.ldw1 = _img(w1)
     s.w2, s.ldw2 = _img(w2)
-    if od is not None:
-        s.out_drop = od
     s.xn, s.u, s.h = xn.buf.data_ptr(), u.buf.data_ptr(), h.buf.data_ptr()
     s.mean, s.rstd = mean.data_ptr(), rstd.data_ptr()
-    s.dy = dy.data_ptr()
-    base = scratch.data_ptr()
-    if sh is not None:
-        s.dya, s.dya_ready = sh.act.buf.data_ptr(), 1
-        g_b2 = _accept_bias(sh)
-    else:
-        s.dya, s.dya_ready = base, 0
-        gb, acc = _grad_slot(b2, fresh)
-        s.g_b2, s.acc_b2 = _ptr(gb), acc
-        g_b2 = gb if rt.grad_mode() != "sink" else None
+    base = b.scratch.data_ptr()
     s.dxn, s.du = base + pr * d * 2, base + pr * 2 * d * 2
-    g_w1, s.acc_w1 = _grad_slot(w1, fresh)
-    g_b1, s.acc_b1 = _grad_slot(b1, fresh)
-    g_w2, s.acc_w2 = _grad_slot(w2, fresh)
-    g_lw, g_lb, s.acc_ln = _ln_grad_slots(ln_w, ln_b, fresh)
+    g_w1, s.acc_w1 = _grad_slot(w1, b.fresh)
+    g_b1, s.acc_b1 = _grad_slot(b1, b.fresh)
+    g_w2, s.acc_w2 = _grad_slot(w2, b.fresh)
+    g_lw, g_lb, s.acc_ln = _ln_grad_slots(ln_w, ln_b, b.fresh)
     s.g_w1, s.g_b1, s.g_w2, s.g_ln_w, s.g_ln_b = _ptr(g_w1), _ptr(g_b1), _ptr(g_w2), _ptr(g_lw), _ptr(g_lb)
     keep = _fuse_updates(s, (("sgd_w1", w1, s.acc_w1), ("sgd_w2", w2, s.acc_w2)))
-    dx = torch.empty(R, d, dtype=torch.float32, device=dev)
-    s.dx = dx.data_ptr()
-    ho = _plan_handover(ctx.up, R, d, dev)
-    if ho.dxa is not None:
-        s.dx_bf16 = ho.dxa.buf.data_ptr()
-        if ctx.up.od is not None:
-            s.up_drop = C.pointer(ctx.up.od)
-        s.up_dcol = _ptr(ho.gbu)
-    partial = _ln_partial(R, d, dev)
-    s.ln_partial = partial.data_ptr()
-    _fill_ws(s, dev, main_raw, aux_raw)
-    L_.check(L_.lib().afft_mlp_sublayer_bwd(C.byref(s), main_raw, aux_raw), "mlp_sublayer_bwd")
-    if _TAP is not None:
-        _TAP("mlp_bwd", dict(scratch=scratch, dy=dy, dx=dx, R=R, d=d, hidden=hidden, w1=w1, w2=w2, saved=saved, shadow=sh, partial=partial, x=x))
-    _keep_for_aux(aux, saved, scratch, dy, sh.act.buf if sh is not None else None, *fresh)
-    _publish_handover(ho, ctx.up, dx)
-    if rt.grad_mode() == "sink":
-        for p in (w2, None if sh is not None else b2, w1, b1, ln_w, ln_b):
-            if p is not None:
-                _ready(p)
-        g_w1 = g_b1 = g_w2 = g_b2 = g_lw = g_lb = None
-    join_side(dev)
-    ctx.acts = None
-    flush_ready()
-    return dx, g_lw, g_lb, g_w1, g_b1, g_w2, g_b2, None, None, None, None, None
+    out = _bwd_finish(b, s, ctx, saved, L_.lib().afft_mlp_sublayer_bwd, "mlp_sublayer_bwd",
+                      ready=(w2, b.bias_ready, w1, b1, ln_w, ln_b), grads=(g_lw, g_lb, g_w1, g_b1, g_w2, b.g_bias),
+                      tap=("mlp_bwd", dict(hidden=hidden, w1=w1, w2=w2, x=x)))
+    return out + (None,) * 5      # eps, gelu, conv1d, pre_ln, drop
 
 
 def _cross_fwd_c(ctx, x, mem, nq_w, nq_b, nkv_w, nkv_b, w_q, w_k, w_v, w_proj, b_proj, L, H, mask, eps, scale, drop):
@@ -954,22 +921,16 @@ def _cross_fwd_c(ctx, x, mem, nq_w, nq_b, nkv_w, nkv_b, w_q, w_k, w_v, w_proj, b
     (s.w_q, s.ldw), (s.w_k, _), (s.w_v, _), (s.w_proj, _) = imgs
     s.b_proj = _ptr(b_proj)
     s.p_attn, s.k_attn = _attn_drop(drop)
-    od = _out_drop(drop)
-    if od is not None:
-        s.out_drop = od
     s.xq, s.mkv, s.q, s.k, s.v, s.ao = (a.buf.data_ptr() for a in (xq, mkv, q, k, v, ao))
     s.mean_q, s.rstd_q, s.mean_kv, s.rstd_kv = (stats[i].data_ptr() for i in range(4))
     s.probs, s.y = probs.data_ptr(), y.data_ptr()
-    main_raw = ops._stream()
-    _fill_ws(s, dev, main_raw, None)
-    L_.check(L_.lib().afft_cross_attn_sublayer_fwd(C.byref(s), main_raw), "cross_attn_sublayer_fwd")
+    _fwd_call(s, L_.lib().afft_cross_attn_sublayer_fwd, "cross_attn_sublayer_fwd", dev, drop, y, b_proj)
     ctx.save_for_backward(x, mem, nq_w, nq_b, nkv_w, nkv_b, w_q, w_k, w_v, w_proj, b_proj, stats[0], stats[1], stats[2], stats[3],
                           probs)
     ctx.acts = (xq, mkv, q, k, v, ao, saved)
     ctx.cfg = (L, H, scale, True, drop)
     ctx.mask = (mk, per)
     ctx.composite = True
-    _note_output(y, od, b_proj)
     return y
 
 
@@ -980,70 +941,35 @@ def _cross_bwd_c(ctx, dy):
     R, d = x.shape
     dev = x.device
     pr = rt.pad64(R)
-    dy = dy.contiguous()
-    od = _out_drop(drop)
-    sh = _take_shadow(dy, od, b_proj)
-    main_raw, aux_raw, aux = _streams(dev, R)
-    fresh: list = []
-    scratch = torch.empty(pr * 6 * d, dtype=torch.bfloat16, device=dev)       # dya | dao | dq | dk | dv | dxq
-    dmkv = torch.empty(R, d, dtype=torch.float32, device=dev)
     s = L_.CrossAttnSublayer()
+    b = _bwd_begin(s, dy, drop, b_proj, "b_proj", pr * 6 * d)       # dya | dao | dq | dk | dv | dxq
+    dmkv = torch.empty(R, d, dtype=torch.float32, device=dev)
+    dmem = torch.empty(R, d, dtype=torch.float32, device=dev)
+    partial_kv = ops.ln_partial(R, d, dev)      # the memory LayerNorm's partials; the query LayerNorm's are _bwd_finish's
     s.rows, s.d, s.L, s.H, s.scale = R, d, L, H, scale
     s.mask, s.mask_period = ctx.mask
     s.x, s.mem, s.nq_w, s.nkv_w = x.data_ptr(), mem.data_ptr(), _ptr(nq_w), _ptr(nkv_w)
     (s.w_q, s.ldw), (s.w_k, _), (s.w_v, _), (s.w_proj, _) = [_img(w) for w in (w_q, w_k, w_v, w_proj)]
     s.p_attn, s.k_attn = _attn_drop(drop)
-    if od is not None:
-        s.out_drop = od
     s.xq, s.mkv, s.q, s.k, s.v, s.ao = (a.buf.data_ptr() for a in (xq, mkv, q, k, v, ao))
     s.mean_q, s.rstd_q, s.mean_kv, s.rstd_kv, s.probs = mq.data_ptr(), rq.data_ptr(), mkm.data_ptr(), rk.data_ptr(), probs.data_ptr()
-    s.dy = dy.data_ptr()
-    base = scratch.data_ptr()
-    if sh is not None:
-        s.dya, s.dya_ready = sh.act.buf.data_ptr(), 1
-        g_bp = _accept_bias(sh)
-    else:
-        s.dya, s.dya_ready = base, 0
-        gb, acc = _grad_slot(b_proj, fresh)
-        s.g_b_proj, s.acc_b_proj = _ptr(gb), acc
-        g_bp = gb if rt.grad_mode() != "sink" else None
+    base = b.scratch.data_ptr()
     s.dao, s.dq, s.dk, s.dv, s.dxq = (base + i * pr * d * 2 for i in range(1, 6))
-    s.dmkv = dmkv.data_ptr()
-    g_q, s.acc_w_q = _grad_slot(w_q, fresh)
-    g_k, s.acc_w_k = _grad_slot(w_k, fresh)
-    g_v, s.acc_w_v = _grad_slot(w_v, fresh)
-    g_wp, s.acc_w_proj = _grad_slot(w_proj, fresh)
-    g_qw, g_qb, s.acc_nq = _ln_grad_slots(nq_w, nq_b, fresh)
-    g_kw, g_kb, s.acc_nkv = _ln_grad_slots(nkv_w, nkv_b, fresh)
+    s.dmkv, s.dmem, s.ln_partial2 = dmkv.data_ptr(), dmem.data_ptr(), partial_kv.data_ptr()
+    g_q, s.acc_w_q = _grad_slot(w_q, b.fresh)
+    g_k, s.acc_w_k = _grad_slot(w_k, b.fresh)
+    g_v, s.acc_w_v = _grad_slot(w_v, b.fresh)
+    g_wp, s.acc_w_proj = _grad_slot(w_proj, b.fresh)
+    g_qw, g_qb, s.acc_nq = _ln_grad_slots(nq_w, nq_b, b.fresh)
+    g_kw, g_kb, s.acc_nkv = _ln_grad_slots(nkv_w, nkv_b, b.fresh)
     s.g_w_q, s.g_w_k, s.g_w_v, s.g_w_proj = _ptr(g_q), _ptr(g_k), _ptr(g_v), _ptr(g_wp)
     keep = _fuse_updates(s, (("sgd_w_q", w_q, s.acc_w_q), ("sgd_w_k", w_k, s.acc_w_k), ("sgd_w_v", w_v, s.acc_w_v),
                              ("sgd_w_proj", w_proj, s.acc_w_proj)))
     s.g_nq_w, s.g_nq_b, s.g_nkv_w, s.g_nkv_b = _ptr(g_qw), _ptr(g_qb), _ptr(g_kw), _ptr(g_kb)
-    dx = torch.empty(R, d, dtype=torch.float32, device=dev)
-    dmem = torch.empty(R, d, dtype=torch.float32, device=dev)
-    s.dx, s.dmem = dx.data_ptr(), dmem.data_ptr()
-    ho = _plan_handover(ctx.up, R, d, dev)
-    if ho.dxa is not None:
-        s.dx_bf16 = ho.dxa.buf.data_ptr()
-        if ctx.up.od is not None:
-            s.up_drop = C.pointer(ctx.up.od)
-        s.up_dcol = _ptr(ho.gbu)
-    partial = _ln_partial(R, 2 * d, dev)
-    s.ln_partial, s.ln_partial2 = partial.data_ptr(), partial.data_ptr() + partial.numel() * 2
-    _fill_ws(s, dev, main_raw, aux_raw)
-    L_.check(L_.lib().afft_cross_attn_sublayer_bwd(C.byref(s), main_raw, aux_raw), "cross_attn_sublayer_bwd")
-    _keep_for_aux(aux, saved, scratch, dy, sh.act.buf if sh is not None else None, *fresh)
-    _publish_handover(ho, ctx.up, dx)
-    if rt.grad_mode() == "sink":
-        for p in (w_proj, None if sh is not None else b_proj, w_q, w_k, w_v, nkv_w, nkv_b, nq_w, nq_b):
-            if p is not None:
-                _ready(p)
-        g_q = g_k = g_v = g_wp = g_bp = g_qw = g_qb = g_kw = g_kb = None
-    join_side(dev)
-    ctx.acts = None
-    flush_ready()
-    return dx, dmem, g_qw, g_qb, g_kw, g_kb, g_q, g_k, g_v, g_wp, g_bp, None, None, None, None, None, None, None, None, None, None
-
+    out = _bwd_finish(b, s, ctx, saved, L_.lib().afft_cross_attn_sublayer_bwd, "cross_attn_sublayer_bwd",
+                      ready=(w_proj, b.bias_ready, w_q, w_k, w_v, nkv_w, nkv_b, nq_w, nq_b),
+                      grads=(g_qw, g_qb, g_kw, g_kb, g_q, g_k, g_v, g_wp, b.g_bias))
+    return out[:1] + (dmem,) + out[1:] + (None,) * 10      # L, H, mask, eps, pre_ln, scale, drop, b_q, b_k, b_v
 
 
 # --------------------------------------------------------------------------- pre-LN self-attention sub-layer

@@ -220,6 +220,11 @@ def layernorm_fwd_split(x: Tensor, w: Optional[Tensor], b: Optional[Tensor], eps
     return y_hi
 
 
+def ln_partial(rows: int, d: int, dev) -> Tensor:
+    """the column-partial scratch of one LayerNorm backward over [rows, d] (afft_layernorm_bwd's `partial`)"""
+    return torch.empty(L.lib().afft_layernorm_bwd_nparts(rows) * 3 * d, dtype=torch.float32, device=dev)
+
+
 def layernorm_bwd(dy: Tensor, x: Tensor, w: Optional[Tensor], mean: Tensor, rstd: Tensor, dx_out: Tensor,
                   dx_in: Optional[Tensor] = None, dx_bf16: Optional[Tensor] = None, dw: Optional[Tensor] = None,
                   db: Optional[Tensor] = None, accumulate: bool = True, copy_drop: Optional["L.Dropout"] = None,
@@ -227,8 +232,7 @@ def layernorm_bwd(dy: Tensor, x: Tensor, w: Optional[Tensor], mean: Tensor, rstd
     """dw / db (optional) receive the weight / bias gradients: added to when `accumulate`, else overwritten.
     dx_bf16 (optional): bf16 copy of dx_out with the mask `copy_drop` replayed; dcol (optional): its column sums."""
     rows, d = x.shape
-    nparts = L.lib().afft_layernorm_bwd_nparts(rows)
-    partial = torch.empty(nparts * 3 * d, dtype=torch.float32, device=x.device)
+    partial = ln_partial(rows, d, x.device)
     lddx = _rowmajor(dx_out, "dx_out")
     if dx_in is not None:
         assert _rowmajor(dx_in, "dx_in") == lddx
