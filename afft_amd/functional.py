@@ -552,12 +552,24 @@ def mask_table(mask) -> Optional[Tensor]:
     return mask[1] if isinstance(mask, tuple) and mask[0] == "table" else None
 
 
+ATTN_SHORT_MAX = 128      # the longest sequence of afft_attention_fwd / _bwd and of the composite sub-layer entry points
+
+
 def _attention_fwd(q, k, v, nseq, L, H, hd, scale, mask, out, probs, drop):
     tab = mask_table(mask)
+    if L > ATTN_SHORT_MAX:
+        mk, per = _mask_args(mask) if tab is None else (MASK_NONE, 0)
+        return ops.attention_long_fwd(q, k, v, nseq, L, H, hd, scale, mk, out, probs, *(_attn_drop(drop)), mask_period=per, table=tab)
     if tab is not None:
         return ops.attention_fwd_table(q, k, v, nseq, L, H, hd, scale, tab, out, probs, *(_attn_drop(drop)))
     mk, per = _mask_args(mask)
     return ops.attention_fwd(q, k, v, nseq, L, H, hd, scale, mk, out, probs, *(_attn_drop(drop)), mask_period=per)
+
+
+def _attention_bwd(dout, q, k, v, probs, nseq, L, H, hd, scale, dq, dk, dv, drop):
+    """sequences above ATTN_SHORT_MAX tokens have kernels of their own (csrc/attention_long.hip), tiled over rows"""
+    fn = ops.attention_long_bwd if L > ATTN_SHORT_MAX else ops.attention_bwd
+    return fn(dout, q, k, v, probs, nseq, L, H, hd, scale, dq, dk, dv, *(_attn_drop(drop)))
 
 
 # --------------------------------------------------------------------------- composite path: one C-ABI call per sub-layer
@@ -575,7 +587,7 @@ def attn_take_ok(x: Tensor, L: int, H: int, pre_ln: bool = True) -> bool:
     counts whose quotient by L is a multiple of 64 (the weight-gradient GEMM reduces over whole 64-row K-tiles of the strided rows)"""
     R, d = x.shape
     hd = d // H
-    return (L > 1 and R % L == 0 and (R // L) % 64 == 0 and _composite_ok(x, pre_ln, d)
+    return (1 < L <= ATTN_SHORT_MAX and R % L == 0 and (R // L) % 64 == 0 and _composite_ok(x, pre_ln, d)
             and (rt.precision() != "fp16x2" or (L <= 64 and hd % 64 == 0 and hd <= 1024)))
 
 
@@ -995,7 +1007,7 @@ class AttnSublayer(torch.autograd.Function):
         # freshly ZERO-FILLED tensor of its shape for it on every call (a fill kernel per attention sub-layer and step)
         ctx.set_materialize_grads(False)
         # fp16x2: the attention core on hi + lo planes exists on the MFMA path only (L <= 64, head dimension a multiple of 64)
-        if mask_table(mask) is None and _composite_ok(x, pre_ln, d) and (rt.precision() != "fp16x2" or (L <= 64 and hd % 64 == 0 and hd <= 1024)):
+        if mask_table(mask) is None and L <= ATTN_SHORT_MAX and _composite_ok(x, pre_ln, d) and (rt.precision() != "fp16x2" or (L <= 64 and hd % 64 == 0 and hd <= 1024)):
             return _attn_fwd_c(ctx, x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, L, H, mask, eps, conv1d, scale, drop, probs_out, take)
         ctx.up = _upstream_of(x) if pre_ln else None
         mean, rstd = _stats(R if pre_ln else 0, dev)
@@ -1044,8 +1056,8 @@ class AttnSublayer(torch.autograd.Function):
         dao = Act(R, d, dev)
         _lin_dgrad(dya, w_proj, conv1d, dao.live)
         dqkv = Act(R, 3 * d, dev)
-        ops.attention_bwd(dao.live, qkv.cols(0, d), qkv.cols(d, 2 * d), qkv.cols(2 * d, 3 * d), probs, nseq, L, H, hd,
-                          scale, dqkv.cols(0, d), dqkv.cols(d, 2 * d), dqkv.cols(2 * d, 3 * d), *(_attn_drop(drop)))
+        _attention_bwd(dao.live, qkv.cols(0, d), qkv.cols(d, 2 * d), qkv.cols(2 * d, 3 * d), probs, nseq, L, H, hd,
+                       scale, dqkv.cols(0, d), dqkv.cols(d, 2 * d), dqkv.cols(2 * d, 3 * d), drop)
         with _Side(dev):
             g_wq = _wgrad(dqkv, xn, w_qkv, conv1d)
             g_bq = _bgrad(dqkv.live, b_qkv)
@@ -1145,7 +1157,7 @@ class CrossAttnSublayer(torch.autograd.Function):
         dev = x.device
         ctx.composite = False
         ctx.qkv_bias = b_q is not None or b_k is not None or b_v is not None
-        if (mask_table(mask) is None and not ctx.qkv_bias and dm == d and _composite_ok(x, pre_ln, d, f16x2=False)
+        if (mask_table(mask) is None and L <= ATTN_SHORT_MAX and not ctx.qkv_bias and dm == d and _composite_ok(x, pre_ln, d, f16x2=False)
                 and mem.stride(0) == d):
             return _cross_fwd_c(ctx, x, mem, nq_w, nq_b, nkv_w, nkv_b, w_q, w_k, w_v, w_proj, b_proj, L, H, mask, eps, scale,
                                 drop)
@@ -1196,8 +1208,7 @@ class CrossAttnSublayer(torch.autograd.Function):
         dao = Act(R, d, dev)
         _lin_dgrad(dya, w_proj, False, dao.live)
         dq, dk, dv = Act(R, d, dev), Act(R, d, dev), Act(R, d, dev)
-        ops.attention_bwd(dao.live, q.live, k.live, v.live, probs, nseq, L, H, hd, scale, dq.live, dk.live, dv.live,
-                          *(_attn_drop(drop)))
+        _attention_bwd(dao.live, q.live, k.live, v.live, probs, nseq, L, H, hd, scale, dq.live, dk.live, dv.live, drop)
         b_q, b_k, b_v = ctx.qkv_b
         with _Side(dev):
             g_q = _wgrad(dq, xq, w_q, False)

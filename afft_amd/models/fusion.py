@@ -234,8 +234,8 @@ class TemporalCMFuser(nn.Module):
         B, T, C = _check_same_shape(modal_feats)
         n = self.num_mods
         L = n * T
-        if L > 128:
-            raise NotImplementedError(f"afft_amd: T-SA-Fuser sequences of {L} tokens (> 128) are not built")
+        if L > 512:
+            raise NotImplementedError(f"afft_amd: T-SA-Fuser sequences of {L} tokens (> 512) are not built")
         feats = [_rows(f, B, T * C) for f in ordered_feature_list(modal_feats)]           # each (B, T*C)
         if self.frame_level_token:
             assert self.temporal_sequence_length == T, \

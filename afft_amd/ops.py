@@ -290,6 +290,31 @@ def attention_bwd(dout: Tensor, q: Tensor, k: Tensor, v: Tensor, probs: Tensor, 
                                        _rowmajor(dv, "dv"), _stream()), "attention_bwd")
 
 
+def attention_long_fwd(q: Tensor, k: Tensor, v: Tensor, nseq: int, L_: int, H: int, hd: int, scale: float, mask: int,
+                       out: Tensor, probs: Optional[Tensor], drop_p: float = 0.0, drop_key: int = 0,
+                       mask_period: int = 0, table: Optional[Tensor] = None) -> Tensor:
+    """attention over 129..512 tokens (afft_attention_long_fwd): in-register mask kind and, optional, an additive fp32 [L, L] table"""
+    assert q.dtype == k.dtype == v.dtype == out.dtype
+    if table is not None:
+        assert table.dtype == torch.float32 and table.shape == (L_, L_) and table.is_contiguous() and table.device == q.device
+    L.check(L.lib().afft_attention_long_fwd(_p(q), _rowmajor(q, "q"), _p(k), _rowmajor(k, "k"), _p(v), _rowmajor(v, "v"),
+                                            _dt(q), nseq, L_, H, hd, scale, mask, mask_period, _p(table), drop_p, drop_key,
+                                            _p(out), _rowmajor(out, "out"), _p(probs), _stream()), "attention_long_fwd")
+    return out
+
+
+def attention_long_bwd(dout: Tensor, q: Tensor, k: Tensor, v: Tensor, probs: Tensor, nseq: int, L_: int, H: int, hd: int,
+                       scale: float, dq: Tensor, dk: Tensor, dv: Tensor, drop_p: float = 0.0, drop_key: int = 0):
+    assert dout.dtype == q.dtype == k.dtype == v.dtype == dq.dtype == dk.dtype == dv.dtype
+    # the hand-over between the two passes (afft_attention_long_bwd: row_term); from torch's allocator, like every buffer of the path
+    row_term = torch.empty(max(nseq * H * L_, 1), dtype=torch.float32, device=q.device)
+    L.check(L.lib().afft_attention_long_bwd(_p(dout), _rowmajor(dout, "dout"), _p(q), _rowmajor(q, "q"), _p(k),
+                                            _rowmajor(k, "k"), _p(v), _rowmajor(v, "v"), _dt(q), _p(probs), nseq, L_, H,
+                                            hd, scale, drop_p, drop_key, _p(dq), _rowmajor(dq, "dq"), _p(dk),
+                                            _rowmajor(dk, "dk"), _p(dv), _rowmajor(dv, "dv"), _p(row_term), _stream()),
+            "attention_long_bwd")
+
+
 def softmax_ce(logits: Tensor, C_: int, *, labels: Optional[Tensor] = None, soft: Optional[Tensor] = None,
                keep: Optional[Tensor] = None, gscale: float = 1.0, row_g: Optional[Tensor] = None,
                loss_sum: Optional[Tensor] = None, dlogits: Optional[Tensor] = None,

@@ -260,6 +260,24 @@ int afft_attention_bwd(const void* dout, int64_t lddo, const void* q, int64_t ld
                        int32_t H, int32_t hd, float scale, float drop_p, uint32_t drop_key, void* dq, int64_t lddq,
                        void* dk, int64_t lddk, void* dv, int64_t lddv, void* stream);
 
+/* ------------------------------------------------------------------ attention over 129..512 tokens (attention_long.hip)
+ * The same computation for the sequences the kernels above refuse (T-SA-Fuser at M*T > 128): one workgroup per (sequence, head,
+ * tile of 32 rows), an fp32 strip of scores [32][L] in LDS.  129 <= L <= 512, 1 <= hd <= 1024; anything else is an error that names
+ * the range.  dtype AFFT_F32 (fp32 arithmetic) or AFFT_BF16 (MFMA when hd % 64 == 0 and rows are 16-byte aligned, else the generic
+ * form with bf16 loads; AFFT_ATTN_GENERIC=1 forces the generic form).
+ * mask / mask_period: as afft_attention_fwd.  mask_table: optional additive fp32 [L, L] table (NULL: none), applied on top of `mask`.
+ * probs (optional in forward): fp32 [nseq, H, L, L], PRE-dropout, masked entries exactly 0; backward reads it back.
+ * Backward is two passes (dQ per query tile; dK, dV per key tile), no atomics: bitwise reproducible.  row_term: fp32 [nseq * H * L]
+ * scratch of the caller (the library never allocates); the first pass leaves sum_j P_ij dP_ij there for the second. */
+int afft_attention_long_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                            int32_t dtype, int32_t nseq, int32_t L, int32_t H, int32_t hd, float scale, int32_t mask,
+                            int32_t mask_period, const float* mask_table, float drop_p, uint32_t drop_key, void* out,
+                            int64_t ldo, float* probs, void* stream);
+int afft_attention_long_bwd(const void* dout, int64_t lddo, const void* q, int64_t ldq, const void* k, int64_t ldk,
+                            const void* v, int64_t ldv, int32_t dtype, const float* probs, int32_t nseq, int32_t L,
+                            int32_t H, int32_t hd, float scale, float drop_p, uint32_t drop_key, void* dq, int64_t lddq,
+                            void* dk, int64_t lddk, void* dv, int64_t lddv, float* row_term, void* stream);
+
 /* afft_layernorm_bwd whose incoming residual gradient dx_in is [rows / in_take, d] (row pitch lddx_in) and belongs to rows 0, in_take,
  * 2 in_take, ..: the other rows take no residual gradient (afft_attn_sublayer_t.take; in_take = 1: every row). */
 int afft_layernorm_bwd_take(const void* dy, int64_t lddy, int32_t dy_dtype, const float* x, int64_t ldx, const float* w, const float* mean,
