@@ -5,6 +5,7 @@ three-term anticipation loss, forward and backward -- behind the reference's own
     afft_amd.models.*          mirrors of the reference's models/{base_model,fusion,transformerblock,
                                future_prediction,feature_mapping}.py
     afft_amd.common.runner     mirror of common/runner.py (loss + step wrapper)
+    afft_amd.common.metric_tracking  mirror of common/metric_tracking.py (meters that take device-side label ranks)
     afft_amd.parallel          data-parallel gradient reduction over RCCL/xGMI + fused SGD
     afft_amd.ops / _lib        the C-ABI (include/afft_hip.h) via ctypes
 """
@@ -13,12 +14,14 @@ import sys as _sys
 from .runtime import precision, precision_scope, set_grad_mode, set_precision  # noqa: F401
 
 
-def install_as_models(patch_ddp: bool = False):
+def install_as_models(patch_ddp: bool = False, device_metrics: bool = False):
     """Make ``import models.fusion`` / Hydra ``_target_: models.fusion.ModalTokenCMFuser`` resolve to this
     package, so the reference's train.py / conf/ work unchanged.
     patch_ddp: also make ``torch.nn.parallel.DistributedDataParallel`` (train.py:364-368) construct
     ``afft_amd.parallel.DistributedDataParallel`` -- the wrapper that works with the gradient sink and hands the all-reduce
-    to ``afft_amd.optim.SGD`` (Hydra: ``opt.optimizer._target_=afft_amd.optim.SGD``)."""
+    to ``afft_amd.optim.SGD`` (Hydra: ``opt.optimizer._target_=afft_amd.optim.SGD``).
+    device_metrics: also register ``common.metric_tracking`` (the tracker whose recall meter takes label ranks that stay on the
+    device) and make ``Runner`` produce them by default, so that train.py's unchanged loop copies no logits to the host."""
     import importlib
     if patch_ddp:
         import torch
@@ -40,3 +43,8 @@ def install_as_models(patch_ddp: bool = False):
         mod = importlib.import_module(f"afft_amd.common.{name}")
         _sys.modules[f"common.{name}"] = mod
         setattr(common, name, mod)
+    if device_metrics:
+        mod = importlib.import_module("afft_amd.common.metric_tracking")
+        _sys.modules["common.metric_tracking"] = mod
+        setattr(common, "metric_tracking", mod)
+        importlib.import_module("afft_amd.common.runner").DEVICE_METRICS_DEFAULT = True

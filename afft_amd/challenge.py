@@ -64,6 +64,33 @@ def compute_accuracy(predictions: np.ndarray, labels: np.ndarray, classes=None):
     return top1 * 100, top5 * 100, topk_recall(predictions, labels, k=5, classes=classes) * 100
 
 
+def device_accuracy(scores: torch.Tensor, labels: torch.Tensor, classes=None):
+    """compute_accuracy for score matrices that are on the device (evaluate.py keeps them there): (top-1, top-5, mean top-5 recall)
+    in percent from ops.label_rank + ops.recall_accumulate; what reaches the host is the two accuracies and the 2 x C integer
+    counters, never the (N, C) scores.  scores fp32 [N, C] with unit column stride, labels [N] integer; classes: optional
+    {name: class id} subset (many-shot / tail classes) the recall mean is restricted to.  Ties rank as include/afft_hip.h says
+    (the lower class index first); on tie-free scores the three numbers are compute_accuracy's."""
+    scores = scores if scores.dtype == torch.float32 else scores.float()
+    scores = scores if scores.stride(-1) == 1 else scores.contiguous()
+    N, C = scores.shape
+    k = min(5, C)
+    rank = torch.empty(N, dtype=torch.int32, device=scores.device)
+    lab = torch.empty(N, dtype=torch.int64, device=scores.device)
+    acc = torch.empty(2, dtype=torch.float32, device=scores.device)
+    counters = torch.zeros(2, C, dtype=torch.int32, device=scores.device)
+    ops.label_rank(scores, C, labels=labels.reshape(-1).to(device=scores.device, dtype=torch.int64).contiguous(), k=k, rank=rank,
+                   label_out=lab, acc=acc)
+    ops.recall_accumulate(rank, lab, k, counters[0], counters[1])
+    tps, nums = counters.cpu().numpy().astype(np.float64)
+    seen = nums > 0
+    if classes is not None:
+        subset = np.zeros(C, dtype=bool)
+        subset[[int(c) for c in classes.values() if 0 <= int(c) < C]] = True
+        seen &= subset
+    top1, top5 = acc.tolist()
+    return top1, top5, float((tps[seen] / nums[seen]).mean() * 100)
+
+
 def _read_id_column(path: str) -> np.ndarray:
     """the RULSTM id tables are header-less one-column CSV files (one narration id per line)"""
     with open(path, "r", encoding="utf-8") as fh:

@@ -1,0 +1,165 @@
+// Training / evaluation metrics on the device: the rank of the label's score among the scores of its row, and the integer
+// counters of the mean top-k recall.  Semantics: common/runner.py:54-92 (MixUp adjustment of the logits, acc1 / acc5 through
+// common/utils.py:59-86) and common/metric_tracking.py:22-29 (per-class true positives / counts); tie rule and the handling
+// of labels outside [0, C) are this project's (include/afft_hip.h).
+#include "common.h"
+
+namespace {
+
+// (value, class) candidates of an arg-max; idx < 0 = no candidate.  Among equal values the LOWER class index wins.
+struct Cand { float v; int i; };
+__device__ __forceinline__ Cand better(Cand a, Cand b) {
+  if (b.i < 0) return a;
+  if (a.i < 0) return b;
+  return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a;
+}
+__device__ __forceinline__ Cand block_argmax(Cand c, Cand* sh) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    Cand t;
+    t.v = __shfl_xor(c.v, o, 64);
+    t.i = __shfl_xor(c.i, o, 64);
+    c = better(c, t);
+  }
+  __syncthreads();
+  if (lane == 0) sh[wave] = c;
+  __syncthreads();
+  Cand r = sh[0];
+  for (int w = 1; w < 4; ++w) r = better(r, sh[w]);
+  return r;
+}
+__device__ __forceinline__ int block_sum_int(int v, int* sh) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();
+  if (lane == 0) sh[wave] = v;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+// fn(c, row[c]) for every c in [0, C), thread-strided; 16-byte loads where the row allows them (vec: host-verified alignment)
+template <typename Fn>
+__device__ __forceinline__ void walk_row(const float* __restrict__ x, int C, bool vec, Fn fn) {
+  const int tid = threadIdx.x;
+  if (vec) {
+    const int C4 = C & ~3;
+    for (int c = tid * 4; c < C4; c += 1024) {
+      const f32x4 v = *(const f32x4*)(x + c);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) fn(c + e, v[e]);
+    }
+    for (int c = C4 + tid; c < C; c += 256) fn(c, x[c]);
+  } else {
+    for (int c = tid; c < C; c += 256) fn(c, x[c]);
+  }
+}
+
+// One workgroup per row.  Hard labels: the scores are the logits.  Soft targets: i1 = arg-max of the target row, i2 = arg-max
+// over c != i1, scores = logits with s[i1] += s[i2], then s[i2] = 0, label = i1; the adjusted row exists in registers only.
+__global__ __launch_bounds__(256) void label_rank_kernel(const float* __restrict__ logits, int64_t row_stride, int C,
+                                                         const int64_t* __restrict__ labels, const float* __restrict__ soft,
+                                                         int64_t lds, int vec_x, int vec_t, int32_t* __restrict__ rank,
+                                                         int64_t* __restrict__ label_out) {
+  __shared__ Cand shc[4];
+  __shared__ int shi[4];
+  const int64_t row = blockIdx.x;
+  const float* x = logits + row * row_stride;
+  int64_t lab;
+  int i1 = -1, i2 = -1;
+  if (soft) {
+    const float* t = soft + row * lds;
+    Cand a = {0.f, -1}, b = {0.f, -1};      // this thread's best and second best target
+    walk_row(t, C, vec_t != 0, [&](int c, float v) {
+      const Cand n = {v, c};
+      // candidates arrive in ascending class order, so an equal value never displaces an earlier one
+      if (a.i < 0 || v > a.v) { b = a; a = n; }
+      else if (b.i < 0 || v > b.v) b = n;
+    });
+    const Cand top = block_argmax(a, shc);
+    i1 = top.i;
+    const Cand second = block_argmax(a.i == i1 ? b : a, shc);
+    i2 = second.i;      // -1 when C == 1: nothing to fold in
+    lab = i1;
+  } else {
+    lab = labels[row];
+  }
+  const bool valid = lab >= 0 && lab < C;       // uniform per block
+  if (!valid) {      // never a hit; nothing is read at the label's position
+    if (threadIdx.x == 0) { rank[row] = C; label_out[row] = lab; }
+    return;
+  }
+  const int l = (int)lab;
+  const float folded = i2 >= 0 ? x[i1] + x[i2] : 0.f;      // i2 >= 0: soft targets, and l == i1
+  const float sl = i2 >= 0 ? folded : x[l];
+  int n = 0;
+  walk_row(x, C, vec_x != 0, [&](int c, float v) {
+    if (i2 >= 0) v = c == i2 ? 0.f : c == i1 ? folded : v;
+    n += (c != l && (v > sl || (v == sl && c < l))) ? 1 : 0;
+  });
+  n = block_sum_int(n, shi);
+  if (threadIdx.x == 0) { rank[row] = n; label_out[row] = lab; }
+}
+
+// acc[0] = #{rank < 1} * scale, acc[1] = #{rank < k} * scale: one workgroup, integer counts
+__global__ __launch_bounds__(256) void rank_hits_kernel(const int32_t* __restrict__ rank, int rows, int k, float scale,
+                                                        float* __restrict__ acc) {
+  __shared__ int shi[4];
+  int h1 = 0, hk = 0;
+  for (int64_t r = threadIdx.x; r < rows; r += 256) {
+    const int v = rank[r];
+    h1 += v < 1 ? 1 : 0;
+    hk += v < k ? 1 : 0;
+  }
+  h1 = block_sum_int(h1, shi);
+  hk = block_sum_int(hk, shi);
+  if (threadIdx.x == 0) { acc[0] = (float)h1 * scale; acc[1] = (float)hk * scale; }
+}
+
+__global__ __launch_bounds__(256) void recall_accumulate_kernel(const int32_t* __restrict__ rank, const int64_t* __restrict__ label,
+                                                                int rows, int C, int k, int32_t* __restrict__ tps,
+                                                                int32_t* __restrict__ nums) {
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (r >= rows) return;
+  const int64_t l = label[r];
+  if (l < 0 || l >= C) return;
+  atomicAdd(nums + l, 1);
+  if (rank[r] < k) atomicAdd(tps + l, 1);
+}
+
+}  // namespace
+
+extern "C" int afft_label_rank(const float* logits, int64_t row_stride, int32_t rows, int32_t C, const int64_t* labels,
+                               const float* soft, int64_t lds, int32_t k, float acc_scale, int32_t* rank, int64_t* label_out,
+                               float* acc, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  AFFT_CHECK(logits && rank && label_out, "label_rank: null logits / rank / label_out");
+  AFFT_CHECK((labels != nullptr) != (soft != nullptr), "label_rank: give exactly one of labels / soft targets");
+  AFFT_CHECK(rows >= 1 && C >= 1, "label_rank: rows >= 1 and C >= 1 (got %d, %d)", rows, C);
+  AFFT_CHECK(k >= 1 && k <= C, "label_rank: 1 <= k <= C (got k = %d, C = %d)", k, C);
+  AFFT_CHECK(row_stride >= C, "label_rank: row_stride %lld < C = %d", (long long)row_stride, C);
+  AFFT_CHECK(!soft || lds >= C, "label_rank: soft-target row stride %lld < C = %d", (long long)lds, C);
+  const int vec_x = ((uintptr_t)logits & 15) == 0 && (row_stride & 3) == 0;
+  const int vec_t = soft && ((uintptr_t)soft & 15) == 0 && (lds & 3) == 0;
+  hipLaunchKernelGGL(label_rank_kernel, dim3(rows), dim3(256), 0, stream, logits, row_stride, C, labels, soft, lds, vec_x, vec_t,
+                     rank, label_out);
+  AFFT_LAUNCH_CHECK();
+  if (acc) {
+    hipLaunchKernelGGL(rank_hits_kernel, dim3(1), dim3(256), 0, stream, rank, rows, k, acc_scale, acc);
+    AFFT_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+extern "C" int afft_recall_accumulate(const int32_t* rank, const int64_t* label, int32_t rows, int32_t C, int32_t k, int32_t* tps,
+                                      int32_t* nums, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  AFFT_CHECK(rank && label && tps && nums, "recall_accumulate: null pointer");
+  AFFT_CHECK(rows >= 1 && C >= 1, "recall_accumulate: rows >= 1 and C >= 1 (got %d, %d)", rows, C);
+  AFFT_CHECK(k >= 1 && k <= C, "recall_accumulate: 1 <= k <= C (got k = %d, C = %d)", k, C);
+  hipLaunchKernelGGL(recall_accumulate_kernel, dim3((unsigned)(((int64_t)rows + 255) / 256)), dim3(256), 0, stream, rank, label, rows,
+                     C, k, tps, nums);
+  AFFT_LAUNCH_CHECK();
+  return 0;
+}

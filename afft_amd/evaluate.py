@@ -5,7 +5,9 @@ The reference copies every batch of logits to the host (``.detach().cpu().numpy(
 concatenates there and marginalises verbs / nouns in numpy.  Here the logits of the branch the reference keeps (the only
 modality, or 'all-fused') stay on the device, are concatenated once, marginalised by ``afft_amd.challenge.
 marginalize_scores`` (row softmax + two fp32 MFMA GEMMs) and leave the device in ONE copy per result.  The accuracy
-bookkeeping over the dataset's annotations (``challenge.compute_accuracies_epic``) stays with the caller.
+bookkeeping over the dataset's annotations (``challenge.compute_accuracies_epic``) stays with the caller; for score matrices
+that should not leave the device at all, ``challenge.device_accuracy(scores, labels, classes)`` gives top-1 / top-5 / mean top-5
+recall from label ranks and integer per-class counters computed there.
 """
 from __future__ import annotations
 

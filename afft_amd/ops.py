@@ -660,6 +660,35 @@ def softmax_rows(x: Tensor, y: Tensor):
     return y
 
 
+def label_rank(logits: Tensor, C_: int, *, labels: Optional[Tensor] = None, soft: Optional[Tensor] = None, k: int, rank: Tensor,
+               label_out: Tensor, acc: Optional[Tensor] = None):
+    """logits fp32 [rows, >= C] VIEW with unit column stride (e.g. x[:, 0, :] of the classifier output); labels int64 [rows] or soft
+    fp32 [rows, C].  rank int32 [rows], label_out int64 [rows]; acc fp32 [2] = (acc1, acc-k) in percent (include/afft_hip.h)."""
+    rows = logits.shape[0]
+    assert logits.dtype == torch.float32
+    assert rank.dtype == torch.int32 and rank.numel() == rows and rank.is_contiguous()
+    assert label_out.dtype == torch.int64 and label_out.numel() == rows and label_out.is_contiguous()
+    if labels is not None:
+        assert labels.dtype == torch.int64 and labels.numel() == rows and labels.is_contiguous()
+    if soft is not None:
+        assert soft.dtype == torch.float32 and soft.shape[0] == rows
+    if acc is not None:
+        assert acc.dtype == torch.float32 and acc.numel() == 2 and acc.is_contiguous()
+    L.check(L.lib().afft_label_rank(_p(logits), _rowmajor(logits, "logits"), rows, C_, _p(labels), _p(soft),
+                                    _rowmajor(soft, "soft") if soft is not None else 0, k, 100.0 / max(rows, 1), _p(rank), _p(label_out),
+                                    _p(acc), _stream()), "label_rank")
+    return rank, label_out
+
+
+def recall_accumulate(rank: Tensor, label: Tensor, k: int, tps: Tensor, nums: Tensor):
+    """tps / nums int32 [C] += the per-class top-k hits / row counts of (rank, label) as ops.label_rank wrote them."""
+    rows = rank.numel()
+    assert rank.dtype == torch.int32 and rank.is_contiguous() and label.dtype == torch.int64 and label.is_contiguous()
+    assert label.numel() == rows and tps.dtype == nums.dtype == torch.int32 and tps.numel() == nums.numel()
+    assert tps.is_contiguous() and nums.is_contiguous()
+    L.check(L.lib().afft_recall_accumulate(_p(rank), _p(label), rows, tps.numel(), k, _p(tps), _p(nums), _stream()), "recall_accumulate")
+
+
 def zero_mask_frames(x: Tensor, k: int, key: int):
     """x fp32 [B, T, ...] contiguous: zero k random frames of every clip in place."""
     assert x.is_contiguous() and x.dtype == torch.float32 and x.dim() >= 2

@@ -439,6 +439,30 @@ int afft_mixup_labels(const int64_t* labels, int32_t B, int32_t rows_per_sample,
 int afft_zero_mask_frames(float* x, int32_t B, int32_t T, int64_t C, int32_t k, uint32_t key, void* stream);
 /* Row softmax of wide fp32 rows: action probabilities for the verb / noun marginalisation (challenge.py:196-203). */
 int afft_softmax_rows(const float* x, int64_t ldx, int32_t rows, int32_t C, float* y, int64_t ldy, void* stream);
+/* Training / evaluation metrics without anything of width C leaving the device (common/runner.py:54-92, common/utils.py:59-86,
+ * common/metric_tracking.py:22-29).  Every number -- top-k hit, acc1 / acc5, mean top-k recall -- is a function of one integer per row,
+ * the RANK of the label's score among the scores of its row:
+ *   rank[r] = #{ c != label : s[c] > s[label]  or  (s[c] == s[label] and c < label) },   top-k hit = rank < k.
+ * Row r is read at logits + r * row_stride (row_stride >= C: logits[:, 0, :] of the (B, T', pitch) classifier output is walked where it lies).
+ *   labels: hard labels int64 [rows]; label_out[r] = labels[r] and the scores are the logits as they are;
+ *   soft:   MixUp targets fp32 [rows, C], row stride lds (exactly one of labels / soft): i1 = arg-max of the target row, i2 = arg-max over
+ *           c != i1, scores = logits with s[i1] += s[i2], then s[i2] = 0 (common/runner.py:60-74); label_out[r] = i1.  The adjusted row is
+ *           never materialised.  C == 1: there is no i2 and nothing is folded in.
+ * TIE RULE (this project's definition; torch.topk and numpy.argsort leave ties unspecified): in both arg-max steps and in the rank the
+ * LOWER class index wins.  On tie-free rows rank < k is exactly "the label is among the k largest scores".
+ * LABELS OUTSIDE [0, C), -1 included: rank = C (never a hit), nothing out of bounds is read, and afft_recall_accumulate leaves the row
+ * out of tps / nums.  A deliberate difference: the reference's meter would index tps[-1] (the last class) for a label of -1.
+ * acc (optional, fp32 [2], overwritten): acc[0] = float(#{rank < 1}) * acc_scale, acc[1] = float(#{rank < k}) * acc_scale; the hits are counted
+ * as integers and every row counts in the denominator.  The caller passes acc_scale = (float)(100.0 / rows), computed in double: the
+ * arithmetic of common/utils.py:84-85.
+ * rows >= 1, C >= 1, 1 <= k <= C; no upper limit on rows.  One launch, two with acc; no host sync, no allocation, no scratch. */
+int afft_label_rank(const float* logits, int64_t row_stride, int32_t rows, int32_t C, const int64_t* labels, const float* soft,
+                    int64_t lds, int32_t k, float acc_scale, int32_t* rank, int64_t* label_out, float* acc, void* stream);
+/* The counters of MeanTopKRecallMeter (common/metric_tracking.py:26-29) from the two vectors above: for every row whose label lies in
+ * [0, C), nums[label] += 1 and tps[label] += (rank < k); tps / nums int32 [C], ADDED to.  Integer atomics: the result has the same bits on
+ * every run, whatever the order (no float atomics anywhere in this library).  One launch. */
+int afft_recall_accumulate(const int32_t* rank, const int64_t* label, int32_t rows, int32_t C, int32_t k, int32_t* tps, int32_t* nums,
+                           void* stream);
 /* Token means of the fusers without a modality token (models/fusion.py:114-116 CMFuser: mean over the M tokens of a
  * frame; :207-210 T-SA-Fuser: mean over the M modality tokens of a frame position): x fp32 [G, S, W] contiguous,
  *   afft_group_sum:   y[g, :]     = scale * sum_s x[g, s, :]
