@@ -23,7 +23,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const T* __restrict__ q, 
                                                        int hd, float scale, int mask, int period, unsigned dthresh,
                                                        unsigned dkey, float dinv, const unsigned* __restrict__ salt,
                                                        T* __restrict__ out, int64_t ldo, float* __restrict__ probs,
-                                                       const float* __restrict__ addm) {      // addm: additive fp32 [L][L] table or null
+                                                       const float* __restrict__ addm, int64_t sb, int64_t sh,
+                                                       int64_t si) {      // addm: additive fp32 bias or null; element (seq, h, i, j) at addm[seq*sb + h*sh + i*si + j] (a stride of 0 broadcasts; the [L][L] table is sb = sh = 0, si = L)
   if (salt) dkey ^= *salt;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float (*sc)[LM + 1] = reinterpret_cast<float (*)[LM + 1]>(smem_raw);
@@ -33,6 +34,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const T* __restrict__ q, 
   const T* qh = q + row0 * ldq + (int64_t)h * hd;
   const T* kh = k + row0 * ldk + (int64_t)h * hd;
   const T* vh = v + row0 * ldv + (int64_t)h * hd;
+  const float* addh = addm ? addm + seq * sb + h * sh : nullptr;
   // scores: a wave owns query rows i = wave, wave + 4, ...: the row is read once into registers (lanes stride the head
   // dimension) and dotted with 4 key rows at a time, so 4 x hd/64 independent loads are in flight per reduction
   // (one (i, j) pair per iteration was a chain of dependent L2 round trips: 1.8 ms per launch at L = 64, hd = 512)
@@ -57,7 +59,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const T* __restrict__ q, 
         const int j = j0 + u;
         if (j < L) {
           float sv = masked(mask, period, i, j) ? -INFINITY : wave_sum(acc4[u]) * scale;
-          if (addm) sv += addm[i * L + j];      // models/transformerblock.py:27-28: attn = attn + attn_mask (any values, -inf included)
+          if (addh) sv += addh[i * si + j];      // models/transformerblock.py:27-28: attn = attn + attn_mask (any values, -inf included)
           if (lane == 0) sc[i][j] = sv;
         }
       }
@@ -201,14 +203,14 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const T* __restrict__ dou
 template <typename T, int LM>
 int launch_fwd(dim3 grid, hipStream_t stream, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
                int L, int H, int hd, float scale, int mask, int period, const DropParams& dp, void* out, int64_t ldo,
-               float* probs, const float* addm = nullptr) {
+               float* probs, const float* addm = nullptr, int64_t sb = 0, int64_t sh = 0, int64_t si = 0) {
   constexpr size_t lds = sizeof(float) * LM * (LM + 1);
   auto kern = attn_fwd_kernel<T, LM>;
   static std::atomic<uint64_t> attr_done{0};
   if (lds > 48 * 1024)
     if (int rc = afft_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, &attr_done)) return rc;
   hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, (const T*)q, ldq, (const T*)k, ldk, (const T*)v, ldv, L, H, hd, scale,
-                     mask, period, dp.thresh, dp.key, dp.inv_keep, dp.salt, (T*)out, ldo, probs, addm);
+                     mask, period, dp.thresh, dp.key, dp.inv_keep, dp.salt, (T*)out, ldo, probs, addm, sb, sh, si);
   return 0;
 }
 template <typename T, int LM>
@@ -275,16 +277,16 @@ extern "C" int afft_attention_fwd(const void* q, int64_t ldq, const void* k, int
   return 0;
 }
 
-extern "C" int afft_attention_fwd_table(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
-                                        int32_t dtype, int32_t nseq, int32_t L, int32_t H, int32_t hd, float scale,
-                                        const float* mask_table, float drop_p, uint32_t drop_key, void* out, int64_t ldo,
-                                        float* probs, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  AFFT_CHECK(q && k && v && out && mask_table, "attention_fwd_table: null pointer");
-  AFFT_CHECK(L >= 1 && L <= LMAX, "attention_fwd_table: sequence length %d outside 1..%d", L, LMAX);
-  AFFT_CHECK(drop_p >= 0.f && drop_p < 1.f, "attention_fwd_table: dropout p outside [0,1)");
-  AFFT_CHECK(hd >= 1 && hd <= 1024, "attention_fwd_table: head dimension %d outside 1..1024", hd);
-  AFFT_CHECK(dtype == AFFT_F32 || dtype == AFFT_BF16, "attention_fwd_table: bad dtype %d", dtype);
+// the arbitrary additive bias, generic kernel: element (seq, h, i, j) at bias[seq*sb + h*sh + i*si + j]
+static int attention_fwd_bias_impl(const char* who, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                                   int32_t dtype, int32_t nseq, int32_t L, int32_t H, int32_t hd, float scale, const float* bias,
+                                   int64_t sb, int64_t sh, int64_t si, float drop_p, uint32_t drop_key, void* out, int64_t ldo,
+                                   float* probs, hipStream_t stream) {
+  AFFT_CHECK(q && k && v && out && bias, "%s: null pointer", who);
+  AFFT_CHECK(L >= 1 && L <= LMAX, "%s: sequence length %d outside 1..%d", who, L, LMAX);
+  AFFT_CHECK(drop_p >= 0.f && drop_p < 1.f, "%s: dropout p outside [0,1)", who);
+  AFFT_CHECK(hd >= 1 && hd <= 1024, "%s: head dimension %d outside 1..1024", who, hd);
+  AFFT_CHECK(dtype == AFFT_F32 || dtype == AFFT_BF16, "%s: bad dtype %d", who, dtype);
   if (nseq == 0) return 0;
   const int64_t es_ = dtype == AFFT_F32 ? 4 : 2, rw_ = (int64_t)nseq * L * H * hd, pb_ = probs ? (int64_t)nseq * H * L * L * 4 : 0;
   AfftKernelScope ktrace(AFFT_K_ATTN_FWD, nseq * L, H * hd, 4 * es_ * rw_ + pb_, 4 * (int64_t)nseq * H * L * L * hd, stream);
@@ -292,13 +294,32 @@ extern "C" int afft_attention_fwd_table(const void* q, int64_t ldq, const void* 
   const DropParams dp = make_drop(&dd);
   const dim3 grid(nseq * H);
   int rc;
-#define FWD(T, LM) launch_fwd<T, LM>(grid, stream, q, ldq, k, ldk, v, ldv, L, H, hd, scale, AFFT_MASK_NONE, 0, dp, out, ldo, probs, mask_table)
+#define FWD(T, LM) launch_fwd<T, LM>(grid, stream, q, ldq, k, ldk, v, ldv, L, H, hd, scale, AFFT_MASK_NONE, 0, dp, out, ldo, probs, bias, sb, sh, si)
   if (dtype == AFFT_F32) rc = L <= 32 ? FWD(float, 32) : L <= 64 ? FWD(float, 64) : FWD(float, 128);
   else rc = L <= 32 ? FWD(bf16_t, 32) : L <= 64 ? FWD(bf16_t, 64) : FWD(bf16_t, 128);
 #undef FWD
   if (rc) return rc;
   AFFT_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int afft_attention_fwd_table(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                                        int32_t dtype, int32_t nseq, int32_t L, int32_t H, int32_t hd, float scale,
+                                        const float* mask_table, float drop_p, uint32_t drop_key, void* out, int64_t ldo,
+                                        float* probs, void* stream_) {
+  return attention_fwd_bias_impl("attention_fwd_table", q, ldq, k, ldk, v, ldv, dtype, nseq, L, H, hd, scale, mask_table, 0, 0, L,
+                                 drop_p, drop_key, out, ldo, probs, (hipStream_t)stream_);
+}
+
+extern "C" int afft_attention_fwd_bias(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                                       int32_t dtype, int32_t nseq, int32_t L, int32_t H, int32_t hd, float scale,
+                                       const float* bias, int64_t sb, int64_t sh, int64_t si, float drop_p, uint32_t drop_key,
+                                       void* out, int64_t ldo, float* probs, void* stream_) {
+  AFFT_CHECK(sb >= 0 && sh >= 0 && si >= 0, "attention_fwd_bias: negative bias stride (sb=%lld, sh=%lld, si=%lld)", (long long)sb,
+             (long long)sh, (long long)si);
+  AFFT_CHECK((((uintptr_t)bias) & 3) == 0, "attention_fwd_bias: bias pointer %p is not 4-byte aligned", (const void*)bias);
+  return attention_fwd_bias_impl("attention_fwd_bias", q, ldq, k, ldk, v, ldv, dtype, nseq, L, H, hd, scale, bias, sb, sh, si, drop_p,
+                                 drop_key, out, ldo, probs, (hipStream_t)stream_);
 }
 
 extern "C" int afft_attention_fwd_split(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, int64_t in_lo,

@@ -17,6 +17,9 @@
 // swizzle of attention_mfma.hip (row fragments by ds_read_b128, transposed fragments by ds_read_b64_tr_b16); any other bf16 shape, or
 // AFFT_ATTN_GENERIC=1, takes the generic form with bf16 loads.
 // Semantics are those of attention.hip: probs = PRE-dropout probabilities, masked entries exactly 0, dropout mask from (key, index).
+// The additive bias of the forward pass is read through element strides (0 = broadcast over batch / head / row: afft_attention_long_fwd_bias);
+// its gradient, for every L from 1 to 512, is the first half of the dQ pass without the score scale plus an ordered sum over the
+// broadcast dimensions (afft_attention_bias_bwd: bias_bwd_ds_kernel, bias_bwd_reduce_kernel).
 #include <stdlib.h>
 
 #include "common.h"
@@ -33,7 +36,10 @@ struct LongArgs {
   void *out, *dq, *dk, *dv;
   int64_t ldo, lddq, lddk, lddv;
   float* probs;           // fwd: written (may be null); bwd: read
-  const float* addm;      // fwd: additive fp32 [L][L] table or null
+  const float* addm;      // fwd: additive fp32 bias or null, element (seq, h, i, j) at addm[seq*sb + h*sh + i*si + j]
+  int64_t sb, sh, si;     //      (a stride of 0 broadcasts; the [L][L] table is sb = sh = 0, si = L)
+  float* dbias;           // bias gradient: dS of (seq, h, i, j) to dbias[seq*ob + h*oh + i*oi + j]
+  int64_t ob, oh, oi;
   float* row_term;        // bwd: sum_j P_ij dP_ij, [nseq, H, L]
   int L, Lp, H, hd, hc, ntiles;
   float scale;
@@ -274,6 +280,7 @@ __global__ __launch_bounds__(256) void long_fwd_kernel(const LongArgs a) {
   const T* qt = (const T*)a.q + (row0 + t0) * a.ldq + (int64_t)h * hd;
   const T* kh = (const T*)a.k + row0 * a.ldk + (int64_t)h * hd;
   const T* vh = (const T*)a.v + row0 * a.ldv + (int64_t)h * hd;
+  const float* addh = a.addm ? a.addm + seq * a.sb + h * a.sh : nullptr;
   dots<T, MFMA>(qt, a.ldq, tv, kh, a.ldk, L, a, strip, sld, stage);
   // masked softmax over the whole strip: a wave owns 8 rows, lanes stride the keys
   for (int r = wave * (QT / 4); r < (wave + 1) * (QT / 4); ++r) {
@@ -286,7 +293,7 @@ __global__ __launch_bounds__(256) void long_fwd_kernel(const LongArgs a) {
     float m = -INFINITY;
     for (int j = lane; j < L; j += 64) {
       float sv = masked(a.mask, a.period, i, j) ? -INFINITY : sr[j] * a.scale;
-      if (a.addm) sv += a.addm[i * L + j];      // models/transformerblock.py:27-28: attn = attn + attn_mask (any values, -inf included)
+      if (addh) sv += addh[i * a.si + j];      // models/transformerblock.py:27-28: attn = attn + attn_mask (any values, -inf included)
       sr[j] = sv;
       m = fmaxf(m, sv);
     }
@@ -383,6 +390,58 @@ __global__ __launch_bounds__(256) void long_bwd_kv_kernel(const LongArgs a) {
   matmul<T, MFMA>(strip, sld, qh, a.ldq, L, a, stage, (T*)a.dk + (row0 + t0) * a.lddk + (int64_t)h * hd, a.lddk, tv);
 }
 
+// dS = P (dP - sum_j P dP) of one tile of query rows, WITHOUT the score scale: the gradient of an additive bias (it is added after the
+// scaling).  The first half of long_bwd_q_kernel, for 1 <= L <= 512; every (seq, h, i, j) is written once, to the caller's strides.
+template <typename T, bool MFMA>
+__global__ __launch_bounds__(256) void bias_bwd_ds_kernel(const LongArgs a) {
+  LONG_PROLOGUE();
+  const T* dot_ = (const T*)a.dout + (row0 + t0) * a.lddo + (int64_t)h * hd;
+  const T* vh = (const T*)a.v + row0 * a.ldv + (int64_t)h * hd;
+  dots<T, MFMA>(dot_, a.lddo, tv, vh, a.ldv, L, a, strip, sld, stage);     // dP' (gradient of the dropped-out probabilities)
+  for (int r = wave * (QT / 4); r < (wave + 1) * (QT / 4); ++r) {
+    float* sr = strip + r * sld;
+    const int i = t0 + r;
+    if (i >= L) continue;
+    const int64_t pbase = (((int64_t)seq * H + h) * L + i) * L;
+    const float* pr = a.probs + pbase;
+    float dsum = 0.f;
+    for (int j = lane; j < L; j += 64) {
+      const float m = (a.dthresh && !drop_keep(dkey, (unsigned)pbase + j, a.dthresh)) ? 0.f : a.dinv;
+      const float dp = sr[j] * m;               // dP = dP' * m / (1 - p)
+      sr[j] = dp;
+      dsum += pr[j] * dp;
+    }
+    dsum = wave_sum(dsum);
+    float* dst = a.dbias + seq * a.ob + h * a.oh + i * a.oi;
+    for (int j = lane; j < L; j += 64) dst[j] = pr[j] * (sr[j] - dsum);
+  }
+}
+
+// dbias = the sum of ds [nseq, H, L, L] over the broadcast dimensions (rb / rh / ri: batch / head / row is summed), one output row
+// per blockIdx.x and 64 columns per blockIdx.y.  Wave w adds the terms w, w + 4, .. in that order and the four partial sums are
+// combined in a fixed order: the same input gives the same bits.
+__global__ __launch_bounds__(256) void bias_bwd_reduce_kernel(const float* __restrict__ ds, float* __restrict__ dbias, int nseq, int H,
+                                                              int L, int rb, int rh, int ri, int64_t ob, int64_t oh, int64_t oi) {
+  __shared__ float part[4][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int j = blockIdx.y * 64 + lane;
+  int row = blockIdx.x;
+  const int io = ri ? 0 : row % L;
+  row /= ri ? 1 : L;
+  const int ho = rh ? 0 : row % H;
+  const int bo = row / (rh ? 1 : H);
+  const int nb = rb ? nseq : 1, nh = rh ? H : 1, ni = ri ? L : 1;
+  float acc = 0.f;
+  if (j < L)
+    for (int t = wave; t < nb * nh * ni; t += 4) {
+      const int i = t % ni, hh = (t / ni) % nh, b = t / (ni * nh);
+      acc += ds[((((int64_t)(bo + b)) * H + ho + hh) * L + io + i) * L + j];
+    }
+  part[wave][lane] = acc;
+  __syncthreads();
+  if (wave == 0 && j < L) dbias[bo * ob + ho * oh + io * oi + j] = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
+}
+
 bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 bool al8(const void* p) { return (((uintptr_t)p) & 7) == 0; }
 bool use_mfma_attention() {
@@ -417,26 +476,25 @@ void fill_common(LongArgs& a, int L, int H, int hd, float scale, float drop_p, u
 
 }  // namespace
 
-extern "C" int afft_attention_long_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
-                                       int32_t dtype, int32_t nseq, int32_t L, int32_t H, int32_t hd, float scale, int32_t mask,
-                                       int32_t mask_period, const float* mask_table, float drop_p, uint32_t drop_key, void* out,
-                                       int64_t ldo, float* probs, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  AFFT_CHECK(q && k && v && out, "attention_long_fwd: null pointer");
-  AFFT_CHECK(L >= LLO && L <= LHI, "attention_long_fwd: sequence length %d outside %d..%d", L, LLO, LHI);
-  AFFT_CHECK(mask >= AFFT_MASK_NONE && mask <= AFFT_MASK_BLOCKCAUSAL, "attention_long_fwd: bad mask %d", mask);
+static int attention_long_fwd_impl(const char* who, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                                   int32_t dtype, int32_t nseq, int32_t L, int32_t H, int32_t hd, float scale, int32_t mask,
+                                   int32_t mask_period, const float* bias, int64_t sb, int64_t sh, int64_t si, float drop_p,
+                                   uint32_t drop_key, void* out, int64_t ldo, float* probs, hipStream_t stream) {
+  AFFT_CHECK(q && k && v && out, "%s: null pointer", who);
+  AFFT_CHECK(L >= LLO && L <= LHI, "%s: sequence length %d outside %d..%d", who, L, LLO, LHI);
+  AFFT_CHECK(mask >= AFFT_MASK_NONE && mask <= AFFT_MASK_BLOCKCAUSAL, "%s: bad mask %d", who, mask);
   AFFT_CHECK(mask != AFFT_MASK_BLOCKCAUSAL || (mask_period >= 1 && L % mask_period == 0),
-             "attention_long_fwd: block-causal mask needs a period that divides L (L=%d, period=%d)", L, mask_period);
-  AFFT_CHECK(drop_p >= 0.f && drop_p < 1.f, "attention_long_fwd: dropout p outside [0,1)");
-  AFFT_CHECK(hd >= 1 && hd <= 1024, "attention_long_fwd: head dimension %d outside 1..1024", hd);
-  AFFT_CHECK(dtype == AFFT_F32 || dtype == AFFT_BF16, "attention_long_fwd: bad dtype %d", dtype);
-  AFFT_CHECK(nseq >= 0 && H >= 1, "attention_long_fwd: bad nseq %d / H %d", nseq, H);
+             "%s: block-causal mask needs a period that divides L (L=%d, period=%d)", who, L, mask_period);
+  AFFT_CHECK(drop_p >= 0.f && drop_p < 1.f, "%s: dropout p outside [0,1)", who);
+  AFFT_CHECK(hd >= 1 && hd <= 1024, "%s: head dimension %d outside 1..1024", who, hd);
+  AFFT_CHECK(dtype == AFFT_F32 || dtype == AFFT_BF16, "%s: bad dtype %d", who, dtype);
+  AFFT_CHECK(nseq >= 0 && H >= 1, "%s: bad nseq %d / H %d", who, nseq, H);
   if (nseq == 0) return 0;
   const int64_t es_ = dtype == AFFT_F32 ? 4 : 2, rw_ = (int64_t)nseq * L * H * hd, pb_ = probs ? (int64_t)nseq * H * L * L * 4 : 0;
   AfftKernelScope ktrace(AFFT_K_ATTN_FWD, nseq * L, H * hd, 4 * es_ * rw_ + pb_, 4 * (int64_t)nseq * H * L * L * hd, stream);
   LongArgs a = {};
   a.q = q; a.k = k; a.v = v; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
-  a.out = out; a.ldo = ldo; a.probs = probs; a.addm = mask_table;
+  a.out = out; a.ldo = ldo; a.probs = probs; a.addm = bias; a.sb = sb; a.sh = sh; a.si = si;
   a.mask = mask; a.period = mask == AFFT_MASK_BLOCKCAUSAL ? mask_period : 1;
   fill_common(a, L, H, hd, scale, drop_p, drop_key);
   const bool mfma = dtype == AFFT_BF16 && use_mfma_attention() && hd % 64 == 0 && ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 &&
@@ -446,6 +504,26 @@ extern "C" int afft_attention_long_fwd(const void* q, int64_t ldq, const void* k
   else LONG_LAUNCH((long_fwd_kernel<bf16_t, false>));
   AFFT_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int afft_attention_long_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                                       int32_t dtype, int32_t nseq, int32_t L, int32_t H, int32_t hd, float scale, int32_t mask,
+                                       int32_t mask_period, const float* mask_table, float drop_p, uint32_t drop_key, void* out,
+                                       int64_t ldo, float* probs, void* stream_) {
+  return attention_long_fwd_impl("attention_long_fwd", q, ldq, k, ldk, v, ldv, dtype, nseq, L, H, hd, scale, mask, mask_period,
+                                 mask_table, 0, 0, L, drop_p, drop_key, out, ldo, probs, (hipStream_t)stream_);
+}
+
+extern "C" int afft_attention_long_fwd_bias(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                                            int32_t dtype, int32_t nseq, int32_t L, int32_t H, int32_t hd, float scale,
+                                            const float* bias, int64_t sb, int64_t sh, int64_t si, float drop_p, uint32_t drop_key,
+                                            void* out, int64_t ldo, float* probs, void* stream_) {
+  AFFT_CHECK(bias, "attention_long_fwd_bias: null pointer");
+  AFFT_CHECK(sb >= 0 && sh >= 0 && si >= 0, "attention_long_fwd_bias: negative bias stride (sb=%lld, sh=%lld, si=%lld)", (long long)sb,
+             (long long)sh, (long long)si);
+  AFFT_CHECK((((uintptr_t)bias) & 3) == 0, "attention_long_fwd_bias: bias pointer %p is not 4-byte aligned", (const void*)bias);
+  return attention_long_fwd_impl("attention_long_fwd_bias", q, ldq, k, ldk, v, ldv, dtype, nseq, L, H, hd, scale, AFFT_MASK_NONE, 0, bias,
+                                 sb, sh, si, drop_p, drop_key, out, ldo, probs, (hipStream_t)stream_);
 }
 
 extern "C" int afft_attention_long_bwd(const void* dout, int64_t lddo, const void* q, int64_t ldq, const void* k, int64_t ldk,
@@ -475,6 +553,45 @@ extern "C" int afft_attention_long_bwd(const void* dout, int64_t lddo, const voi
   if (dtype == AFFT_F32) { LONG_LAUNCH((long_bwd_q_kernel<float, false>)); LONG_LAUNCH((long_bwd_kv_kernel<float, false>)); }
   else if (mfma) { LONG_LAUNCH((long_bwd_q_kernel<bf16_t, true>)); LONG_LAUNCH((long_bwd_kv_kernel<bf16_t, true>)); }
   else { LONG_LAUNCH((long_bwd_q_kernel<bf16_t, false>)); LONG_LAUNCH((long_bwd_kv_kernel<bf16_t, false>)); }
+  AFFT_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int afft_attention_bias_bwd(const void* dout, int64_t lddo, const void* v, int64_t ldv, int32_t dtype, const float* probs,
+                                       int32_t nseq, int32_t L, int32_t H, int32_t hd, float drop_p, uint32_t drop_key, float* dbias,
+                                       int64_t sb, int64_t sh, int64_t si, float* scratch, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  AFFT_CHECK(dout && v && probs && dbias, "attention_bias_bwd: null pointer");
+  AFFT_CHECK(L >= 1 && L <= LHI, "attention_bias_bwd: sequence length %d outside 1..%d", L, LHI);
+  AFFT_CHECK(drop_p >= 0.f && drop_p < 1.f, "attention_bias_bwd: dropout p outside [0,1)");
+  AFFT_CHECK(hd >= 1 && hd <= 1024, "attention_bias_bwd: head dimension %d outside 1..1024", hd);
+  AFFT_CHECK(dtype == AFFT_F32 || dtype == AFFT_BF16, "attention_bias_bwd: bad dtype %d", dtype);
+  AFFT_CHECK(nseq >= 0 && H >= 1, "attention_bias_bwd: bad nseq %d / H %d", nseq, H);
+  AFFT_CHECK(sb >= 0 && sh >= 0 && si >= 0, "attention_bias_bwd: negative bias stride (sb=%lld, sh=%lld, si=%lld)", (long long)sb,
+             (long long)sh, (long long)si);
+  AFFT_CHECK((((uintptr_t)dbias) & 3) == 0, "attention_bias_bwd: dbias pointer %p is not 4-byte aligned", (void*)dbias);
+  const bool reduce = sb == 0 || sh == 0 || si == 0;
+  AFFT_CHECK(!reduce || (scratch && (((uintptr_t)scratch) & 3) == 0),
+             "attention_bias_bwd: a broadcast bias needs 4-byte aligned scratch of nseq*H*L*L floats (scratch=%p)", (void*)scratch);
+  if (nseq == 0) return 0;
+  const int64_t es_ = dtype == AFFT_F32 ? 4 : 2, rw_ = (int64_t)nseq * L * H * hd, pb_ = (int64_t)nseq * H * L * L * 4;
+  AfftKernelScope ktrace(AFFT_K_ATTN_BWD, nseq * L, H * hd, 2 * es_ * rw_ + (reduce ? 3 : 2) * pb_, 2 * (int64_t)nseq * H * L * L * hd, stream);
+  LongArgs a = {};
+  a.dout = dout; a.v = v; a.lddo = lddo; a.ldv = ldv;
+  a.probs = const_cast<float*>(probs);
+  a.mask = AFFT_MASK_NONE; a.period = 1;
+  if (reduce) { a.dbias = scratch; a.ob = (int64_t)H * L * L; a.oh = (int64_t)L * L; a.oi = L; }
+  else { a.dbias = dbias; a.ob = sb; a.oh = sh; a.oi = si; }
+  fill_common(a, L, H, hd, 1.0f, drop_p, drop_key);
+  const bool mfma = dtype == AFFT_BF16 && use_mfma_attention() && hd % 64 == 0 && lddo % 8 == 0 && ldv % 8 == 0 && al16(dout) && al16(v);
+  if (dtype == AFFT_F32) LONG_LAUNCH((bias_bwd_ds_kernel<float, false>));
+  else if (mfma) LONG_LAUNCH((bias_bwd_ds_kernel<bf16_t, true>));
+  else LONG_LAUNCH((bias_bwd_ds_kernel<bf16_t, false>));
+  if (reduce) {
+    const int64_t rows = (int64_t)(sb ? nseq : 1) * (sh ? H : 1) * (si ? L : 1);
+    hipLaunchKernelGGL(bias_bwd_reduce_kernel, dim3((unsigned)rows, (unsigned)((L + 63) / 64)), dim3(256), 0, stream, scratch, dbias,
+                       nseq, H, L, (int)(sb == 0), (int)(sh == 0), (int)(si == 0), sb, sh, si);
+  }
   AFFT_LAUNCH_CHECK();
   return 0;
 }

@@ -552,10 +552,25 @@ def mask_table(mask) -> Optional[Tensor]:
     return mask[1] if isinstance(mask, tuple) and mask[0] == "table" else None
 
 
+def mask_bias(mask) -> Optional[Tensor]:
+    """('bias', fp32 device tensor of 2..4 dimensions that broadcasts to (nseq, H, L, L)): an additive mask over batch and / or heads, or one
+    that takes a gradient -- the attention core runs call by call on afft_attention_fwd_bias / afft_attention_long_fwd_bias with the strides
+    `expand` gives (nothing is materialised); the sub-layer Functions take the tensor as an argument of its own so that autograd can
+    return its gradient (afft_attention_bias_bwd)"""
+    return mask[1] if isinstance(mask, tuple) and mask[0] == "bias" else None
+
+
+def _mask_is_tensor(mask) -> bool:
+    return isinstance(mask, tuple) and mask[0] in ("table", "bias")
+
+
 ATTN_SHORT_MAX = 128      # the longest sequence of afft_attention_fwd / _bwd and of the composite sub-layer entry points
 
 
-def _attention_fwd(q, k, v, nseq, L, H, hd, scale, mask, out, probs, drop):
+def _attention_fwd(q, k, v, nseq, L, H, hd, scale, mask, out, probs, drop, bias=None):
+    if bias is not None:
+        fn = ops.attention_long_fwd_bias if L > ATTN_SHORT_MAX else ops.attention_fwd_bias
+        return fn(q, k, v, nseq, L, H, hd, scale, bias, out, probs, *(_attn_drop(drop)))
     tab = mask_table(mask)
     if L > ATTN_SHORT_MAX:
         mk, per = _mask_args(mask) if tab is None else (MASK_NONE, 0)
@@ -570,6 +585,21 @@ def _attention_bwd(dout, q, k, v, probs, nseq, L, H, hd, scale, dq, dk, dv, drop
     """sequences above ATTN_SHORT_MAX tokens have kernels of their own (csrc/attention_long.hip), tiled over rows"""
     fn = ops.attention_long_bwd if L > ATTN_SHORT_MAX else ops.attention_bwd
     return fn(dout, q, k, v, probs, nseq, L, H, hd, scale, dq, dk, dv, *(_attn_drop(drop)))
+
+
+def _attention_bias_bwd(bias, dout, v, probs, nseq, L, H, hd, drop):
+    """the gradient of an additive attention bias, in the bias's own shape: into the gradient sink for a leaf (the way AddRowTable's table
+    gets its gradient), else returned to autograd"""
+    if rt.grad_mode() == "sink" and bias.is_leaf:
+        g, acc = rt.SINK.grad_buffer(bias)
+        if acc:      # the same mask in several sub-layers (DecoderBlock: self- and cross-attention): the kernel overwrites, later uses add
+            g.add_(ops.attention_bias_bwd(dout, v, probs, nseq, L, H, hd, torch.empty_like(g), *(_attn_drop(drop))))
+        else:
+            ops.attention_bias_bwd(dout, v, probs, nseq, L, H, hd, g, *(_attn_drop(drop)))
+        _ready(bias)
+        return None
+    return ops.attention_bias_bwd(dout, v, probs, nseq, L, H, hd, torch.empty(bias.shape, dtype=torch.float32, device=bias.device),
+                                  *(_attn_drop(drop)))
 
 
 # --------------------------------------------------------------------------- composite path: one C-ABI call per sub-layer
@@ -992,10 +1022,11 @@ class AttnSublayer(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, L, H, mask, eps, conv1d, pre_ln=True, scale=None,
-                drop=None, probs_out=None, take=0):
+                drop=None, probs_out=None, take=0, bias=None):
         """probs_out: fp32 [nseq, H, L, L] to write the attention maps into (the caller's slice of ONE buffer for all its blocks:
         the SA-Fuser returns the stacked maps, models/fusion.py:144 -- no torch.stack copy of every block's maps per forward)
-        take = L: y is [nseq, d], token 0 of every sequence (attn_take_ok says whether this call can do that)"""
+        take = L: y is [nseq, d], token 0 of every sequence (attn_take_ok says whether this call can do that)
+        bias: the tensor of mask = ('bias', tensor), as an argument of its own so that it can take a gradient"""
         R, d = x.shape
         assert take in (0, L) and (not take or attn_take_ok(x, L, H, pre_ln)), "AttnSublayer: take needs the composite path (attn_take_ok)"
         nseq, hd = R // L, d // H
@@ -1007,7 +1038,9 @@ class AttnSublayer(torch.autograd.Function):
         # freshly ZERO-FILLED tensor of its shape for it on every call (a fill kernel per attention sub-layer and step)
         ctx.set_materialize_grads(False)
         # fp16x2: the attention core on hi + lo planes exists on the MFMA path only (L <= 64, head dimension a multiple of 64)
-        if mask_table(mask) is None and L <= ATTN_SHORT_MAX and _composite_ok(x, pre_ln, d) and (rt.precision() != "fp16x2" or (L <= 64 and hd % 64 == 0 and hd <= 1024)):
+        if bias is None:
+            bias = mask_bias(mask)
+        if not _mask_is_tensor(mask) and L <= ATTN_SHORT_MAX and _composite_ok(x, pre_ln, d) and (rt.precision() != "fp16x2" or (L <= 64 and hd % 64 == 0 and hd <= 1024)):
             return _attn_fwd_c(ctx, x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, L, H, mask, eps, conv1d, scale, drop, probs_out, take)
         ctx.up = _upstream_of(x) if pre_ln else None
         mean, rstd = _stats(R if pre_ln else 0, dev)
@@ -1021,7 +1054,8 @@ class AttnSublayer(torch.autograd.Function):
         ao = Act(R, d, dev)
         probs = probs_out if probs_out is not None else torch.empty(nseq, H, L, L, dtype=torch.float32, device=dev)
         scale = float(scale) if scale else float(hd) ** -0.5
-        _attention_fwd(qkv.cols(0, d), qkv.cols(d, 2 * d), qkv.cols(2 * d, 3 * d), nseq, L, H, hd, scale, mask, ao.live, probs, drop)
+        _attention_fwd(qkv.cols(0, d), qkv.cols(d, 2 * d), qkv.cols(2 * d, 3 * d), nseq, L, H, hd, scale, mask, ao.live, probs, drop, bias)
+        ctx.attn_bias = bias if len(ctx.needs_input_grad) > 17 and ctx.needs_input_grad[17] else None
         y = torch.empty(R, d, dtype=torch.float32, device=dev)
         _lin_fwd(ao, w_proj, conv1d, y, bias=b_proj, residual=x if pre_ln else None, drop=_out_drop(drop))
         ctx.save_for_backward(x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, mean, rstd, probs)
@@ -1037,9 +1071,9 @@ class AttnSublayer(torch.autograd.Function):
         if dy is None:          # (set_materialize_grads(False)) nobody used y
             _drop_shadow()      # a hand-over meant for this backward and queued notifications must not outlive it
             flush_ready()
-            return (None,) * 17
+            return (None,) * 18
         if ctx.composite:
-            return _attn_bwd_c(ctx, dy) + (None,)
+            return _attn_bwd_c(ctx, dy) + (None, None)
         x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, mean, rstd, probs = ctx.saved_tensors
         xn, qkv, ao = (_b16(t) for t in ctx.acts)
         L, H, scale, conv1d, pre_ln, drop = ctx.cfg
@@ -1058,6 +1092,9 @@ class AttnSublayer(torch.autograd.Function):
         dqkv = Act(R, 3 * d, dev)
         _attention_bwd(dao.live, qkv.cols(0, d), qkv.cols(d, 2 * d), qkv.cols(2 * d, 3 * d), probs, nseq, L, H, hd,
                        scale, dqkv.cols(0, d), dqkv.cols(d, 2 * d), dqkv.cols(2 * d, 3 * d), drop)
+        g_bias = None
+        if ctx.attn_bias is not None:
+            g_bias = _attention_bias_bwd(ctx.attn_bias, dao.live, qkv.cols(2 * d, 3 * d), probs, nseq, L, H, hd, drop)
         with _Side(dev):
             g_wq = _wgrad(dqkv, xn, w_qkv, conv1d)
             g_bq = _bgrad(dqkv.live, b_qkv)
@@ -1072,7 +1109,7 @@ class AttnSublayer(torch.autograd.Function):
         join_side(dev)
         ctx.acts = None
         flush_ready()
-        return dx, g_lw, g_lb, g_wq, g_bq, g_wp, g_bp, None, None, None, None, None, None, None, None, None
+        return dx, g_lw, g_lb, g_wq, g_bq, g_wp, g_bp, None, None, None, None, None, None, None, None, None, None, g_bias
 
 
 # --------------------------------------------------------------------------- pre-LN MLP sub-layer
@@ -1148,7 +1185,7 @@ class CrossAttnSublayer(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, mem, nq_w, nq_b, nkv_w, nkv_b, w_q, w_k, w_v, w_proj, b_proj, L, H, mask, eps, pre_ln=True,
-                scale=None, drop=None, b_q=None, b_k=None, b_v=None):
+                scale=None, drop=None, b_q=None, b_k=None, b_v=None, bias=None):
         """b_q / b_k / b_v: CrossAttention(qkv_bias=True); mem may be narrower or wider than x (mem_dim != dim: w_k, w_v are [d, mem_dim]) --
         both off the AFFT configurations (models/transformerblock.py:41-50) and served call by call."""
         R, d = x.shape
@@ -1157,7 +1194,9 @@ class CrossAttnSublayer(torch.autograd.Function):
         dev = x.device
         ctx.composite = False
         ctx.qkv_bias = b_q is not None or b_k is not None or b_v is not None
-        if (mask_table(mask) is None and L <= ATTN_SHORT_MAX and not ctx.qkv_bias and dm == d and _composite_ok(x, pre_ln, d, f16x2=False)
+        if bias is None:
+            bias = mask_bias(mask)
+        if (not _mask_is_tensor(mask) and L <= ATTN_SHORT_MAX and not ctx.qkv_bias and dm == d and _composite_ok(x, pre_ln, d, f16x2=False)
                 and mem.stride(0) == d):
             return _cross_fwd_c(ctx, x, mem, nq_w, nq_b, nkv_w, nkv_b, w_q, w_k, w_v, w_proj, b_proj, L, H, mask, eps, scale,
                                 drop)
@@ -1177,7 +1216,8 @@ class CrossAttnSublayer(torch.autograd.Function):
         ao = Act(R, d, dev)
         probs = torch.empty(nseq, H, L, L, dtype=torch.float32, device=dev)
         scale = float(scale) if scale else float(hd) ** -0.5
-        _attention_fwd(q.live, k.live, v.live, nseq, L, H, hd, scale, mask, ao.live, probs, drop)
+        _attention_fwd(q.live, k.live, v.live, nseq, L, H, hd, scale, mask, ao.live, probs, drop, bias)
+        ctx.attn_bias = bias if len(ctx.needs_input_grad) > 21 and ctx.needs_input_grad[21] else None
         y = torch.empty(R, d, dtype=torch.float32, device=dev)
         _lin_fwd(ao, w_proj, False, y, bias=b_proj, residual=x if pre_ln else None, drop=_out_drop(drop))
         ctx.save_for_backward(x, mem, nq_w, nq_b, nkv_w, nkv_b, w_q, w_k, w_v, w_proj, b_proj, mq, rq, mk, rk, probs)
@@ -1191,7 +1231,7 @@ class CrossAttnSublayer(torch.autograd.Function):
     @_in_backward_precision
     def backward(ctx, dy):
         if ctx.composite:
-            return _cross_bwd_c(ctx, dy)
+            return _cross_bwd_c(ctx, dy) + (None,)
         (x, mem, nq_w, nq_b, nkv_w, nkv_b, w_q, w_k, w_v, w_proj, b_proj, mq, rq, mk, rk, probs) = ctx.saved_tensors
         xq, mkv, q, k, v, ao = (_b16(t) for t in ctx.acts)
         L, H, scale, pre_ln, drop = ctx.cfg
@@ -1209,6 +1249,9 @@ class CrossAttnSublayer(torch.autograd.Function):
         _lin_dgrad(dya, w_proj, False, dao.live)
         dq, dk, dv = Act(R, d, dev), Act(R, d, dev), Act(R, d, dev)
         _attention_bwd(dao.live, q.live, k.live, v.live, probs, nseq, L, H, hd, scale, dq.live, dk.live, dv.live, drop)
+        g_bias = None
+        if ctx.attn_bias is not None:
+            g_bias = _attention_bias_bwd(ctx.attn_bias, dao.live, v.live, probs, nseq, L, H, hd, drop)
         b_q, b_k, b_v = ctx.qkv_b
         with _Side(dev):
             g_q = _wgrad(dq, xq, w_q, False)
@@ -1232,7 +1275,7 @@ class CrossAttnSublayer(torch.autograd.Function):
         join_side(dev)
         ctx.acts = None
         flush_ready()
-        return dx, dmem, g_qw, g_qb, g_kw, g_kb, g_q, g_k, g_v, g_wp, g_bp, None, None, None, None, None, None, None, g_bq, g_bk, g_bv
+        return dx, dmem, g_qw, g_qb, g_kw, g_kb, g_q, g_k, g_v, g_wp, g_bp, None, None, None, None, None, None, None, g_bq, g_bk, g_bv, g_bias
 
 
 # --------------------------------------------------------------------------- plain linear (mapping, enc/dec, classifier)

@@ -10,6 +10,7 @@ parameter names and return values; the arithmetic runs in the HIP kernels (afft_
 """
 from __future__ import annotations
 
+import weakref
 from typing import Optional, Union
 
 import torch
@@ -22,26 +23,12 @@ Tensor = torch.Tensor
 MaskArg = Union[None, str, Tensor]
 
 
-def mask_kind(attn_mask: MaskArg, n: int):
-    """The HIP attention kernels apply their mask in-register from a kind: 'none' | 'diag' | 'causal' |
-    ('blockcausal', T).  The reference passes additive -inf tensors (models/fusion.py:30-32,170-171,313-317);
-    recognise those.  Any other (N, N) tensor -- the reference adds whatever it is given -- becomes ('table', fp32 tensor);
-    masks that broadcast over batch or heads ((B, 1, N, N), ...) are not supported."""
-    if attn_mask is None:
-        return "none"
-    if isinstance(attn_mask, tuple):
-        if len(attn_mask) == 2 and attn_mask[0] == "table":
-            return attn_mask
-        if len(attn_mask) != 2 or attn_mask[0] != "blockcausal" or n % int(attn_mask[1]) != 0:
-            raise ValueError(f"unknown mask kind {attn_mask!r}")
-        return ("blockcausal", int(attn_mask[1]))
-    if isinstance(attn_mask, str):
-        if attn_mask not in ("none", "diag", "causal"):
-            raise ValueError(f"unknown mask kind {attn_mask!r}")
-        return attn_mask
+_KIND_CACHE: dict = {}     # (data_ptr, _version, shape) -> (weak reference to the mask, n, kind): the classification of a 2-D mask
+
+
+def _classify_2d(attn_mask: Tensor, n: int):
+    """today's kinds for an (N, N) mask that takes no gradient: the in-register patterns, else ('table', fp32 tensor)"""
     m = attn_mask.detach().to("cpu", torch.float32)
-    if m.shape != (n, n):
-        raise ValueError(f"attn_mask must be ({n},{n}), got {tuple(m.shape)}")
     if torch.equal(m, torch.zeros(n, n)):
         return "none"
     causal = lambda t: torch.triu(torch.full((t, t), float("-inf")), diagonal=1)   # noqa: E731
@@ -57,6 +44,50 @@ def mask_kind(attn_mask: MaskArg, n: int):
     # anything else: `attn = attn + attn_mask` for an arbitrary (N, N) tensor (models/transformerblock.py:26-28, :66-68) -- the table goes to
     # the generic attention kernel (afft_attention_fwd_table) instead of an in-register mask of the MFMA kernels
     return ("table", attn_mask.detach().to(torch.float32).contiguous())
+
+
+def mask_kind(attn_mask: MaskArg, n: int, nseq: Optional[int] = None, heads: Optional[int] = None):
+    """The HIP attention kernels apply their mask in-register from a kind: 'none' | 'diag' | 'causal' |
+    ('blockcausal', T).  The reference passes additive -inf tensors (models/fusion.py:30-32,170-171,313-317);
+    recognise those.  Any other (N, N) tensor -- the reference adds whatever it is given -- becomes ('table', fp32 tensor).
+    A tensor of 2, 3 or 4 dimensions that broadcasts to (nseq, H, N, N) -- key padding (B, 1, 1, N), a per-head bias (H, N, N), a per-sample
+    mask (B, 1, N, N), the full tensor -- and ANY mask that requires grad, (N, N) included, becomes ('bias', fp32 tensor in its own shape):
+    it is never compared against the patterns and never detached, so its gradient flows back (functional.mask_bias).
+    nseq, heads: the batch size and head count the leading dimensions are checked against (None: checked at the launch, ops.bias_strides)."""
+    if attn_mask is None:
+        return "none"
+    if isinstance(attn_mask, tuple):
+        if len(attn_mask) == 2 and attn_mask[0] in ("table", "bias"):
+            return attn_mask
+        if len(attn_mask) != 2 or attn_mask[0] != "blockcausal" or n % int(attn_mask[1]) != 0:
+            raise ValueError(f"unknown mask kind {attn_mask!r}")
+        return ("blockcausal", int(attn_mask[1]))
+    if isinstance(attn_mask, str):
+        if attn_mask not in ("none", "diag", "causal"):
+            raise ValueError(f"unknown mask kind {attn_mask!r}")
+        return attn_mask
+    shp = tuple(attn_mask.shape)
+    s4 = (1,) * (4 - len(shp)) + shp if 2 <= len(shp) <= 4 else None
+    if (s4 is None or s4[3] != n or s4[2] not in (1, n) or (nseq is not None and s4[0] not in (1, nseq))
+            or (heads is not None and s4[1] not in (1, heads))):
+        want = f"({'B' if nseq is None else nseq}|1, {'H' if heads is None else heads}|1, {n}|1, {n})"
+        raise ValueError(f"attn_mask must be ({n},{n}) or broadcast to (B, H, N, N) as {want} with 2 to 4 dimensions, got {shp}")
+    if shp == (n, n) and not attn_mask.requires_grad:
+        # the host-side pattern probes run once per (storage, version, shape), not on every forward; the entry also has to be this
+        # very tensor (a freed mask's address can come back under another mask with the same version and shape)
+        key = (attn_mask.data_ptr(), attn_mask._version, shp)
+        hit = _KIND_CACHE.get(key)
+        if hit is not None and hit[0]() is attn_mask and hit[1] == n:
+            return hit[2]
+        kind = _classify_2d(attn_mask, n)
+        if len(_KIND_CACHE) >= 64:
+            _KIND_CACHE.clear()
+        _KIND_CACHE[key] = (weakref.ref(attn_mask), n, kind)
+        return kind
+    b = attn_mask if attn_mask.dtype == torch.float32 else attn_mask.to(torch.float32)
+    if n > 1 and b.stride(-1) != 1:
+        b = b.contiguous()
+    return ("bias", b)
 
 
 def _flat(x: Tensor):
@@ -83,9 +114,10 @@ class Attention(nn.Module):
 
     def forward(self, x, attn_mask: MaskArg = None):
         x2, B, N, C = _flat(x)
+        mask = mask_kind(attn_mask, N, B, self.num_heads)
         y, probs = F_.AttnSublayer.apply(x2, None, None, self.qkv.weight, self.qkv.bias, self.proj.weight,
-                                         self.proj.bias, N, self.num_heads, mask_kind(attn_mask, N), 0.0, False,
-                                         False, self.scale, self.drop_cfg())
+                                         self.proj.bias, N, self.num_heads, mask, 0.0, False,
+                                         False, self.scale, self.drop_cfg(), None, 0, F_.mask_bias(mask))
         return y.view(B, N, C), probs
 
 
@@ -111,10 +143,11 @@ class CrossAttention(nn.Module):
     def forward(self, x, mem, attn_mask: MaskArg = None):
         x2, B, N, C = _flat(x)
         m2, _, _, _ = _flat(mem)
+        mask = mask_kind(attn_mask, N, B, self.num_heads)
         y = F_.CrossAttnSublayer.apply(x2, m2, None, None, None, None, self.w_q.weight, self.w_k.weight,
                                        self.w_v.weight, self.proj.weight, self.proj.bias, N, self.num_heads,
-                                       mask_kind(attn_mask, N), 0.0, False, self.scale, self.drop_cfg(),
-                                       self.w_q.bias, self.w_k.bias, self.w_v.bias)
+                                       mask, 0.0, False, self.scale, self.drop_cfg(),
+                                       self.w_q.bias, self.w_k.bias, self.w_v.bias, F_.mask_bias(mask))
         return y.view(B, N, C)
 
 
@@ -183,7 +216,7 @@ class Block(nn.Module):
         dp = _dp_rate(self.drop_path)
         x2, probs = F_.AttnSublayer.apply(x2, self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias,
                                           a.proj.weight, a.proj.bias, L, a.num_heads, mask, self.norm1.eps, False,
-                                          True, a.scale, D_.with_path(a.drop_cfg(), dp, L), probs_out)
+                                          True, a.scale, D_.with_path(a.drop_cfg(), dp, L), probs_out, 0, F_.mask_bias(mask))
         m = self.mlp.mlp
         x2 = F_.MLPSublayer.apply(x2, self.norm2.weight, self.norm2.bias, m[0].weight, m[0].bias, m[2].weight,
                                   m[2].bias, self.norm2.eps, "erf", False, True,
@@ -209,7 +242,7 @@ class Block(nn.Module):
         else:
             x2, probs = F_.AttnSublayer.apply(x2, self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias,
                                               a.proj.weight, a.proj.bias, L, a.num_heads, mask, self.norm1.eps, False,
-                                              True, a.scale, D_.with_path(a.drop_cfg(), dp, L), probs_out)
+                                              True, a.scale, D_.with_path(a.drop_cfg(), dp, L), probs_out, 0, F_.mask_bias(mask))
             x0 = F_.TakeRows.apply(x2, L)
         m = self.mlp.mlp
         x0 = F_.MLPSublayer.apply(x0, self.norm2.weight, self.norm2.bias, m[0].weight, m[0].bias, m[2].weight,
@@ -219,7 +252,7 @@ class Block(nn.Module):
 
     def forward(self, x, attn_mask: MaskArg = None):
         x2, B, N, C = _flat(x)
-        y, probs = self.forward_rows(x2, N, mask_kind(attn_mask, N))
+        y, probs = self.forward_rows(x2, N, mask_kind(attn_mask, N, B, self.attn.num_heads))
         return y.view(B, N, C), probs
 
 
@@ -246,11 +279,11 @@ class DecoderBlock(nn.Module):
         dp = _dp_rate(self.drop_path)
         x2, _ = F_.AttnSublayer.apply(x2, self.norm_self.weight, self.norm_self.bias, a.qkv.weight, a.qkv.bias,
                                       a.proj.weight, a.proj.bias, L, a.num_heads, mask, self.norm_self.eps, False,
-                                      True, a.scale, D_.with_path(a.drop_cfg(), dp, L))
+                                      True, a.scale, D_.with_path(a.drop_cfg(), dp, L), None, 0, F_.mask_bias(mask))
         x2 = F_.CrossAttnSublayer.apply(x2, m2, self.norm_q.weight, self.norm_q.bias, self.norm_kv.weight,
                                         self.norm_kv.bias, c.w_q.weight, c.w_k.weight, c.w_v.weight, c.proj.weight,
                                         c.proj.bias, L, c.num_heads, mask, self.norm_q.eps, True, c.scale,
-                                        D_.with_path(c.drop_cfg(), dp, L), c.w_q.bias, c.w_k.bias, c.w_v.bias)
+                                        D_.with_path(c.drop_cfg(), dp, L), c.w_q.bias, c.w_k.bias, c.w_v.bias, F_.mask_bias(mask))
         m = self.mlp.mlp
         x2 = F_.MLPSublayer.apply(x2, self.norm_mlp.weight, self.norm_mlp.bias, m[0].weight, m[0].bias, m[2].weight,
                                   m[2].bias, self.norm_mlp.eps, "erf", False, True,
@@ -260,4 +293,4 @@ class DecoderBlock(nn.Module):
     def forward(self, x, mem, attn_mask: MaskArg = None):
         x2, B, N, C = _flat(x)
         m2, _, _, _ = _flat(mem)
-        return self.forward_rows(x2, m2, N, mask_kind(attn_mask, N)).view(B, N, C)
+        return self.forward_rows(x2, m2, N, mask_kind(attn_mask, N, B, self.attn.num_heads)).view(B, N, C)

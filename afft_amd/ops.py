@@ -315,6 +315,62 @@ def attention_long_bwd(dout: Tensor, q: Tensor, k: Tensor, v: Tensor, probs: Ten
             "attention_long_bwd")
 
 
+def bias_strides(bias: Tensor, nseq: int, L_: int, H: int):
+    """element strides (sb, sh, si) of an additive attention bias of 2, 3 or 4 dimensions read as (nseq, H, L, L): what `expand` gives, so a
+    broadcast dimension has stride 0 and nothing is materialised.  Leading dimensions are 1 or the full size, the row dimension 1 or L,
+    the last dimension L with unit stride."""
+    shp = tuple(bias.shape)
+    full = (nseq, H, L_, L_)
+    s4 = (1,) * (4 - len(shp)) + shp if 2 <= len(shp) <= 4 else None
+    if s4 is None or s4[3] != L_ or any(a not in (1, f) for a, f in zip(s4[:3], full[:3])):
+        raise ValueError(f"afft_amd: attention bias must broadcast to {full} with a last dimension of {L_}, got {shp}")
+    if bias.dtype != torch.float32:
+        raise TypeError(f"afft_amd: attention bias must be float32, got {bias.dtype}")
+    if L_ > 1 and bias.stride(-1) != 1:
+        raise ValueError(f"afft_amd: attention bias must have unit stride in its last dimension, got strides {bias.stride()}")
+    st = bias.detach()[(None,) * (4 - len(shp))].expand(full).stride()
+    return int(st[0]), int(st[1]), int(st[2])
+
+
+def attention_fwd_bias(q: Tensor, k: Tensor, v: Tensor, nseq: int, L_: int, H: int, hd: int, scale: float, bias: Tensor,
+                       out: Tensor, probs: Optional[Tensor], drop_p: float = 0.0, drop_key: int = 0) -> Tensor:
+    """attention over <= 128 tokens with an additive fp32 bias that broadcasts to (nseq, H, L, L) (afft_attention_fwd_bias)"""
+    assert q.dtype == k.dtype == v.dtype == out.dtype
+    assert bias.device == q.device
+    sb, sh, si = bias_strides(bias, nseq, L_, H)
+    L.check(L.lib().afft_attention_fwd_bias(_p(q), _rowmajor(q, "q"), _p(k), _rowmajor(k, "k"), _p(v), _rowmajor(v, "v"),
+                                            _dt(q), nseq, L_, H, hd, scale, _p(bias), sb, sh, si, drop_p, drop_key, _p(out),
+                                            _rowmajor(out, "out"), _p(probs), _stream()), "attention_fwd_bias")
+    return out
+
+
+def attention_long_fwd_bias(q: Tensor, k: Tensor, v: Tensor, nseq: int, L_: int, H: int, hd: int, scale: float, bias: Tensor,
+                            out: Tensor, probs: Optional[Tensor], drop_p: float = 0.0, drop_key: int = 0) -> Tensor:
+    """the same over 129..512 tokens (afft_attention_long_fwd_bias)"""
+    assert q.dtype == k.dtype == v.dtype == out.dtype
+    assert bias.device == q.device
+    sb, sh, si = bias_strides(bias, nseq, L_, H)
+    L.check(L.lib().afft_attention_long_fwd_bias(_p(q), _rowmajor(q, "q"), _p(k), _rowmajor(k, "k"), _p(v), _rowmajor(v, "v"),
+                                                 _dt(q), nseq, L_, H, hd, scale, _p(bias), sb, sh, si, drop_p, drop_key, _p(out),
+                                                 _rowmajor(out, "out"), _p(probs), _stream()), "attention_long_fwd_bias")
+    return out
+
+
+def attention_bias_bwd(dout: Tensor, v: Tensor, probs: Tensor, nseq: int, L_: int, H: int, hd: int, dbias: Tensor,
+                       drop_p: float = 0.0, drop_key: int = 0) -> Tensor:
+    """dbias (fp32, the bias's own shape, overwritten) = dS = P (dP - sum_j P dP) summed over the dimensions the bias broadcasts
+    (afft_attention_bias_bwd); probs: the saved pre-dropout probabilities [nseq, H, L, L]; 1 <= L <= 512"""
+    assert dout.dtype == v.dtype
+    assert probs.dtype == torch.float32 and probs.shape == (nseq, H, L_, L_) and probs.is_contiguous()
+    assert dbias.device == probs.device == dout.device
+    sb, sh, si = bias_strides(dbias, nseq, L_, H)
+    # the per-(sequence, head) dS that the ordered sum reads (afft_attention_bias_bwd: scratch); from torch's allocator, like every buffer of the path
+    scratch = torch.empty(max(nseq * H * L_ * L_, 1), dtype=torch.float32, device=dout.device) if 0 in (sb, sh, si) else None
+    L.check(L.lib().afft_attention_bias_bwd(_p(dout), _rowmajor(dout, "dout"), _p(v), _rowmajor(v, "v"), _dt(v), _p(probs), nseq, L_, H,
+                                            hd, drop_p, drop_key, _p(dbias), sb, sh, si, _p(scratch), _stream()), "attention_bias_bwd")
+    return dbias
+
+
 def softmax_ce(logits: Tensor, C_: int, *, labels: Optional[Tensor] = None, soft: Optional[Tensor] = None,
                keep: Optional[Tensor] = None, gscale: float = 1.0, row_g: Optional[Tensor] = None,
                loss_sum: Optional[Tensor] = None, dlogits: Optional[Tensor] = None,

@@ -278,6 +278,33 @@ int afft_attention_long_bwd(const void* dout, int64_t lddo, const void* q, int64
                             int32_t H, int32_t hd, float scale, float drop_p, uint32_t drop_key, void* dq, int64_t lddq,
                             void* dk, int64_t lddk, void* dv, int64_t lddv, float* row_term, void* stream);
 
+/* ------------------------------------------------------------------ additive attention bias that broadcasts over batch and heads
+ * `attn = attn + attn_mask` for any tensor that broadcasts against the (nseq, H, L, L) scores (models/transformerblock.py:26-28, :66-68):
+ * a key-padding mask (nseq, 1, 1, L), a per-head bias (1, H, L, L), a per-sample mask (nseq, 1, L, L), the full tensor.
+ * bias: fp32, 4-byte aligned; element (b, h, i, j) is read at bias[b*sb + h*sh + i*si + j].  sb, sh, si are ELEMENT strides, each >= 0;
+ * 0 means that the dimension is broadcast; the last dimension is contiguous; entries may be -inf (never a whole row).
+ * Everything else as afft_attention_fwd_table (L <= 128, generic kernel) / afft_attention_long_fwd without an in-register mask
+ * (129 <= L <= 512); sb = sh = 0, si = L gives bitwise the results of the table entry points.  dq / dk / dv come from
+ * afft_attention_bwd / afft_attention_long_bwd as before (they work from the saved probabilities). */
+int afft_attention_fwd_bias(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                            int32_t dtype, int32_t nseq, int32_t L, int32_t H, int32_t hd, float scale,
+                            const float* bias, int64_t sb, int64_t sh, int64_t si, float drop_p, uint32_t drop_key,
+                            void* out, int64_t ldo, float* probs, void* stream);
+int afft_attention_long_fwd_bias(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                                 int32_t dtype, int32_t nseq, int32_t L, int32_t H, int32_t hd, float scale,
+                                 const float* bias, int64_t sb, int64_t sh, int64_t si, float drop_p, uint32_t drop_key,
+                                 void* out, int64_t ldo, float* probs, void* stream);
+/* The gradient of that bias, 1 <= L <= 512: per (b, h) dP = dO V^T (dropout mask and 1/(1-p) regenerated from drop_key as the backward
+ * entry points do), r_i = sum_j P_ij dP_ij, dS_ij = P_ij (dP_ij - r_i) -- no `scale`: the bias is added after the scaling -- summed
+ * over every dimension whose stride is 0 and written, fp32, at dbias[b*sb + h*sh + i*si + j] (the bias's own layout).
+ * probs: the saved PRE-dropout probabilities fp32 [nseq, H, L, L]; dout, v: dtype and strides as afft_attention_bwd.
+ * Two stages, no atomics, sums in a fixed order (bitwise reproducible): dS per (b, h) -- straight into dbias when no stride is 0 --,
+ * then an ordered sum over the broadcast dimensions.  scratch: fp32 [nseq * H * L * L] of the caller when any of sb, sh, si is 0
+ * (the library never allocates), else unused (may be NULL). */
+int afft_attention_bias_bwd(const void* dout, int64_t lddo, const void* v, int64_t ldv, int32_t dtype, const float* probs,
+                            int32_t nseq, int32_t L, int32_t H, int32_t hd, float drop_p, uint32_t drop_key, float* dbias,
+                            int64_t sb, int64_t sh, int64_t si, float* scratch, void* stream);
+
 /* afft_layernorm_bwd whose incoming residual gradient dx_in is [rows / in_take, d] (row pitch lddx_in) and belongs to rows 0, in_take,
  * 2 in_take, ..: the other rows take no residual gradient (afft_attn_sublayer_t.take; in_take = 1: every row). */
 int afft_layernorm_bwd_take(const void* dy, int64_t lddy, int32_t dy_dtype, const float* x, int64_t ldx, const float* w, const float* mean,
