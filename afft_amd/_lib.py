@@ -146,6 +146,7 @@ _SIGS = {
     "afft_gemm_splitk_for": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int], C.c_int),
     "afft_gemm_trace_begin": ([i32], C.c_int),
     "afft_gemm_trace_end": ([C.POINTER(GemmTraceRec), i32], C.c_int),
+    "afft_gemm_plan_for": ([C.POINTER(GemmDesc), C.POINTER(GemmTraceRec)], C.c_int),
     "afft_kernel_trace_begin": ([i32], C.c_int),
     "afft_kernel_trace_end": ([C.POINTER(KernelTraceRec), i32], C.c_int),
     "afft_gemm_workspace_bytes": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int], i64),

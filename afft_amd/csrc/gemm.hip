@@ -18,8 +18,8 @@
 //    X3 instantiations (afft_gemm_t.split3, "bf16x3"): A and B are two-plane hi / lo splits of fp32 matrices; the K loop runs
 //    three segments (hi*hi, lo*hi, hi*lo) with the operand planes chosen per K-step on the SALU -- fp32-grade products.
 //    Every epilogue can end in the fused optimizer update instead of a store (afft_sgd_fused_t, common.h: SgdEpi).
-//    Dispatch (choose_variant / choose_splitk): 256x256 ping-pong tiles (gemm_pp.hip) when the utilisation of their last
-//    round beats that of the 128x128 grid (x1.25); split-K into caller-provided scratch (afft_gemm_t.workspace).
+//    Dispatch (gemm_plan.h: plan_gemm, the one place that decides): 256x256 ping-pong tiles (gemm_pp.hip) when the utilisation of
+//    their last round beats that of the 128x128 grid (x1.25); split-K into caller-provided scratch (afft_gemm_t.workspace).
 //  * gemm_f32_kernel: exact fp32 (v_mfma_f32_32x32x2_f32), any strides / sizes; the parity mode
 //    and the fallback for shapes the fast path does not take.
 //
@@ -33,9 +33,8 @@
 
 using namespace afft_gemm_detail;
 
-thread_local int afft_gemm_detail::g_launched_variant = 0;
-
-int afft_gemm_launch_pp(int a_ks, int b_ks, afft_gemm_detail::GemmFast& g, hipStream_t stream, int x3);
+// the launchers of the other translation units run what the plan chose (GemmPlan.kernel / .x3)
+int afft_gemm_launch_pp(int steady, int a_ks, int b_ks, int x3, afft_gemm_detail::GemmFast& g, hipStream_t stream);
 int afft_gemm_launch_bd(int rows160, int packed, afft_gemm_detail::GemmFast& g, hipStream_t stream);
 #ifdef AFFT_EXPERIMENT_Q4      // tools/experiments/gemm_q4.hip (tools/experiments/build_q4.sh): the four-quadrant kernel, variant 11
 int afft_gemm_launch_q4(afft_gemm_detail::GemmFast& g, hipStream_t stream);
@@ -322,13 +321,6 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_g2_kernel(const GemmFast g) 
   }
 }
 
-#ifndef AFFT_G2
-#define AFFT_G2 1      // 0: every 128x128 launch on gemm_bf16_kernel (A/B builds)
-#endif
-bool g2_shape(int M, int N, int K, int splitk) {
-  return AFFT_G2 && M % 128 == 0 && N % 128 == 0 && K % (BK * splitk) == 0 && (K / BK / splitk) % 2 == 0 && K / BK / splitk >= 2;
-}
-
 // ---------------------------------------------------------------------------------------------
 // exact-fp32 path: 64x64x16 tiles, 4 waves (2x2), each wave one 32x32 tile on v_mfma_f32_32x32x2_f32.
 struct GemmF32 {
@@ -404,10 +396,6 @@ int cu_count() {
   return n;
 }
 
-// Split-K workspace: provided by the caller per launch (afft_gemm_t.workspace, private to the stream): AFFT_GEMM_WS_HEADER
-// bytes of arrival counters (zero between launches) followed by the fp32 partial tiles.  Nothing is allocated here.
-constexpr int kMaxSplitTiles = AFFT_GEMM_WS_HEADER / (int)sizeof(int);
-
 // ---- measurement hook: event pairs around fast-path launches while a trace is open (afft_gemm_trace_begin / _end)
 struct TraceRec { afft_gemm_trace_rec_t r; hipEvent_t a, b; };
 std::mutex g_trace_mu;
@@ -416,22 +404,23 @@ size_t g_trace_cap = 0;
 
 int g_variant = 0;  // 0 auto, 1 = 128x128 tile, 2 = 256x128 tile, 3 = 256x256 ping-pong (tuning / tests)
 
+int g_bd_mode = [] { const char* e = getenv("AFFT_BD_MODE"); return e ? atoi(e) : 1; }();   // gemm_plan.h: bd_packed_wins
+
+GemmTuning tuning() { return GemmTuning{g_variant, g_splitk_mode, g_bd_mode, cu_count()}; }
+
+// g2: the plan chose the steady-state kernel (GemmPlan.kernel = 12; 2-stage instantiations with plain bf16 or fp16 operands only)
 template <int WM, int WN, int STAGES, bool A_KS, bool B_KS, bool SPLITK, int X3 = 0>
-int launch_fast(GemmFast& g, hipStream_t stream) {
+int launch_fast(bool g2, GemmFast& g, hipStream_t stream) {
   constexpr int BM = 64 * WM, BN = 64 * WN;
   constexpr size_t ring = (size_t)STAGES * (BM + BN) * BK * 2, epi = (size_t)BM * (BN * 4 + 16);
   constexpr size_t lds = ring > epi ? ring : epi;
   g.tiles_m = (g.e.M + BM - 1) / BM;
   g.tiles_n = (g.e.N + BN - 1) / BN;
   if constexpr (WM == 2 && WN == 2 && STAGES == 2 && (X3 == 0 || X3 == 2)) {
-    const bool fits32 = (A_KS ? (int64_t)(g.K + 8) * g.lda * 2 : (8 * g.lda + g.K) * 2) < (1LL << 32) &&
-                        (B_KS ? (int64_t)(g.K + 8) * g.ldb * 2 : (8 * g.ldb + g.K) * 2) < (1LL << 32);      // the running K offset is a 32-bit VGPR
-    const bool one_segment = X3 == 0 || g.K == g.nk_seg * BK;      // X3 = 2: only the one-pass form (split3 = 4) -- the kernel has no operand planes
-    if (fits32 && one_segment && g2_shape(g.e.M, g.e.N, g.K, g.splitk)) {      // whole tiles, even K-tile count per slice: the steady-state kernel
+    if (g2) {
       auto k2 = gemm_bf16_g2_kernel<A_KS, B_KS, SPLITK, X3 == 2>;
       static std::atomic<uint64_t> attr2_done{0};
       if (int rc = afft_ensure_dynamic_lds(reinterpret_cast<const void*>(k2), lds, &attr2_done)) return rc;
-      g_launched_variant = 12;
       hipLaunchKernelGGL(k2, dim3(g.tiles_m * g.tiles_n, g.splitk), dim3(256), lds, stream, g);
       AFFT_LAUNCH_CHECK();
       return 0;
@@ -440,202 +429,105 @@ int launch_fast(GemmFast& g, hipStream_t stream) {
   auto kern = gemm_bf16_kernel<WM, WN, STAGES, A_KS, B_KS, SPLITK, X3>;
   static std::atomic<uint64_t> attr_done{0};
   if (int rc = afft_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, &attr_done)) return rc;
-  g_launched_variant = STAGES == 4 ? 4 : 1;
   hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n, g.splitk), dim3(64 * WM * WN), lds, stream, g);
   AFFT_LAUNCH_CHECK();
   return 0;
 }
 
-int choose_variant(int M, int N, int K, bool A_KS, bool B_KS);
-bool bd_packed_wins(int M, int N, int K);
-extern int g_bd_mode;
-
-// K-slices afft_gemm will use for a fast-path problem (1 = no split-K)
-int choose_splitk(int variant, int M, int N, int K) {
-  if (!g_splitk_mode) return 1;
-  const int nk = K / BK;
-  if (variant == 3) return 1;     // 256x256 tiles never split K (stream-K was built, measured slower on this power-limited part and removed: profiles/HISTORY.md)
-  // 128x128 tiles (2 workgroups per CU = 512 slots): a grid that leaves slots empty is bound by the LDS fill rate of the CUs
-  // that have a workgroup -- more workgroups pulling is the lever.  Cut K so that tiles x slices approaches 512, keeping at
-  // least 16 K-steps (K = 1024) per slice: <= 128 tiles -> 2 slices (4 when K >= 6144), and -- round 2, measured on the
-  // K = 5120 weight gradients of the d = 1024 and d = 2048 models (profiles/r02_gemm_ek100_shapes.txt: 3072x1024x5120
-  // 70 -> 49 us, 4096x1024x5120 74 -> 54 us, 1024x1024x5120 39 -> 30 us) -- <= 256 tiles with K >= 4096 -> 2 slices,
-  // <= 64 tiles with K >= 4096 -> 4.
-  const int64_t t1 = (int64_t)((M + 127) / 128) * ((N + 127) / 128);
-  int s = 1;
-  if (g_splitk_mode == 1) {
-    if (t1 <= 128 && nk >= 32) s = (nk >= 96 && t1 * 4 <= 512) ? 4 : 2;
-    if (t1 <= 64 && nk >= 64) s = 4;
-    if (t1 > 128 && t1 <= 256 && nk >= 64) s = 2;
+// the 128x128 kernels of this file (GemmPlan.kernel 1, 12, 4) in one operand layout
+template <bool A_KS, bool B_KS>
+int launch_128(const GemmPlan& p, GemmFast& g, hipStream_t stream) {
+  const bool g2 = p.kernel == 12;
+  if (p.x3 == 2) {     // fp16 two-pass / one pass: forward layouts only
+    if constexpr (!A_KS) {
+      if (p.splitk > 1) return launch_fast<2, 2, 2, A_KS, B_KS, true, 2>(g2, g, stream);
+      return launch_fast<2, 2, 2, A_KS, B_KS, false, 2>(g2, g, stream);
+    }
+  } else if (p.x3 == 1) {
+    return launch_fast<2, 2, 2, A_KS, B_KS, false, 1>(false, g, stream);
+  } else if (p.x3 == 0) {
+    if (p.kernel == 4) return launch_fast<2, 2, 4, A_KS, B_KS, false>(false, g, stream);
+    if (p.splitk > 1) return launch_fast<2, 2, 2, A_KS, B_KS, true>(g2, g, stream);
+    return launch_fast<2, 2, 2, A_KS, B_KS, false>(g2, g, stream);
   }
-  else if (t1 * g_splitk_mode <= kMaxSplitTiles && nk >= 2 * g_splitk_mode) s = g_splitk_mode;
-  while (s > 1 && nk % s != 0) s >>= 1;
-  return (s > 1 && t1 <= kMaxSplitTiles) ? s : 1;
+  afft_set_error("afft_gemm: no 128x128 kernel is built for precision mode %d in this layout", p.x3);
+  return 1;
 }
 
-// bytes of partial tiles (without the counter header) split-K needs for this problem; 0 = it does not split
-int64_t splitk_bytes(int variant, int M, int N, int K, int* slices) {
-  const int s = variant >= 4 ? 1 : choose_splitk(variant, M, N, K);
-  if (slices) *slices = s;
-  if (s <= 1) return 0;
-  const int64_t tiles = (int64_t)((M + 127) / 128) * ((N + 127) / 128);
-  return tiles * s * 128 * 128 * (int64_t)sizeof(float);
+// everything afft_gemm decides before it launches: the validated epilogue, the problem and its plan
+struct GemmPrep {
+  enum { kEmpty, kFast, kExact } path;      // nothing to do (M or N = 0) / MFMA fast path / exact-fp32 kernel
+  EpiParams e;
+  GemmProblem p;      // kFast only
+  GemmPlan plan;      // kFast only
+};
+
+// the one launch switch: the plan's kernel -> its launcher
+int launch_plan(const GemmPrep& q, GemmFast& g, hipStream_t stream) {
+  const GemmPlan& p = q.plan;
+  const bool a_ks = q.p.a_ks, b_ks = q.p.b_ks;
+  if (p.kernel == 3 || p.kernel == 13) return afft_gemm_launch_pp(p.kernel == 13, a_ks, b_ks, p.x3, g, stream);
+#ifdef AFFT_EXPERIMENT_Q4
+  if (p.kernel == 11) return afft_gemm_launch_q4(g, stream);
+#endif
+  if (p.kernel >= 7 && p.kernel <= 10) return afft_gemm_launch_bd(p.kernel == 8 || p.kernel == 10, p.kernel >= 9, g, stream);
+  if (!a_ks && !b_ks) return launch_128<false, false>(p, g, stream);
+  if (!a_ks && b_ks) return launch_128<false, true>(p, g, stream);
+  return launch_128<true, true>(p, g, stream);
 }
 
-template <bool A_KS, bool B_KS>
-int launch_layout_impl(GemmFast& g, hipStream_t stream, const afft_gemm_t* d);
+// what the trace hook records of a fast-path launch, and afft_gemm_plan_for reports
+afft_gemm_trace_rec_t trace_rec(const afft_gemm_t* d, const GemmPrep& q) {
+  return afft_gemm_trace_rec_t{d->M, d->N, d->K, q.p.a_ks, q.p.b_ks, q.plan.kernel, q.plan.splitk, d->split3, d->sgd != nullptr, 0.f};
+}
 
-template <bool A_KS, bool B_KS>
-int launch_layout(GemmFast& g, hipStream_t stream, const afft_gemm_t* d) {
-  if (!g_trace) return launch_layout_impl<A_KS, B_KS>(g, stream, d);
+int launch_traced(const GemmPrep& q, GemmFast& g, hipStream_t stream, const afft_gemm_t* d) {
+  if (!g_trace) return launch_plan(q, g, stream);
   TraceRec t = {};
   {
     std::lock_guard<std::mutex> lk(g_trace_mu);
-    if (!g_trace || g_trace->size() >= g_trace_cap) return launch_layout_impl<A_KS, B_KS>(g, stream, d);
+    if (!g_trace || g_trace->size() >= g_trace_cap) return launch_plan(q, g, stream);
   }
-  if (hipEventCreate(&t.a) != hipSuccess || hipEventCreate(&t.b) != hipSuccess) { (void)hipGetLastError(); return launch_layout_impl<A_KS, B_KS>(g, stream, d); }
+  if (hipEventCreate(&t.a) != hipSuccess || hipEventCreate(&t.b) != hipSuccess) { (void)hipGetLastError(); return launch_plan(q, g, stream); }
   (void)hipEventRecord(t.a, stream);
-  g_launched_variant = 0;
-  const int rc = launch_layout_impl<A_KS, B_KS>(g, stream, d);
+  const int rc = launch_plan(q, g, stream);
   (void)hipEventRecord(t.b, stream);
-  t.r = afft_gemm_trace_rec_t{g.e.M, g.e.N, d->K, A_KS, B_KS, g_launched_variant, g.splitk, d->split3, d->sgd != nullptr, 0.f};
+  t.r = trace_rec(d, q);
   std::lock_guard<std::mutex> lk(g_trace_mu);
   if (g_trace) g_trace->push_back(t);
   return rc;
 }
 
-// "B direct" kernel on a fragment-packed weight (afft_gemm_t.b_packed, gemm_bd.hip) against the 256x256 ping-pong kernel: a cost
-// model in us fitted to both kernels alone on one MI355X (profiles/r04_gemm_bd.txt).  Ping-pong: one workgroup per CU, a K-tile
-// of a full round costs ~1.9 us, of a last round with <= 160 busy CUs 1.4 us (the part is power-limited), + 10 us; B-direct
-// 160x256 tiles: 1.09 us per K-tile and round + 8.8 us per round (prologue drain + epilogue, one workgroup per CU and no
-// overlap between tiles).  Taken only when its grid is ONE round (N = 2048 outputs of M = 5120 rows: 256 tiles on 256 CUs where
-// 256-row tiles give 160): inside the model's forward pass the multi-round shapes measured slower than the ping-pong kernel
-// (fc1 with its GELU epilogue 229 vs 201 us: four rounds of epilogues with nothing beside them), the one-round shapes faster
-// (fc2 162 vs 184 us, projection 64 vs 67 us; profiles/r04_gemm_bd.txt "in the step").
-// AFFT_BD_MODE: 0 = never, 1 = by the model (default), 2 = whenever the shape is eligible.
-int g_bd_mode = [] { const char* e = getenv("AFFT_BD_MODE"); return e ? atoi(e) : 1; }();   // declared above
-bool bd_packed_wins(int M, int N, int K) {
-  if (g_bd_mode == 0 || N % 16 != 0 || N < 256 || K % 64 != 0) return false;
-  const int ncu = cu_count(), nk = K / BK;
-  const int64_t t160 = (int64_t)((M + 159) / 160) * ((N + 255) / 256), t256 = (int64_t)((M + 255) / 256) * ((N + 255) / 256);
-  if (t256 < 160) return false;                      // small grids: the 128x128 kernel's territory
-  if (g_bd_mode >= 2) return true;
-  const int64_t r160 = (t160 + ncu - 1) / ncu, r256 = (t256 + ncu - 1) / ncu;
-  if (r160 != 1) return false;
-  const int64_t busy = t256 - (r256 - 1) * ncu;
-  const double last = 1.4 + 0.5 * (double)std::max<int64_t>(0, busy - 160) / 96.0;
-  const double pp_us = nk * ((double)(r256 - 1) * 1.9 + last) + 10.0;
-  const double bd_us = (double)r160 * (nk * 1.09 + 8.8);
-  return bd_us < pp_us;
-}
-
-template <bool A_KS, bool B_KS>
-int launch_layout_impl(GemmFast& g, hipStream_t stream, const afft_gemm_t* d) {
-  if constexpr (!A_KS && !B_KS) {
-    if (d->b_packed && !d->split3 && g_variant == 0 && g.ldb == d->K && bd_packed_wins(g.e.M, g.e.N, g.K)) {
-      g.splitk = 1; g.ws = nullptr; g.counters = nullptr;
-      g.B = (const bf16_t*)d->b_packed;
-      return afft_gemm_launch_bd(1, 1, g, stream);
-    }
-  }
-  const int variant = choose_variant(g.e.M, g.e.N, g.K, A_KS, B_KS);
-  g.splitk = 1;
-  g.ws = nullptr;
-  g.counters = nullptr;
-  if (d->split3 == 3) {     // fp16 hi pass + fp8 lo pass: NT on the 256x256 kernel (callers ask afft_gemm_lo8_ok first)
-    if constexpr (!A_KS && !B_KS) {
-      if (variant == 3) return afft_gemm_launch_pp(A_KS, B_KS, g, stream, 3);
-    }
-    afft_set_error("afft_gemm: split3 = 3 needs the NT layout and a problem the 256x256 kernel takes (afft_gemm_lo8_ok)");
-    return 1;
-  }
-  if (d->split3 == 2 || d->split3 == 4) {     // fp16 two-pass / one pass (g.K = one segment) (forward layouts only): same tile choice as bf16x3
-    if constexpr (!A_KS) {
-      if (variant == 3) return afft_gemm_launch_pp(A_KS, B_KS, g, stream, 2);
-      // small grids (the predictor's M = B*T rows): split-K over the 2K-long loop -- with two slices one workgroup runs the hi
-      // pass of a tile and another its lo pass, and the last to arrive adds them (slice order: bitwise repeatable)
-      int s2 = 1;
-      const int64_t need2 = splitk_bytes(variant, g.e.M, g.e.N, g.K, &s2);
-      if (s2 > 1 && d->workspace && d->workspace_bytes >= need2 + AFFT_GEMM_WS_HEADER) {
-        g.counters = (int*)d->workspace;
-        g.ws = (float*)((char*)d->workspace + AFFT_GEMM_WS_HEADER);
-        g.splitk = s2;
-        return launch_fast<2, 2, 2, A_KS, B_KS, true, 2>(g, stream);
-      }
-      return launch_fast<2, 2, 2, A_KS, B_KS, false, 2>(g, stream);
-    } else {
-      afft_set_error("afft_gemm: the fp16 two-pass mode (split3 = 2) is built for the forward layouts only (A k-contiguous)");
-      return 1;
-    }
-  }
-  if (d->split3) {     // bf16x3: 256x256 tiles once the grid fills the chip, else 128x128; no split-K
-    if (variant == 3) return afft_gemm_launch_pp(A_KS, B_KS, g, stream, 1);
-    return launch_fast<2, 2, 2, A_KS, B_KS, false, 1>(g, stream);
-  }
-  int s = 1;
-  const int64_t need = splitk_bytes(variant, g.e.M, g.e.N, g.K, &s);
-  if (s > 1 && d->workspace && d->workspace_bytes >= need + AFFT_GEMM_WS_HEADER) {   // else: run unsplit
-    g.counters = (int*)d->workspace;
-    g.ws = (float*)((char*)d->workspace + AFFT_GEMM_WS_HEADER);
-    g.splitk = s;
-  }
-  if (variant == 3) return afft_gemm_launch_pp(A_KS, B_KS, g, stream, 0);
-#ifdef AFFT_EXPERIMENT_Q4
-  if (variant == 11) { g.splitk = 1; g.ws = nullptr; g.counters = nullptr; return afft_gemm_launch_q4(g, stream); }
-#endif
-  if (variant >= 7 && variant <= 10) return afft_gemm_launch_bd(variant == 8 || variant == 10, variant >= 9, g, stream);
-  if (variant == 4) return launch_fast<2, 2, 4, A_KS, B_KS, false>(g, stream);
-  if (g.splitk > 1) return launch_fast<2, 2, 2, A_KS, B_KS, true>(g, stream);
-  return launch_fast<2, 2, 2, A_KS, B_KS, false>(g, stream);
-}
-
-// B-direct kernels (gemm_bd.hip): k-contiguous operands only, whole 16-column blocks
-bool bd_ok(int N, bool A_KS, bool B_KS) { return !A_KS && !B_KS && N >= 16 && N % 16 == 0; }
-
-int choose_variant(int M, int N, int K, bool A_KS, bool B_KS) {
-  if (g_variant >= 7 && g_variant <= 10) { if (bd_ok(N, A_KS, B_KS)) return g_variant; }
-#ifdef AFFT_EXPERIMENT_Q4
-  else if (g_variant == 11) { if (!A_KS && !B_KS) return 11; }      // four-quadrant kernel: k-contiguous operands only
-#endif
-  else if (g_variant != 0) return g_variant;
-  // measured (profiles/r01_gemm_variants_bench2.txt): the 256x256 ping-pong kernel (1 workgroup/CU) wins once its
-  // grid covers >= ~60 % of the CUs; below that (GPT-2's M = 1024 GEMMs, small weight gradients) two independent
-  // 128x128 workgroups per CU win.  The 256x128 3-stage shape (variant 2) never wins and is kept for reference.
-  const int64_t t3 = (int64_t)((M + 255) / 256) * ((N + 255) / 256);
-  if (t3 < 160) return 1;
-  // Both shapes waste the slots of their last, partial round (256 slots of one 256x256 tile, 512 of two 128x128 tiles per
-  // CU); per FLOP the big tile is ~1.25x as efficient.  Round 2 (profiles/r02_gemm_ek100_shapes.txt): 5120x4096x1024 is 320
-  // big tiles = 1.25 rounds (57 us on 128x128 tiles, 66 us on 256x256), 5120x3072x1024 is 240 = one nearly full round (45
-  // vs 38 us); 5120x2048x2048 (160 big tiles) 60 vs 55 us.
-  const int64_t t1 = (int64_t)((M + 127) / 128) * ((N + 127) / 128);
-  const int ncu = cu_count();
-  const double u3 = (double)t3 / ((double)ncu * ((t3 + ncu - 1) / ncu)), u1 = (double)t1 / (2.0 * ncu * ((t1 + 2 * ncu - 1) / (2 * ncu)));
-  return u3 * 1.25 >= u1 ? 3 : 1;
+// the plan of a row-major problem as the shape queries describe it: unpadded operands, ample workspace, no packed B unless asked for
+GemmPlan plan_of_shape(int M, int N, int K, bool a_ks, bool b_ks, int split3 = 0, bool b_packed = false) {
+  const GemmProblem p = {M, N, K, a_ks, b_ks, a_ks ? M : K, b_ks ? N : K, K / 2, K / 2, 0, 0, split3, b_packed, INT64_MAX};
+  return plan_gemm(p, tuning());
 }
 
 }  // namespace
 
+// The shape queries: each asks the plan of the row-major problem its arguments describe (plan_of_shape).
 extern "C" int afft_gemm_variant_for(int M, int N, int K, int a_kstrided, int b_kstrided) {
-  return choose_variant(M, N, K, a_kstrided != 0, b_kstrided != 0);
+  const int k = plan_of_shape(M, N, K, a_kstrided != 0, b_kstrided != 0).kernel;
+  return k == 12 ? 1 : k == 13 ? 3 : k;      // the tile shape, whichever kernel of that shape runs
 }
 
 extern "C" int afft_gemm_lo8_ok(int M, int N, int K) {
-  return (g_variant == 0 || g_variant == 3) && K % 128 == 0 && K >= 128 && choose_variant(M, N, 2 * K, false, false) == 3 ? 1 : 0;
+  return (g_variant == 0 || g_variant == 3) && K % 128 == 0 && K >= 128 && !plan_of_shape(M, N, K, false, false, 3).refusal ? 1 : 0;
 }
 
 extern "C" int afft_gemm_packed_wanted(int M, int N, int K) {
-  return (g_variant == 0 && bd_packed_wins(M, N, K)) ? 1 : 0;
+  return plan_of_shape(M, N, K, false, false, 0, true).b_from_packed ? 1 : 0;
 }
 
 extern "C" int64_t afft_gemm_workspace_bytes(int M, int N, int K, int a_kstrided, int b_kstrided) {
-  const int v = choose_variant(M, N, K, a_kstrided != 0, b_kstrided != 0);
-  const int64_t b = splitk_bytes(v, M, N, K, nullptr);
+  const int s = plan_of_shape(M, N, K, a_kstrided != 0, b_kstrided != 0).splitk;
+  const int64_t b = s > 1 ? splitk_bytes(M, N, s) : 0;      // (no tiles: nothing to park)
   return b ? b + AFFT_GEMM_WS_HEADER : 0;
 }
 
 extern "C" int afft_gemm_splitk_for(int M, int N, int K, int a_kstrided, int b_kstrided) {
-  const int v = choose_variant(M, N, K, a_kstrided != 0, b_kstrided != 0);
-  return v >= 4 ? 1 : choose_splitk(v, M, N, K);
+  return plan_of_shape(M, N, K, a_kstrided != 0, b_kstrided != 0).splitk;
 }
 
 extern "C" int afft_gemm_trace_begin(int32_t capacity) {
@@ -686,8 +578,9 @@ extern "C" int afft_set_gemm_variant(int v) {
   return 0;
 }
 
-extern "C" int afft_gemm(const afft_gemm_t* d, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+// Everything afft_gemm does before it launches -- validation, the fast-path gate, the plan -- shared with afft_gemm_plan_for: no
+// stream is touched and no operand dereferenced.  0 = q is filled, else afft_gemm's error code (afft_last_error is set).
+static int prepare_gemm(const afft_gemm_t* d, GemmPrep& q) {
   AFFT_CHECK(d != nullptr, "afft_gemm: null descriptor");
   AFFT_CHECK(d->M >= 0 && d->N >= 0 && d->K >= 0, "afft_gemm: negative size");
   AFFT_CHECK(d->dtype == AFFT_F32 || d->dtype == AFFT_BF16, "afft_gemm: bad dtype %d", d->dtype);
@@ -695,9 +588,10 @@ extern "C" int afft_gemm(const afft_gemm_t* d, void* stream_) {
   AFFT_CHECK(!d->accumulate || d->out_dtype == AFFT_F32, "afft_gemm: accumulate needs an fp32 output");
   AFFT_CHECK(d->act >= AFFT_ACT_NONE && d->act <= AFFT_ACT_SIGMOID_GATE, "afft_gemm: bad activation %d", d->act);
   AFFT_CHECK(!act_needs_aux(d->act) || d->aux, "afft_gemm: this activation needs aux");
+  q.path = GemmPrep::kEmpty;
   if (d->M == 0 || d->N == 0) return 0;
 
-  EpiParams e;
+  EpiParams& e = q.e;
   e.M = d->M; e.N = d->N; e.alpha = d->alpha; e.bias = d->bias; e.act = d->act;
   e.aux = d->aux; e.ldaux = d->ldaux; e.aux_dtype = d->aux_dtype;
   e.pre = d->pre; e.ldpre = d->ldpre; e.pre_dtype = d->pre_dtype;
@@ -751,29 +645,53 @@ extern "C" int afft_gemm(const afft_gemm_t* d, void* stream_) {
                                 aligned16(d->a8) && aligned16(d->b8)),
              "afft_gemm: split3 = 3 needs the two e4m3 byte planes (16-byte aligned rows) and K %% 128 == 0");
   AFFT_CHECK(!d->split3 || fast, "afft_gemm: split3 needs 16-bit planes in a fast-path layout (K %% 64 == 0, 16-byte aligned rows)");
+  q.path = fast ? GemmPrep::kFast : GemmPrep::kExact;
   if (fast) {
+    q.p = GemmProblem{d->M, d->N, d->K, !a_kc, !b_kc, lda, ldb, d->a8_ld / 2, d->b8_ld / 2, d->a_lo, d->b_lo, d->split3,
+                      d->b_packed && ldb == d->K, d->workspace ? d->workspace_bytes : 0};
+    q.plan = plan_gemm(q.p, tuning());
+    if (q.plan.refusal) { afft_set_error("%s", q.plan.refusal); return 1; }
+  }
+  return 0;
+}
+
+extern "C" int afft_gemm_plan_for(const afft_gemm_t* d, afft_gemm_trace_rec_t* out) {
+  GemmPrep q;
+  if (int rc = prepare_gemm(d, q)) return -rc;
+  if (q.path != GemmPrep::kFast) return 0;
+  if (out) *out = trace_rec(d, q);
+  return 1;
+}
+
+extern "C" int afft_gemm(const afft_gemm_t* d, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  GemmPrep q;
+  if (int rc = prepare_gemm(d, q)) return rc;
+  if (q.path == GemmPrep::kEmpty) return 0;
+  if (q.path == GemmPrep::kFast) {
+    const GemmPlan& plan = q.plan;
     GemmFast g;
-    g.A = (const bf16_t*)d->A; g.B = (const bf16_t*)d->B;
-    g.lda = lda; g.ldb = ldb;
-    g.K = d->split3 == 3 ? d->K + d->K / 2 : d->split3 == 2 ? 2 * d->K : d->split3 == 1 ? 3 * d->K : d->K;      // in 64-wide K-tiles of 128 B per row
+    g.A = (const bf16_t*)d->A; g.B = (const bf16_t*)(plan.b_from_packed ? d->b_packed : d->B);
+    g.lda = q.p.lda; g.ldb = q.p.ldb;
+    g.K = plan.K;
     g.nk_seg = d->K / BK;
     g.a_lo = d->a_lo; g.b_lo = d->b_lo;
-    g.A8 = (const bf16_t*)d->a8; g.B8 = (const bf16_t*)d->b8; g.lda8 = d->a8_ld / 2; g.ldb8 = d->b8_ld / 2;
-    g.e = e;
+    g.A8 = (const bf16_t*)d->a8; g.B8 = (const bf16_t*)d->b8; g.lda8 = q.p.lda8; g.ldb8 = q.p.ldb8;
+    g.splitk = plan.splitk;
+    g.counters = plan.splitk > 1 ? (int*)d->workspace : nullptr;
+    g.ws = plan.splitk > 1 ? (float*)((char*)d->workspace + AFFT_GEMM_WS_HEADER) : nullptr;
+    g.e = q.e;
     // bf16-operand kernels: activation math on v_exp_f32 / v_rcp_f32 (common.h: AFFT_ACT_FAST, |error| ~2e-7) instead of the
     // library's erff / tanhf, whose 45-80 instructions per element showed as +64..140 us per launch; AFFT_EXACT_ACT=1 keeps them
     static const bool exact_act = [] { const char* v = getenv("AFFT_EXACT_ACT"); return v && v[0] == '1'; }();
     if (g.e.act != AFFT_ACT_NONE && !exact_act) g.e.act |= AFFT_ACT_FAST;
-    const bool A_KS = !a_kc, B_KS = !b_kc;
-    if (!A_KS && !B_KS) return launch_layout<false, false>(g, stream, d);
-    if (!A_KS && B_KS) return launch_layout<false, true>(g, stream, d);
-    return launch_layout<true, true>(g, stream, d);
+    return launch_traced(q, g, stream, d);
   }
   GemmF32 g;
   g.A = d->A; g.a_rs = d->a_rs; g.a_cs = d->a_cs;
   g.B = d->B; g.b_rs = d->b_rs; g.b_cs = d->b_cs;
   g.K = d->K; g.tiles_m = (d->M + 63) / 64;
-  g.e = e;
+  g.e = q.e;
   const int grid = g.tiles_m * ((d->N + 63) / 64);
   if (d->dtype == AFFT_F32) hipLaunchKernelGGL(gemm_f32_kernel<float>, dim3(grid), dim3(256), 0, stream, g);
   else hipLaunchKernelGGL(gemm_f32_kernel<bf16_t>, dim3(grid), dim3(256), 0, stream, g);

@@ -277,7 +277,6 @@ int launch_bd(GemmFast& g, hipStream_t stream) {
   auto kern = gemm_bf16_bd_kernel<NI, PA, PB, PACKED>;
   static std::atomic<uint64_t> attr_done{0};
   if (int rc = afft_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, &attr_done)) return rc;
-  g_launched_variant = (NI == 10 ? 8 : 7) + (PACKED ? 2 : 0);      // 7 / 8 row-major B, 9 / 10 fragment-packed B
   hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n), dim3(256), lds, stream, g);
   AFFT_LAUNCH_CHECK();
   return 0;
@@ -292,7 +291,8 @@ int launch_bd(GemmFast& g, hipStream_t stream) {
 #define AFFT_BD_PB160 2
 #endif
 
-// rows160 != 0: 160 x 256 tiles, else 256 x 256.  NT layout only, N % 16 == 0 (afft_gemm checks).
+// GemmPlan.kernel 7 / 8: row-major B, 9 / 10: fragment-packed B; rows160 != 0 (8, 10): 160 x 256 tiles, else 256 x 256.  NT layout only,
+// N % 16 == 0 (gemm_plan.h: bd_ok).
 int afft_gemm_launch_bd(int rows160, int packed, afft_gemm_detail::GemmFast& g, hipStream_t stream) {
   if (packed) {
     if (rows160) return launch_bd<10, AFFT_BD_PA, AFFT_BD_PB160, true>(g, stream);

@@ -684,42 +684,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp2_kernel(const GemmFast g)
   pp_epilogue(g, smem, acc, m0, n0, lane, wave, gp, wc);
 }
 
-#ifndef AFFT_PP2
-#define AFFT_PP2 1      // 0: every shape on gemm_bf16_pp_kernel (A/B builds)
-#endif
-bool pp2_shape(int M, int N, int K) { return AFFT_PP2 && M % 256 == 0 && N % 256 == 0 && K % (2 * BK) == 0 && K >= 4 * BK; }
-// the running K offset lives in a 32-bit VGPR (k-strided operands: K rows of `ld` elements): the whole walk must stay below 4 GiB
-inline bool walk_fits32(bool ks, int K, int64_t ld) { return ks ? (int64_t)(K + 8) * ld * 2 < (1LL << 32) : (8 * ld + K) * 2 < (1LL << 32); }
-template <bool A_KS, bool B_KS>
-bool pp2_takes(const GemmFast& g) { return pp2_shape(g.e.M, g.e.N, g.K) && walk_fits32(A_KS, g.K, g.lda) && walk_fits32(B_KS, g.K, g.ldb); }
-
-// fp16 + fp8 forward (X3 = 3): g.K counts both segments in 64-wide K-tiles (nk_seg + nk_seg / 2); pairs in both: nk_seg % 4 == 0, nk_seg >= 4
-bool pp2x3_takes(const GemmFast& g) {
-#ifdef AFFT_PP2_X3_OFF
-  return false;
-#else
-  return AFFT_PP2 && g.e.M % 256 == 0 && g.e.N % 256 == 0 && g.nk_seg % 4 == 0 && g.nk_seg >= 4 && g.K == g.nk_seg * BK + g.nk_seg * BK / 2 &&
-         walk_fits32(false, g.nk_seg * BK, g.lda) && walk_fits32(false, g.nk_seg * BK, g.ldb) && walk_fits32(false, g.nk_seg * BK, g.lda8) &&
-         walk_fits32(false, g.nk_seg * BK, g.ldb8);
-#endif
-}
-
-// bf16x3 / fp16 two-pass (X3 = 1 / 2): g.K counts all segments; whole tiles, an even number of K-tiles per segment (pairs never straddle a
-// segment), every plane inside the 32-bit walk
-template <bool A_KS, bool B_KS, int X3>
-bool pp2planes_takes(const GemmFast& g) {
-#ifdef AFFT_PP2_PLANES_OFF
-  return false;
-#else
-  const int64_t span = ((int64_t)(g.a_lo > g.b_lo ? g.a_lo : g.b_lo)) * 2;
-  const bool one_pass = X3 == 2 && g.K == g.nk_seg * BK && g.nk_seg >= 4;      // afft_gemm_t.split3 = 4: the first segment alone (no jump is ever taken)
-  return AFFT_PP2 && g.e.M % 256 == 0 && g.e.N % 256 == 0 && g.nk_seg % 2 == 0 && g.nk_seg >= 2 && (g.K == (X3 == 1 ? 3 : 2) * g.nk_seg * BK || one_pass) &&
-         span < (1LL << 30) && walk_fits32(A_KS, g.nk_seg * BK, g.lda) && walk_fits32(B_KS, g.nk_seg * BK, g.ldb) &&
-         (A_KS ? (int64_t)g.nk_seg * BK * g.lda * 2 : (int64_t)8 * g.lda * 2) + span < (1LL << 31) &&
-         (B_KS ? (int64_t)g.nk_seg * BK * g.ldb * 2 : (int64_t)8 * g.ldb * 2) + span < (1LL << 31);
-#endif
-}
-
 template <bool A_KS, bool B_KS, int X3 = 0>
 int launch_pp2(GemmFast& g, hipStream_t stream) {
   constexpr size_t lds = 128 * 1040;
@@ -728,7 +692,6 @@ int launch_pp2(GemmFast& g, hipStream_t stream) {
   auto kern = gemm_bf16_pp2_kernel<A_KS, B_KS, X3>;
   static std::atomic<uint64_t> attr_done{0};
   if (int rc = afft_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, &attr_done)) return rc;
-  g_launched_variant = 13;
   hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n), dim3(512), lds, stream, g);
   AFFT_LAUNCH_CHECK();
   return 0;
@@ -743,7 +706,6 @@ int launch_pp(GemmFast& g, hipStream_t stream) {
   static std::atomic<uint64_t> attr_done{0};
   if (int rc = afft_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, &attr_done)) return rc;
   const int grid = g.tiles_m * g.tiles_n;
-  g_launched_variant = 3;
 #ifdef AFFT_PP_STAMP
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, g, g_pp_stamp);
 #else
@@ -753,6 +715,11 @@ int launch_pp(GemmFast& g, hipStream_t stream) {
   return 0;
 }
 
+// steady: the plan chose the steady-state kernel (GemmPlan.kernel = 13), else the general one (3)
+template <bool A_KS, bool B_KS, int X3 = 0>
+int launch_pp_kernel(bool steady, GemmFast& g, hipStream_t stream) {
+  return steady ? launch_pp2<A_KS, B_KS, X3>(g, stream) : launch_pp<A_KS, B_KS, X3>(g, stream);
+}
 
 }  // namespace
 
@@ -760,29 +727,23 @@ int launch_pp(GemmFast& g, hipStream_t stream) {
 extern "C" void afft_debug_pp_stamp(void* p) { g_pp_stamp = (unsigned long long*)p; }
 #endif
 
-int afft_gemm_launch_pp(int a_ks, int b_ks, afft_gemm_detail::GemmFast& g, hipStream_t stream, int x3) {
-#ifndef AFFT_PP_NT_ONLY   // development switch: build only the plain NT instantiation (compile time)
-  if (x3 == 3) {   // fp16 + fp8 lo pass: nn.Linear forward GEMMs (NT) only
-    if (!a_ks && !b_ks) return pp2x3_takes(g) ? launch_pp2<false, false, 3>(g, stream) : launch_pp<false, false, 3>(g, stream);
-    afft_set_error("afft_gemm: the fp16 + fp8 mode (split3 = 3) is built for the NT layout only");
-    return 1;
-  }
-  if (x3 == 2) {   // fp16x2: forward GEMMs only (NT, and NN for [in, out] weights)
-    if (!a_ks && !b_ks) return pp2planes_takes<false, false, 2>(g) ? launch_pp2<false, false, 2>(g, stream) : launch_pp<false, false, 2>(g, stream);
-    if (!a_ks && b_ks) return pp2planes_takes<false, true, 2>(g) ? launch_pp2<false, true, 2>(g, stream) : launch_pp<false, true, 2>(g, stream);
-    afft_set_error("afft_gemm: the fp16 two-pass mode is built for the forward layouts only");
-    return 1;
-  }
-  if (x3) {        // bf16x3 operand planes
-    if (!a_ks && !b_ks) return pp2planes_takes<false, false, 1>(g) ? launch_pp2<false, false, 1>(g, stream) : launch_pp<false, false, 1>(g, stream);
-    if (!a_ks && b_ks) return pp2planes_takes<false, true, 1>(g) ? launch_pp2<false, true, 1>(g, stream) : launch_pp<false, true, 1>(g, stream);
-    if (a_ks && b_ks) return pp2planes_takes<true, true, 1>(g) ? launch_pp2<true, true, 1>(g, stream) : launch_pp<true, true, 1>(g, stream);
-  }
+// the plan's choice (gemm_plan.h: pp_kernel) -> the instantiation.  x3: 3 = fp16 + fp8 lo pass (nn.Linear forward GEMMs, NT only), 2 = fp16x2
+// (forward GEMMs only: NT, and NN for [in, out] weights), 1 = bf16x3 operand planes
+int afft_gemm_launch_pp(int steady, int a_ks, int b_ks, int x3, afft_gemm_detail::GemmFast& g, hipStream_t stream) {
+#ifdef AFFT_PP_NT_ONLY   // development switch: build only the plain NT instantiation (compile time)
+  x3 = 0;
+#else
+  if (x3 == 3 && !a_ks && !b_ks) return launch_pp_kernel<false, false, 3>(steady, g, stream);
+  if (x3 == 2 && !a_ks && !b_ks) return launch_pp_kernel<false, false, 2>(steady, g, stream);
+  if (x3 == 2 && !a_ks && b_ks) return launch_pp_kernel<false, true, 2>(steady, g, stream);
+  if (x3 == 1 && !a_ks && !b_ks) return launch_pp_kernel<false, false, 1>(steady, g, stream);
+  if (x3 == 1 && !a_ks && b_ks) return launch_pp_kernel<false, true, 1>(steady, g, stream);
+  if (x3 == 1 && a_ks && b_ks) return launch_pp_kernel<true, true, 1>(steady, g, stream);
 #endif
-  if (!a_ks && !b_ks) return pp2_takes<false, false>(g) ? launch_pp2<false, false>(g, stream) : launch_pp<false, false>(g, stream);
+  if (x3 == 0 && !a_ks && !b_ks) return launch_pp_kernel<false, false>(steady, g, stream);
 #ifndef AFFT_PP_NT_ONLY
-  if (!a_ks && b_ks) return pp2_takes<false, true>(g) ? launch_pp2<false, true>(g, stream) : launch_pp<false, true>(g, stream);
-  if (a_ks && b_ks) return pp2_takes<true, true>(g) ? launch_pp2<true, true>(g, stream) : launch_pp<true, true>(g, stream);
+  if (x3 == 0 && !a_ks && b_ks) return launch_pp_kernel<false, true>(steady, g, stream);
+  if (x3 == 0 && a_ks && b_ks) return launch_pp_kernel<true, true>(steady, g, stream);
 #endif
   afft_set_error("afft_gemm: layout (A k-strided, B k-contiguous) is not built");
   return 1;

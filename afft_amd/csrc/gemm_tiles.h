@@ -4,6 +4,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "gemm_plan.h"      // BK; the dispatch plan the launchers of these kernels are handed
 
 namespace afft_gemm_detail {
 
@@ -16,7 +17,6 @@ __device__ __forceinline__ void static_for(F&& f) {
   }
 }
 
-constexpr int BK = 64;
 #ifndef AFFT_GROUP_M
 #define AFFT_GROUP_M 6     // tile rows per column group inside an XCD's chunk.  Alone every path shape is flat over 4..12 (round 1 took 8); inside
 #endif                     // the step, beside the other stream, 4-6 are 1-2.3 % ahead of 8 on cfg2 / EK100 / cfg4 (profiles/r02_knob_sweeps.txt)
@@ -41,10 +41,6 @@ struct GemmFast {
   const bf16_t* A8; const bf16_t* B8; int64_t lda8, ldb8;
   EpiParams e;
 };
-
-// the trace variant (afft_gemm_trace_rec_t.variant) of the kernel the last fast-path launch of this thread ran: written by the
-// launcher that launches (gemm.hip launch_fast, gemm_pp.hip launch_pp / launch_pp2, gemm_bd.hip launch_bd), read by the trace hook
-extern thread_local int g_launched_variant;
 
 // global K-tile index -> K offset inside the segment and the operand planes of that segment (wave-uniform SALU work)
 // the MFMA of every bf16-path kernel: 16-bit operands by the instantiation's plane format (X3 = 2: fp16, else bf16)

@@ -163,8 +163,12 @@ int afft_set_gemm_variant(int variant);
  * parks its fp32 partial tile in the caller's workspace (afft_gemm_t.workspace) and the slice that arrives last adds them up in slice order
  * and runs the epilogue (no waiting, any epilogue, bitwise repeatable).  mode: 0 off, 1 auto (default), 2 / 4 force. */
 int afft_set_gemm_splitk(int mode);
-/* Which bf16 tile shape afft_gemm picks for a fast-path problem (1 / 3 as above); used by bench.py to attribute
- * launches to kernel symbols. */
+/* The shape queries (afft_gemm_variant_for, _splitk_for, _workspace_bytes, _lo8_ok, _packed_wanted) read the same dispatch plan as
+ * afft_gemm (csrc/gemm_plan.h) for the ROW-MAJOR problem their arguments describe: unpadded operands, no fragment-packed B (except
+ * _packed_wanted), ample workspace.  What a particular descriptor runs -- pitches, planes, b_packed, the workspace it offers -- is
+ * afft_gemm_plan_for's answer.
+ * afft_gemm_variant_for: the tile shape of that problem in afft_set_gemm_variant's numbers (1 or 3 under automatic dispatch, the
+ * forced variant where it applies), whichever kernel of that shape runs; used by bench.py to attribute launches to kernel symbols. */
 int afft_gemm_variant_for(int M, int N, int K, int a_kstrided, int b_kstrided);
 /* K-slices afft_gemm uses for that problem under the current split-K mode (1 = none). */
 int afft_gemm_splitk_for(int M, int N, int K, int a_kstrided, int b_kstrided);
@@ -181,6 +185,10 @@ typedef struct {
 } afft_gemm_trace_rec_t;
 int afft_gemm_trace_begin(int32_t capacity);
 int afft_gemm_trace_end(afft_gemm_trace_rec_t* out, int32_t capacity);
+/* What afft_gemm would do with this descriptor, without doing it: the same validation, fast-path gate and dispatch plan, no stream
+ * touched, no operand dereferenced (no device needed).  1: a fast-path kernel would run and *out is the record the trace would hold
+ * for it (ms = 0); 0: the exact-fp32 kernel would run (or nothing: M or N = 0); < 0: afft_gemm would fail (afft_last_error says why). */
+int afft_gemm_plan_for(const afft_gemm_t* g, afft_gemm_trace_rec_t* out);
 
 /* The same hook for the HBM-bound kernels of the path (bench.py's `hbm_kernels` / `roofline.sublayers`): while a kernel trace is
  * open every afft_attention_fwd / _bwd and afft_layernorm_fwd / _bwd call -- from any entry point, the composite ones included --

@@ -1,7 +1,9 @@
-"""The GEMM case table shared by the kernel-vs-float64 GEMM section of test_kernels_gpu.py and the coverage check of
+"""The GEMM case table shared by the kernel-vs-float64 GEMM section of test_kernels_gpu.py and the coverage and dispatch checks of
 test_gemm_coverage_cpu.py: for every case the layout, shape, precision mode, forced dispatch, epilogue -- and the kernel
 instantiation the dispatcher must run for it, written the way `nm -C` prints the symbol.  Every `gemm_*_kernel<...>`
-instantiation the library compiles is the expected kernel of at least one case (test_gemm_coverage_cpu.py).
+instantiation the library compiles is the expected kernel of at least one case (test_gemm_coverage_cpu.py).  Below the table: the
+operand geometry of a case (pitches, plane offsets: what dispatch depends on), shared by the GPU test, which allocates such operands,
+and the CPU test, which asks afft_gemm_plan_for about a descriptor of them.
 
 layout: nt (A[M][K], B[N][K]), nn (A[M][K], B[K][N]), tn (A[K][M], B[K][N]), tt (A[K][M], B[N][K]: exact-fp32 kernel only).
 mode:   bf16           plain bf16 operands (the fast path, or the exact-fp32 kernel where the fast path refuses the problem)
@@ -227,3 +229,81 @@ CASES = [
 ]
 
 assert len({c.name for c in CASES}) == len(CASES), "case names must be unique"
+
+
+def _traced_symbol(r):
+    """afft_gemm_trace_rec_t -> the kernel symbol (as nm -C prints it) that the launcher recorded"""
+    b = lambda x: "true" if x else "false"    # noqa: E731
+    a, bb, sk = b(r.a_kstrided), b(r.b_kstrided), b(r.splitk > 1)
+    x3 = 2 if r.split3 == 4 else int(r.split3)      # one fp16 pass runs the two-pass instantiation over one segment
+    if r.variant in (1, 4):
+        return f"gemm_bf16_kernel<2, 2, {2 if r.variant == 1 else 4}, {a}, {bb}, {sk}, {x3}>"
+    if r.variant == 12:
+        return f"gemm_bf16_g2_kernel<{a}, {bb}, {sk}, {b(x3 == 2)}>"
+    if r.variant in (3, 13):
+        return f"gemm_bf16_{'pp' if r.variant == 3 else 'pp2'}_kernel<{a}, {bb}, {x3}>"
+    if r.variant in (7, 8, 9, 10):
+        rows160 = r.variant in (8, 10)
+        return f"gemm_bf16_bd_kernel<{10 if rows160 else 16}, 3, {2 if rows160 else 1}, {b(r.variant >= 9)}>"
+    return f"<trace variant {r.variant}>"
+
+
+# ---- operand geometry
+def padded_pitch(cols, col0=0, al=8):
+    """row pitch of a NaN-padded operand view of `cols` columns starting at column col0 of its buffer: a little wider than the view,
+    a multiple of `al` elements (8: 16-bit operands, 16: e4m3 byte planes)"""
+    return col0 + cols + al + (-(col0 + cols)) % al
+
+
+def plane_shape(rows, cols):
+    """[rows, cols] of one plane of an ops.Split: both padded to 64"""
+    return (rows + 63) // 64 * 64, (cols + 63) // 64 * 64
+
+
+def pitches(c):
+    """{lda, ldb, ld8}: element pitches of the stored operands of case c (A [K, M] if transposed else [M, K]; B [N, K] if transposed
+    else [K, N]) and the byte pitch of the e4m3 planes (fp16_lo8)"""
+    a_t, b_t = c.layout[0] == "t", c.layout[1] == "t"
+    a_cols, b_cols = (c.M if a_t else c.K), (c.K if b_t else c.N)
+    if c.mode == "bf16x3":
+        lda, ldb = plane_shape(1, a_cols)[1], plane_shape(1, b_cols)[1]
+    else:
+        lda = (c.ld if a_t else 0) or padded_pitch(a_cols, c.epi.get("a_off", 0))
+        ldb = (c.ld if not b_t else 0) or padded_pitch(b_cols)
+        if c.mode == "fp16x2":
+            lda = plane_shape(1, a_cols)[1]
+        if c.variant == 9 or c.epi.get("packed"):      # the packed image / the weight beside it: unpadded (the B-direct path wants b_cs == K)
+            ldb = c.K
+    return dict(lda=lda, ldb=ldb, ld8=padded_pitch(c.K, 0, 16))
+
+
+def gemm_fields(layout, M, N, K, lda, ldb, *, split3=0, f32=False, a_off=0, a_lo=0, b_lo=0, ld8=0, packed=False, ws_bytes=0):
+    """afft_gemm_t fields (name -> value) that validation and dispatch read, for operands of the given geometry at synthetic 16-byte
+    aligned addresses (nothing dereferences them on the way to the plan)"""
+    a_t, b_t = layout[0] == "t", layout[1] == "t"
+    f = dict(M=M, N=N, K=K, dtype=0 if f32 else 1, split3=split3, a_lo=a_lo, b_lo=b_lo,
+             A=(1 << 32) + a_off * (4 if f32 else 2), B=2 << 32, out=3 << 32, ldo=padded_pitch(N), alpha=1.0)
+    f["a_rs"], f["a_cs"] = (1, lda) if a_t else (lda, 1)
+    f["b_rs"], f["b_cs"] = (1, ldb) if b_t else (ldb, 1)
+    if split3 == 3:
+        f.update(a8=4 << 32, b8=5 << 32, a8_ld=ld8, b8_ld=ld8)
+    if packed:
+        f["b_packed"] = 6 << 32
+    if ws_bytes:
+        f.update(workspace=7 << 32, workspace_bytes=ws_bytes)
+    return f
+
+
+def dispatch_fields(c):
+    """gemm_fields of case c as the GPU test's operands make them: strides and pitches of its NaN-padded views and Split planes, plane
+    offsets, the e4m3 planes' pitch, the packed flag, A one element off alignment (a_off), the workspace ops.gemm hands over"""
+    from afft_amd import ops
+    a_t, b_t = c.layout[0] == "t", c.layout[1] == "t"
+    p = pitches(c)
+    split3 = {"bf16": 0, "f32": 0, "bf16x3": 1, "fp16x2": 2, "fp16_lo8": 3, "fp16": 4}[c.mode]
+    a_plane = plane_shape(*((c.K, c.M) if a_t else (c.M, c.K)))
+    b_plane = plane_shape(*((c.N, c.K) if b_t else (c.K, c.N)))
+    return gemm_fields(c.layout, c.M, c.N, c.K, p["lda"], p["ldb"], split3=split3, f32=c.mode == "f32", a_off=c.epi.get("a_off", 0),
+                       a_lo=a_plane[0] * a_plane[1] if split3 in (1, 2) else 0, b_lo=b_plane[0] * b_plane[1] if split3 == 1 else 0,
+                       ld8=p["ld8"], packed=bool(c.epi.get("packed")),
+                       ws_bytes=ops._WS_BYTES if c.mode != "f32" and split3 != 1 else 0)

@@ -1,13 +1,16 @@
 """CPU: every GEMM kernel instantiation the library compiles is the expected kernel of at least one case of the shared GEMM case
 table (tests/gemm_cases.py), which the GPU suite runs against float64 and checks, through the GEMM trace, that it ran that kernel.
-A kernel added without a case fails here, by name.  No compute call is made (no GPU in the build container)."""
+A kernel added without a case fails here, by name.  The dispatch plan (csrc/gemm_plan.h) is host arithmetic: afft_gemm_plan_for
+answers here what afft_gemm would launch for every case, and the shape queries are held against it.  No compute call is made (no
+GPU in the build container)."""
+import ctypes
 import os
 import re
 import subprocess
 
 import pytest
 
-from gemm_cases import CASES
+from gemm_cases import CASES, _traced_symbol, dispatch_fields, gemm_fields
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _KERNEL = re.compile(r"\b(gemm_[a-z0-9_]+_kernel<[^()]*>)\(")
@@ -54,3 +57,61 @@ def test_case_table_is_well_formed():
         assert c.variant in (0, 1, 3, 4, 7, 8, 9, 10) and c.splitk in (0, 1, 2, 4), c.name
         assert not (c.epi.get("accumulate") and c.epi.get("out", "f32") != "f32"), c.name
         assert not ((c.epi.get("out_lo") or c.epi.get("out_lo8")) and c.epi.get("out") != "f16"), c.name
+
+
+def _plan_for(_lib, fields):
+    """afft_gemm_plan_for on a descriptor with these fields -> (return value, trace record)"""
+    d, rec = _lib.GemmDesc(), _lib.GemmTraceRec()
+    for k, v in fields.items():
+        setattr(d, k, v)
+    return _lib.lib().afft_gemm_plan_for(ctypes.byref(d), ctypes.byref(rec)), rec
+
+
+def test_every_case_dispatches_to_its_kernel(built_lib):
+    """The kernel the table names for a case is the kernel the dispatch plan picks for the case's operands (the GPU suite checks the same
+    through the trace of the launch itself).  The expectations were established on a 256-CU part; without a device the library
+    assumes 256 CUs as well."""
+    lib = built_lib.lib()
+    for c in CASES:
+        built_lib.check(lib.afft_set_gemm_variant(c.variant))
+        built_lib.check(lib.afft_set_gemm_splitk(c.splitk))
+        try:
+            rc, rec = _plan_for(built_lib, dispatch_fields(c))
+        finally:
+            built_lib.check(lib.afft_set_gemm_variant(0))
+            built_lib.check(lib.afft_set_gemm_splitk(1))
+        if c.fast:
+            assert rc == 1, (c.name, rc, lib.afft_last_error())
+            assert _traced_symbol(rec) == c.kernel, f"{c.name}: the plan picks {_traced_symbol(rec)}, the case is written for {c.kernel}"
+            assert (rec.M, rec.N, rec.K, rec.ms) == (c.M, c.N, c.K, 0.0), c.name
+        else:
+            assert rc == 0, (c.name, rc, _traced_symbol(rec))
+
+
+def test_shape_queries_agree_with_the_plan(built_lib):
+    """The five shape queries against afft_gemm_plan_for on the row-major problem they describe (unpadded operands, ample workspace),
+    for the shapes of the training step's forward and backward GEMMs."""
+    from afft_amd import ops
+    lib = built_lib.lib()
+    shapes = [c for c in CASES if c.name.startswith(("fwd_", "bwd_"))]
+    assert len(shapes) >= 20
+    for c in shapes:
+        M, N, K = c.M, c.N, c.K
+        a_t, b_t = c.layout[0] == "t", c.layout[1] == "t"
+        a_ks, b_ks = int(a_t), int(not b_t)
+        geom = (c.layout, M, N, K, M if a_t else K, K if b_t else N)
+        rc, rec = _plan_for(built_lib, gemm_fields(*geom, ws_bytes=ops._WS_BYTES))
+        assert rc == 1, c.name
+        assert lib.afft_gemm_variant_for(M, N, K, a_ks, b_ks) == {12: 1, 13: 3}.get(rec.variant, rec.variant), c.name
+        assert lib.afft_gemm_splitk_for(M, N, K, a_ks, b_ks) == rec.splitk, c.name
+        need = lib.afft_gemm_workspace_bytes(M, N, K, a_ks, b_ks)
+        assert (need > 0) == (rec.splitk > 1) and need <= ops._WS_BYTES, c.name
+        if need:      # exactly that many bytes let the launch split; one fewer and it runs unsplit
+            assert _plan_for(built_lib, gemm_fields(*geom, ws_bytes=need))[1].splitk == rec.splitk, c.name
+            assert _plan_for(built_lib, gemm_fields(*geom, ws_bytes=need - 1))[1].splitk == 1, c.name
+        # the NT problem of this size: with a fragment-packed B, and in the fp16 + fp8 precision
+        rc, rec = _plan_for(built_lib, gemm_fields("nt", M, N, K, K, K, packed=True, ws_bytes=ops._WS_BYTES))
+        assert rc == 1 and lib.afft_gemm_packed_wanted(M, N, K) == int(rec.variant == 10), c.name
+        rc, rec = _plan_for(built_lib, gemm_fields("nt", M, N, K, K, K, split3=3, ld8=K, ws_bytes=ops._WS_BYTES))
+        assert K % 128 == 0 and lib.afft_gemm_lo8_ok(M, N, K) == int(rc == 1), (c.name, rc)
+        assert rc == 1 or (rc < 0 and b"afft_gemm_lo8_ok" in lib.afft_last_error()), (c.name, rc)

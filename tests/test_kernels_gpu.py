@@ -1345,29 +1345,13 @@ def test_errors_are_reported():
 # larger buffer whose other bits are a sentinel: a read outside the problem turns an output NaN, a write outside it breaks the sentinel.
 from gemm_cases import CASES as GEMM_TABLE  # noqa: E402
 from gemm_cases import DGELU_ERF, DGELU_TANH, GELU_ERF, GELU_TANH, RELU, SIGMOID_GATE  # noqa: E402
+from gemm_cases import _traced_symbol, padded_pitch, pitches, plane_shape  # noqa: E402
 
 _TDT = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
 _SENTINEL = {torch.float32: (torch.int32, 0x7FC0DEAD), torch.bfloat16: (torch.int16, 0x7DAD), torch.float16: (torch.int16, 0x7DAD),
              torch.uint8: (torch.uint8, 0xA5)}
 _E4M3_OF_INT = (0xC0, 0xB8, 0x00, 0x38, 0x40)      # e4m3fn codes of -2 .. 2
 _ACT_TOL = {GELU_ERF: 1e-6, GELU_TANH: 1e-6, DGELU_ERF: 1e-6, DGELU_TANH: 4e-6, SIGMOID_GATE: 1e-6}     # test_epilogue_activation_accuracy
-
-
-def _traced_symbol(r):
-    """afft_gemm_trace_rec_t -> the kernel symbol (as nm -C prints it) that the launcher recorded"""
-    b = lambda x: "true" if x else "false"    # noqa: E731
-    a, bb, sk = b(r.a_kstrided), b(r.b_kstrided), b(r.splitk > 1)
-    x3 = 2 if r.split3 == 4 else int(r.split3)      # one fp16 pass runs the two-pass instantiation over one segment
-    if r.variant in (1, 4):
-        return f"gemm_bf16_kernel<2, 2, {2 if r.variant == 1 else 4}, {a}, {bb}, {sk}, {x3}>"
-    if r.variant == 12:
-        return f"gemm_bf16_g2_kernel<{a}, {bb}, {sk}, {b(x3 == 2)}>"
-    if r.variant in (3, 13):
-        return f"gemm_bf16_{'pp' if r.variant == 3 else 'pp2'}_kernel<{a}, {bb}, {x3}>"
-    if r.variant in (7, 8, 9, 10):
-        rows160 = r.variant in (8, 10)
-        return f"gemm_bf16_bd_kernel<{10 if rows160 else 16}, 3, {2 if rows160 else 1}, {b(r.variant >= 9)}>"
-    return f"<trace variant {r.variant}>"
 
 
 def _ints(shape, amp, sh, gen):
@@ -1379,8 +1363,7 @@ def _nan_padded(t, dtype, ld=0, col0=0):
     multiple of 8 elements, of 16 for e4m3 byte planes), starting at column col0: the view the GEMM gets; whatever it may read of the
     rest is NaN"""
     R, C = t.shape
-    al = 16 if dtype == torch.uint8 else 8
-    ld = ld or (col0 + C + al + (-(col0 + C)) % al)
+    ld = ld or padded_pitch(C, col0, 16 if dtype == torch.uint8 else 8)
     buf = torch.full((R + 2, ld), 0x7F if dtype == torch.uint8 else float("nan"), dtype=dtype, device=dev())
     v = buf[:R, col0:col0 + C]
     v.copy_(t.to(dtype))
@@ -1431,13 +1414,12 @@ def _operands(c, A, Bm, gen, exact):
     from afft_amd import ops
     a_t, b_t = c.layout[0] == "t", c.layout[1] == "t"
     At, Bt = (A.t() if a_t else A), (Bm.t() if b_t else Bm)      # stored orientation
-    lda = c.ld if a_t else 0
-    ldb = c.ld if not b_t else 0
+    ld = pitches(c)      # the geometry test_gemm_coverage_cpu.py asks the dispatch plan about
     kw = {}
     if c.mode in ("bf16", "f32"):
         dt = torch.float32 if c.mode == "f32" else torch.bfloat16
-        a = _nan_padded(At, dt, lda, col0=c.epi.get("a_off", 0))
-        b = _nan_padded(Bt, dt, ldb)
+        a = _nan_padded(At, dt, ld["lda"], col0=c.epi.get("a_off", 0))
+        b = _nan_padded(Bt, dt, ld["ldb"])
         if c.variant == 9:      # the forced packed variant reads B as the fragment-packed image of the weight [N, K]
             pk = torch.empty(c.N * c.K, dtype=torch.bfloat16, device=dev())
             ops.pack_weight(Bt.float().contiguous(), pk)
@@ -1445,7 +1427,7 @@ def _operands(c, A, Bm, gen, exact):
         elif c.epi.get("packed"):      # b_packed with the row-major weight, unpadded (the B-direct path wants b_cs == K)
             pk = torch.empty(c.N * c.K, dtype=torch.bfloat16, device=dev())
             ops.pack_weight(Bt.float().contiguous(), pk)
-            b = _nan_padded(Bt, dt, c.K)
+            b = _nan_padded(Bt, dt, ld["ldb"])
             kw["b_packed"] = pk
         return a, b, kw, A @ Bm, A.abs() @ Bm.abs()
     # split modes: the planes are built here, so the lo planes carry values of their own (dyadic, non-zero) -- a read of the wrong
@@ -1457,7 +1439,7 @@ def _operands(c, A, Bm, gen, exact):
     def split(X):
         R, C = X.shape
         sp = ops.Split.__new__(ops.Split)
-        sp.planes = torch.zeros(2, (R + 63) // 64 * 64, (C + 63) // 64 * 64, dtype=pdt, device=dev())
+        sp.planes = torch.zeros(2, *plane_shape(R, C), dtype=pdt, device=dev())
         lo = _ints((R, C), 2, lo_sh, gen) if exact else (X - X.to(pdt).double()).to(pdt).double()
         sp.planes[0, :R, :C] = X.to(pdt)
         sp.planes[1, :R, :C] = lo.to(pdt)
@@ -1471,18 +1453,18 @@ def _operands(c, A, Bm, gen, exact):
         Bhi, Blo = (Bhi.t(), Blo.t()) if b_t else (Bhi, Blo)
         ref = Ahi @ Bhi + Alo @ Bhi + Ahi @ Blo      # the kernel's formula: lo x lo is not computed
         return sa, sb, kw, ref, Ahi.abs() @ Bhi.abs() + Alo.abs() @ Bhi.abs() + Ahi.abs() @ Blo.abs()
-    b = _nan_padded(Bt, torch.float16)
+    b = _nan_padded(Bt, torch.float16, ld["ldb"])
     if c.mode == "fp16x2":
         sa, Ahi, Alo = split(A)
         return sa, b, kw, (Ahi + Alo) @ Bm, (Ahi.abs() + Alo.abs()) @ Bm.abs()
-    a = _nan_padded(A, torch.float16)
+    a = _nan_padded(A, torch.float16, ld["lda"])
     if c.mode == "fp16":
         return a, b, kw, A @ Bm, A.abs() @ Bm.abs()
     # fp16 + fp8 lo pass: hi A_hi W16 on the fp16 MFMA, then 2^-19 a8 b8 over e4m3 byte planes (here: codes of the integers -2 .. 2)
     ia, ib = torch.randint(-2, 3, (c.M, c.K), generator=gen, device=dev()), torch.randint(-2, 3, (c.N, c.K), generator=gen, device=dev())
     codes = torch.tensor(_E4M3_OF_INT, dtype=torch.uint8, device=dev())
-    kw["a8"] = _nan_padded(codes[ia + 2].double(), torch.uint8)
-    kw["b8"] = _nan_padded(codes[ib + 2].double(), torch.uint8)
+    kw["a8"] = _nan_padded(codes[ia + 2].double(), torch.uint8, ld["ld8"])
+    kw["b8"] = _nan_padded(codes[ib + 2].double(), torch.uint8, ld["ld8"])
     lo = (ia.double() @ ib.double().t()) * 2.0 ** -19
     return a, b, kw, A @ Bm + lo, A.abs() @ Bm.abs() + (ia.double().abs() @ ib.double().abs().t()) * 2.0 ** -19
 

@@ -212,7 +212,6 @@ int afft_gemm_launch_q4(afft_gemm_detail::GemmFast& g, hipStream_t stream) {
   g.tiles_n = (g.e.N + 255) / 256;
   static std::atomic<uint64_t> attr_done{0};
   if (int rc = afft_ensure_dynamic_lds(reinterpret_cast<const void*>(gemm_bf16_q4_kernel), lds, &attr_done)) return rc;
-  g_launched_variant = 11;
   hipLaunchKernelGGL(gemm_bf16_q4_kernel, dim3(g.tiles_m * g.tiles_n), dim3(256), lds, stream, g);
   AFFT_LAUNCH_CHECK();
   return 0;

@@ -10,7 +10,8 @@ if [ "$1" = "build" ]; then
   cd afft_amd/csrc
   mkdir -p build_var
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -DAFFT_PP_LEAD=7 -DAFFT_PP_ALLOW_RACY_LEAD -DAFFT_PP2=0 -c gemm_pp.hip -o build_var/gemm_pp_lead7.o
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../lib/libafft_hip_lead7.so build_var/gemm_pp_lead7.o build/gemm.o build/gemm_bd.o build/norm.o build/attention.o build/attention_mfma.o build/loss.o build/elementwise.o build/sublayer.o
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -DAFFT_PP2=0 -c gemm.hip -o build_var/gemm_lead7.o      # the pp / pp2 choice is made in gemm.hip (gemm_plan.h)
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../lib/libafft_hip_lead7.so build_var/gemm_pp_lead7.o build_var/gemm_lead7.o build/gemm_bd.o build/norm.o build/attention.o build/attention_mfma.o build/loss.o build/elementwise.o build/sublayer.o
   ls -la ../lib/
   exit 0
 fi
