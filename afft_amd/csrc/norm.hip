@@ -69,9 +69,21 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 // (16 waves per CU and more stay resident, their loads overlap), the two per-row sums are combined over the 4 slices
 // through a double-buffered LDS cell with one barrier per row step, and the dw/db column partials stay in registers
 // until the end, when the 4 row groups add them into one [2][d] LDS slab in a fixed order (deterministic).
+// Rows of 2049 to 4096 columns (RG x CS = 2 x 8): the same 16 waves as 2 row groups x 8 column slices, so that a wave's slice
+// is again at most 128 float4 (NV = 2) and the per-lane state is that of the 2048-wide instantiation (no scratch; the 4 x 4
+// arrangement at NV = 4 spilled 101-125 registers).  The two row sums are combined over 8 cells as a fixed pairwise tree.
+// LDS at d = 4096 with dcol: the [3][4096] fp32 slab, 48 KiB, + 2 x 2 x 8 x 2 cells, 256 B = 49408 B (of 160 KiB per CU).
 constexpr int LNB_RG = 4, LNB_CS = 4;
+constexpr int LNB_WIDE_RG = 2, LNB_WIDE_CS = 8, LNB_WIDE_D = 2048;    // d > LNB_WIDE_D takes the 2 x 8 arrangement
 
-template <int NV, bool DY32>  // float4 chunks per lane inside a slice: d/4 <= LNB_CS * 64 * NV; DY32: dy is fp32 (else bf16)
+template <int N>  // one row sum over the N slice cells of a row group ([N][2] floats): pairwise, in a fixed order
+__device__ __forceinline__ float cell_sum(const float* c) {
+  if constexpr (N == 1) return c[0];
+  else return cell_sum<N / 2>(c) + cell_sum<N / 2>(c + N);
+}
+
+// float4 chunks per lane inside a slice: d/4 <= CS * 64 * NV; DY32: dy is fp32 (else bf16); RG x CS = 16 waves
+template <int NV, bool DY32, int RG = LNB_RG, int CS = LNB_CS>
 __global__ __launch_bounds__(1024) void ln_bwd_kernel(const void* __restrict__ dy, int64_t lddy,
                                                       const float* __restrict__ x, int64_t ldx,
                                                       const float* __restrict__ w, const float* __restrict__ mean,
@@ -83,10 +95,10 @@ __global__ __launch_bounds__(1024) void ln_bwd_kernel(const void* __restrict__ d
   const DropParams drop = with_salt(drop_);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* slab = (float*)smem;                      // [nslab][d]: dw, db (, column sums of the masked copy)
-  float* cell = slab + nslab * d;                  // [2 buffers][LNB_RG][LNB_CS][2]
+  float* cell = slab + nslab * d;                  // [2 buffers][RG][CS][2]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int rg = wave >> 2, cs = wave & 3;
-  const int nq = d >> 2, qs = (nq + LNB_CS - 1) / LNB_CS;
+  const int rg = wave / CS, cs = wave % CS;
+  const int nq = d >> 2, qs = (nq + CS - 1) / CS;
   const int q0 = cs * qs, q1 = min(nq, q0 + qs);
   float4 pw[NV], pb[NV], pc[NV], ww[NV];
 #pragma unroll
@@ -118,9 +130,9 @@ __global__ __launch_bounds__(1024) void ln_bwd_kernel(const void* __restrict__ d
       }
     }
   };
-  constexpr bool PIPE = NV <= 2;      // d <= 2048: the second register set fits (no spills at 16 waves per CU); wider rows load in place
-  if (PIPE) prefetch(blockIdx.x * LNB_RG + rg);
-  for (int base = blockIdx.x * LNB_RG; base < rows; base += gridDim.x * LNB_RG, buf ^= 1) {
+  constexpr bool PIPE = NV <= 2;      // slices of <= 128 float4 (every instantiation built): the second register set fits (no spills at 16 waves per CU); wider slices load in place
+  if (PIPE) prefetch(blockIdx.x * RG + rg);
+  for (int base = blockIdx.x * RG; base < rows; base += gridDim.x * RG, buf ^= 1) {
     const int row = base + rg;
     const bool live = row < rows;
     float g[NV][4], xh[NV][4];
@@ -132,7 +144,7 @@ __global__ __launch_bounds__(1024) void ln_bwd_kernel(const void* __restrict__ d
     for (int t = 0; t < NV; ++t) cur[t] = nxt[t];
     const float mu = nmu;
     rs = nrs;
-    if (PIPE) prefetch(row + gridDim.x * LNB_RG);       // the next row step of this wave: in flight from here on
+    if (PIPE) prefetch(row + gridDim.x * RG);       // the next row step of this wave: in flight from here on
     // in_take > 1: the incoming dx is [rows / in_take, d] and belongs to rows 0, in_take, ..: the others take none
     const bool has_in = dx_in && (in_take <= 1 || row % in_take == 0);
     if (live && dx_in) {                      // this step's incoming dx is only needed behind the barrier: its latency hides under the reductions
@@ -169,11 +181,11 @@ __global__ __launch_bounds__(1024) void ln_bwd_kernel(const void* __restrict__ d
     }
     c1 = wave_sum(c1);
     c2 = wave_sum(c2);
-    float* my = cell + ((buf * LNB_RG + rg) * LNB_CS) * 2;
+    float* my = cell + ((buf * RG + rg) * CS) * 2;
     if (lane == 0) { my[cs * 2] = c1; my[cs * 2 + 1] = c2; }
     __syncthreads();
-    c1 = ((my[0] + my[2]) + (my[4] + my[6])) * inv_d;
-    c2 = ((my[1] + my[3]) + (my[5] + my[7])) * inv_d;
+    c1 = cell_sum<CS>(my) * inv_d;
+    c2 = cell_sum<CS>(my + 1) * inv_d;
     if (live) {
 #pragma unroll
       for (int t = 0; t < NV; ++t) {
@@ -198,8 +210,8 @@ __global__ __launch_bounds__(1024) void ln_bwd_kernel(const void* __restrict__ d
       }
     }
   }
-  // the 4 row groups add their column partials into the slab one after the other
-  for (int r = 0; r < LNB_RG; ++r) {
+  // the row groups add their column partials into the slab one after the other
+  for (int r = 0; r < RG; ++r) {
     if (rg == r) {
 #pragma unroll
       for (int t = 0; t < NV; ++t) {
@@ -316,19 +328,24 @@ extern "C" int afft_layernorm_bwd_take(const void* dy, int64_t lddy, int32_t dy_
   AFFT_CHECK(in_take >= 1 && lddx_in % 4 == 0, "layernorm_bwd: bad in_take / lddx_in");
   AFFT_CHECK(dy && x && mean && rstd && dx_out && partial, "layernorm_bwd: null pointer");
   AFFT_CHECK(d > 0 && d % 4 == 0 && ldx % 4 == 0 && lddy % 4 == 0 && lddx % 4 == 0, "layernorm_bwd: d/ld must be multiples of 4");
-  AFFT_CHECK(d <= 2048, "layernorm_bwd: d=%d exceeds 2048 (the widest stream of the path; the 4096-wide instantiation spilled 101-125 registers and was removed in round 6)", d);
+  AFFT_CHECK(d <= 4096, "layernorm_bwd: d=%d exceeds 4096", d);
   if (rows == 0) return 0;
   AfftKernelScope ktrace(AFFT_K_LN_BWD, rows, d,
                          (int64_t)rows * d * ((dy_dtype == AFFT_F32 ? 4 : 2) + 4 + (dx_in ? 4 : 0) + 4 + (dx_bf16 ? 2 : 0)) + (int64_t)rows * 8, 0, stream);
-  const int qs = (d / 4 + LNB_CS - 1) / LNB_CS;
+  const bool wide = d > LNB_WIDE_D;    // 2 row groups x 8 column slices: NV = 2 up to d = 4096
+  const int rgs = wide ? LNB_WIDE_RG : LNB_RG, css = wide ? LNB_WIDE_CS : LNB_CS;
+  const int qs = (d / 4 + css - 1) / css;
   const int nv = qs <= 64 ? 1 : 2;
+  // the caller's `partial` holds afft_layernorm_bwd_nparts(rows) parts, whichever arrangement runs: the wide one takes the same grid
+  // (a workgroup then runs twice the row steps) and the reduction below is told that number
   const int grid = afft_layernorm_bwd_nparts(rows);
   const int nslab = dcol ? 3 : 2;
   const DropParams drop = make_drop(copy_drop);
-  const size_t lds = (size_t)nslab * d * sizeof(float) + 2 * LNB_RG * LNB_CS * 2 * sizeof(float);
+  const size_t lds = (size_t)nslab * d * sizeof(float) + 2 * rgs * css * 2 * sizeof(float);
   AFFT_CHECK(dy_dtype == AFFT_F32 || dy_dtype == AFFT_BF16, "layernorm_bwd: dy is fp32 or bf16");
-#define LN_BWD(NV, F) hipLaunchKernelGGL((ln_bwd_kernel<NV, F>), dim3(grid), dim3(1024), lds, stream, dy, lddy, x, ldx, w, mean, rstd, rows, d, dx_in, dx_out, lddx, (bf16_t*)dx_bf16, drop, nslab, partial, lddx_in, in_take)
-  if (dy_dtype == AFFT_F32) { if (nv == 1) LN_BWD(1, true); else LN_BWD(2, true); }
+#define LN_BWD(...) hipLaunchKernelGGL((ln_bwd_kernel<__VA_ARGS__>), dim3(grid), dim3(1024), lds, stream, dy, lddy, x, ldx, w, mean, rstd, rows, d, dx_in, dx_out, lddx, (bf16_t*)dx_bf16, drop, nslab, partial, lddx_in, in_take)
+  if (wide) { if (dy_dtype == AFFT_F32) LN_BWD(2, true, LNB_WIDE_RG, LNB_WIDE_CS); else LN_BWD(2, false, LNB_WIDE_RG, LNB_WIDE_CS); }
+  else if (dy_dtype == AFFT_F32) { if (nv == 1) LN_BWD(1, true); else LN_BWD(2, true); }
   else { if (nv == 1) LN_BWD(1, false); else LN_BWD(2, false); }
 #undef LN_BWD
   AFFT_LAUNCH_CHECK();

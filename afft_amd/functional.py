@@ -1425,6 +1425,17 @@ class WeightedSum(torch.autograd.Function):
 
 
 # --------------------------------------------------------------------------- standalone LayerNorm (final norms)
+LN_MAX_WIDTH = 4096      # afft_layernorm_fwd / afft_layernorm_bwd: rows of up to 4096 columns, a multiple of 4 (16-byte accesses)
+
+
+def check_ln_width(width: int, what: str):
+    """Called by the constructors of the modules that normalise rows of `width` columns: what the LayerNorm kernels do not take is an
+    error where the model is built, not a library check inside backward()."""
+    if width > LN_MAX_WIDTH or width % 4 != 0:
+        raise ValueError(f"{what}: LayerNorm over {width} columns is not built: the width must be a multiple of 4 and at most "
+                         f"{LN_MAX_WIDTH}")
+
+
 class LayerNormRows(torch.autograd.Function):
     """y[r] = LN(X[r*stride_rows]) for r < rows: stride_rows = S picks token 0 of every frame
     (models/fusion.py:362-364), stride_rows = 1 is a plain LayerNorm (GPT-2 ln_f, CA-Fuser norm)."""

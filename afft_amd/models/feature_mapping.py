@@ -25,6 +25,10 @@ class _HipLinear(nn.Linear):
 
 
 class _HipLayerNorm(nn.LayerNorm):
+    def __init__(self, normalized_shape, *args, **kwargs):
+        F_.check_ln_width(int(normalized_shape), "feature mapping")
+        super().__init__(normalized_shape, *args, **kwargs)
+
     def forward(self, x):
         shp = x.shape
         y = F_.LayerNormRows.apply(x.reshape(-1, shp[-1]).float().contiguous(), self.weight, self.bias, self.eps, 1)

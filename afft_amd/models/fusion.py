@@ -93,6 +93,7 @@ class ModalTokenCMFuser(nn.Module):
             Block(dim=dim, num_heads=num_heads, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, qk_scale=qk_scale,
                   drop=drop_rate, attn_drop=attn_drop_rate, drop_path=dpr[i], act_layer=act_layer,
                   norm_layer=norm_layer) for i in range(depth)])
+        F_.check_ln_width(dim, type(self).__name__)
         self.norm = norm_layer(dim)
         self.num_mods = len(modalities) + 1  # + the modality-agnostic token
         self.modality_embedding = nn.Parameter(torch.zeros(1, self.num_mods, dim)) if modal_encoding else None
@@ -166,6 +167,7 @@ class CMFuser(nn.Module):
             Block(dim=dim, num_heads=num_heads, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, qk_scale=qk_scale,
                   drop=drop_rate, attn_drop=attn_drop_rate, drop_path=dpr[i], act_layer=act_layer,
                   norm_layer=norm_layer) for i in range(depth)])
+        F_.check_ln_width(dim, type(self).__name__)
         self.norm = norm_layer(dim)
         self.embd_drop = nn.Dropout(embd_drop_rate)
         self.cross_attn = cross_attn
@@ -211,6 +213,7 @@ class TemporalCMFuser(nn.Module):
             Block(dim=dim, num_heads=num_heads, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, qk_scale=qk_scale,
                   drop=drop_rate, attn_drop=attn_drop_rate, drop_path=dpr[i], act_layer=act_layer,
                   norm_layer=norm_layer) for i in range(depth)])
+        F_.check_ln_width(dim, type(self).__name__)
         self.norm = norm_layer(dim)
         # frame position embedding and modality embedding
         self.num_mods = len(modalities) + 1 if frame_level_token else len(modalities)
@@ -277,6 +280,7 @@ class TemporalCrossAttentFuser(nn.Module):
             DecoderBlock(dim=dim, mem_dim=None, num_heads=num_heads, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias,
                          qk_scale=qk_scale, drop=drop_rate, attn_drop=attn_drop_rate, drop_path=dpr[i],
                          act_layer=act_layer, norm_layer=norm_layer) for i in range(depth)])
+        F_.check_ln_width(dim, type(self).__name__)
         self.norm = norm_layer(dim)
         self.embd_drop = nn.Dropout(embd_drop_rate)
         self.position_embeddings = nn.Embedding(max_position_embeddings, dim)

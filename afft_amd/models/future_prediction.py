@@ -67,6 +67,7 @@ class GPT2MLP(nn.Module):
 class GPT2Block(nn.Module):
     def __init__(self, n_embd, n_head, attn_pdrop, resid_pdrop, eps=1e-5):
         super().__init__()
+        F_.check_ln_width(n_embd, "GPT2Block")
         self.ln_1 = nn.LayerNorm(n_embd, eps=eps)
         self.attn = GPT2Attention(n_embd, n_head, attn_pdrop, resid_pdrop)
         self.ln_2 = nn.LayerNorm(n_embd, eps=eps)
@@ -89,6 +90,7 @@ class GPT2Model(nn.Module):
     def __init__(self, n_embd, n_layer, n_head, n_positions=1024, embd_pdrop=0.1, resid_pdrop=0.1, attn_pdrop=0.1,
                  layer_norm_epsilon=1e-5):
         super().__init__()
+        F_.check_ln_width(n_embd, "GPT2Model")
         self.embed_dim = n_embd
         self.wpe = nn.Embedding(n_positions, n_embd)
         self.wpe.weight._afft_fp32_table = True      # read as fp32 rows (AddRowTable), never a GEMM image: parallel.FlatParams.owns_image

@@ -230,7 +230,8 @@ def layernorm_bwd(dy: Tensor, x: Tensor, w: Optional[Tensor], mean: Tensor, rstd
                   db: Optional[Tensor] = None, accumulate: bool = True, copy_drop: Optional["L.Dropout"] = None,
                   dcol: Optional[Tensor] = None, dcol_accumulate: bool = True) -> Tensor:
     """dw / db (optional) receive the weight / bias gradients: added to when `accumulate`, else overwritten.
-    dx_bf16 (optional): bf16 copy of dx_out with the mask `copy_drop` replayed; dcol (optional): its column sums."""
+    dx_bf16 (optional): bf16 copy of dx_out with the mask `copy_drop` replayed; dcol (optional): its column sums.
+    Rows of up to 4096 columns, a multiple of 4 (the forward's range; beyond 2048 a kernel arrangement of its own runs)."""
     rows, d = x.shape
     partial = ln_partial(rows, d, x.device)
     lddx = _rowmajor(dx_out, "dx_out")
@@ -243,6 +244,27 @@ def layernorm_bwd(dy: Tensor, x: Tensor, w: Optional[Tensor], mean: Tensor, rstd
                                        C.byref(copy_drop) if copy_drop is not None else None,
                                        _p(dw), _p(db), 1 if accumulate else 0, _p(dcol), 1 if dcol_accumulate else 0,
                                        _p(partial), _stream()), "layernorm_bwd")
+    return dx_out
+
+
+def layernorm_bwd_take(dy: Tensor, x: Tensor, w: Optional[Tensor], mean: Tensor, rstd: Tensor, dx_out: Tensor,
+                       dx_in: Tensor, in_take: int, dx_bf16: Optional[Tensor] = None, dw: Optional[Tensor] = None,
+                       db: Optional[Tensor] = None, accumulate: bool = True, copy_drop: Optional["L.Dropout"] = None,
+                       dcol: Optional[Tensor] = None, dcol_accumulate: bool = True) -> Tensor:
+    """layernorm_bwd whose incoming residual gradient dx_in is [rows / in_take, d] and belongs to rows 0, in_take, 2 in_take, ..:
+    the other rows take none (afft_layernorm_bwd_take).  The same widths as layernorm_bwd."""
+    rows, d = x.shape
+    assert in_take >= 1 and rows % in_take == 0 and tuple(dx_in.shape) == (rows // in_take, d)
+    partial = ln_partial(rows, d, x.device)
+    lddx = _rowmajor(dx_out, "dx_out")
+    if dx_bf16 is not None:
+        assert dx_bf16.dtype == torch.bfloat16 and _rowmajor(dx_bf16, "dx_bf16") == lddx
+    L.check(L.lib().afft_layernorm_bwd_take(_p(dy), _rowmajor(dy, "dy"), _dt(dy), _p(x), _rowmajor(x, "x"), _p(w),
+                                            _p(mean), _p(rstd), rows, d, _p(dx_in), _rowmajor(dx_in, "dx_in"), in_take,
+                                            _p(dx_out), lddx, _p(dx_bf16),
+                                            C.byref(copy_drop) if copy_drop is not None else None,
+                                            _p(dw), _p(db), 1 if accumulate else 0, _p(dcol), 1 if dcol_accumulate else 0,
+                                            _p(partial), _stream()), "layernorm_bwd_take")
     return dx_out
 
 

@@ -223,7 +223,9 @@ int afft_layernorm_fwd_split(const float* x, int64_t ldx, const float* w, const 
  * on it: the operand of the dgrad/wgrad GEMMs of the sub-layer that produced this LayerNorm's input, whose output
  * dropout it is.  dcol (optional, fp32 [d]) receives the column sums of that masked copy (= that sub-layer's output
  * bias gradient), written or added to per dcol_accumulate.
- * partial: fp32 workspace of at least 3*d*afft_layernorm_bwd_nparts(rows) floats. */
+ * partial: fp32 workspace of at least 3*d*afft_layernorm_bwd_nparts(rows) floats.
+ * Widths: d a multiple of 4 up to 4096, forward and backward alike (afft_layernorm_bwd_take too; rows of more than 2048 columns
+ * run a kernel arrangement of their own, with the same arguments, the same workspace and the same fixed summation order). */
 int afft_layernorm_bwd_nparts(int32_t rows);
 int afft_layernorm_bwd(const void* dy, int64_t lddy, int32_t dy_dtype, const float* x, int64_t ldx,
                        const float* w, const float* mean, const float* rstd,
