@@ -177,6 +177,7 @@ _SIGS = {
     "afft_attention_long_fwd_bias": ([vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, i32, f32, vp, i64, i64, i64, f32, C.c_uint32,
                                       vp, i64, vp, vp], C.c_int),
     "afft_attention_bias_bwd": ([vp, i64, vp, i64, i32, vp, i32, i32, i32, i32, f32, C.c_uint32, vp, i64, i64, i64, vp, vp], C.c_int),
+    "afft_attention_plan_for": ([i32, i32, i32, i32, i32, i32, i32], C.c_int),
     "afft_softmax_ce": ([vp, i64, i32, i32, vp, vp, i64, vp, f32, vp, vp, vp, i64, i32, vp, vp], C.c_int),
     "afft_loss_reduce": ([C.POINTER(vp), C.POINTER(i64), C.POINTER(f32), i32, vp, vp, vp], C.c_int),
     "afft_loss_reduce_bwd_ok": ([C.POINTER(vp), C.POINTER(i64), C.POINTER(f32), i32, vp, vp, vp, vp], C.c_int),

@@ -4,18 +4,14 @@
 // the scores are produced.  HBM-bound by construction (reads q,k,v once
 // through L1/L2, writes out once): attention is < 0.2 % of the path's FLOPs.
 //   softmax(q k^T * hd^-0.5 + mask) v : models/transformerblock.py:24-33,64-73 ; HF GPT-2 eager attention.
-#include <stdlib.h>
+// The mask rule is attention_tiles.h's; which kernel runs a call is attn_plan.h's decision.  The nine entry points' shared body
+// (run_attention) and the short ones are at the end of this file.
+#include "attention_tiles.h"
+#include "attn_plan.h"
 
-#include "common.h"
+using namespace afft_attn_detail;
 
 namespace {
-
-constexpr int LMAX = 128;
-
-__device__ __forceinline__ bool masked(int mask, int period, int i, int j) {
-  return (mask == AFFT_MASK_DIAG && i == j) || (mask == AFFT_MASK_CAUSAL && j > i) ||
-         (mask == AFFT_MASK_BLOCKCAUSAL && (j % period) > (i % period));
-}
 
 template <typename T, int LM>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const T* __restrict__ q, int64_t ldq, const T* __restrict__ k,
@@ -199,181 +195,118 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const T* __restrict__ dou
 }
 
 
-
+// one instantiation pair: forward or backward by the call's direction, LDS bytes and grid from the plan
 template <typename T, int LM>
-int launch_fwd(dim3 grid, hipStream_t stream, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
-               int L, int H, int hd, float scale, int mask, int period, const DropParams& dp, void* out, int64_t ldo,
-               float* probs, const float* addm = nullptr, int64_t sb = 0, int64_t sh = 0, int64_t si = 0) {
-  constexpr size_t lds = sizeof(float) * LM * (LM + 1);
-  auto kern = attn_fwd_kernel<T, LM>;
-  static std::atomic<uint64_t> attr_done{0};
-  if (lds > 48 * 1024)
-    if (int rc = afft_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, &attr_done)) return rc;
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, (const T*)q, ldq, (const T*)k, ldk, (const T*)v, ldv, L, H, hd, scale,
-                     mask, period, dp.thresh, dp.key, dp.inv_keep, dp.salt, (T*)out, ldo, probs, addm, sb, sh, si);
+int launch_short(const AttnCall& c, const AttnPlan& p, hipStream_t stream) {
+  afft_dropout_t dd = {c.drop_p, c.drop_key, 0.f, 0u, 1};
+  const DropParams dp = make_drop(&dd);
+  const dim3 grid(p.grid);
+  static std::atomic<uint64_t> fwd_attr{0}, bwd_attr{0};
+  if (c.dir == kFwd) {
+    auto kern = attn_fwd_kernel<T, LM>;
+    if (p.lds > 48 * 1024)
+      if (int rc = afft_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), p.lds, &fwd_attr)) return rc;
+    hipLaunchKernelGGL(kern, grid, dim3(256), p.lds, stream, (const T*)c.q, c.ldq, (const T*)c.k, c.ldk, (const T*)c.v, c.ldv, c.L, c.H, c.hd,
+                       c.scale, c.mask, c.period, dp.thresh, dp.key, dp.inv_keep, dp.salt, (T*)c.out, c.ldo, c.probs, c.bias, c.sb, c.sh, c.si);
+  } else {
+    auto kern = attn_bwd_kernel<T, LM>;
+    if (p.lds > 48 * 1024)
+      if (int rc = afft_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), p.lds, &bwd_attr)) return rc;
+    hipLaunchKernelGGL(kern, grid, dim3(256), p.lds, stream, (const T*)c.dout, c.lddo, (const T*)c.q, c.ldq, (const T*)c.k, c.ldk, (const T*)c.v,
+                       c.ldv, c.probs, c.L, c.H, c.hd, c.scale, dp.thresh, dp.key, dp.inv_keep, dp.salt, (T*)c.dq, c.lddq, (T*)c.dk, c.lddk,
+                       (T*)c.dv, c.lddv);
+  }
   return 0;
 }
-template <typename T, int LM>
-int launch_bwd(dim3 grid, hipStream_t stream, const void* dout, int64_t lddo, const void* q, int64_t ldq, const void* k,
-               int64_t ldk, const void* v, int64_t ldv, const float* probs, int L, int H, int hd, float scale,
-               const DropParams& dp, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv) {
-  constexpr size_t lds = sizeof(float) * 2 * LM * (LM + 1);
-  auto kern = attn_bwd_kernel<T, LM>;
-  static std::atomic<uint64_t> attr_done{0};
-  if (lds > 48 * 1024)
-    if (int rc = afft_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, &attr_done)) return rc;
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, (const T*)dout, lddo, (const T*)q, ldq, (const T*)k, ldk, (const T*)v, ldv,
-                     probs, L, H, hd, scale, dp.thresh, dp.key, dp.inv_keep, dp.salt, (T*)dq, lddq, (T*)dk, lddk, (T*)dv, lddv);
-  return 0;
+template <typename T>
+int launch_short_lm(const AttnCall& c, const AttnPlan& p, hipStream_t stream) {
+  return p.p0 == 32 ? launch_short<T, 32>(c, p, stream) : p.p0 == 64 ? launch_short<T, 64>(c, p, stream) : launch_short<T, 128>(c, p, stream);
 }
 
 }  // namespace
 
-// bf16 MFMA path (attention_mfma.hip); returns -1 when the shape is not handled
-int afft_attention_mfma(bool backward, const void* dout, int64_t lddo, const void* q, int64_t ldq, const void* k,
-                        int64_t ldk, const void* v, int64_t ldv, float* probs, int nseq, int L, int H, int hd,
-                        float scale, int mask, float drop_p, unsigned drop_key, void* out, int64_t ldo, void* dq,
-                        int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv, hipStream_t stream,
-                        int planes = 0, int64_t in_lo = 0, int64_t out_lo = 0, void* out_b = nullptr, int64_t ldob = 0, void* out_lo8 = nullptr);
-static bool use_mfma_attention() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("AFFT_ATTN_GENERIC"); v = (e && e[0] == '1') ? 0 : 1; }
-  return v == 1;
+int launch_attention_generic(const AttnCall& c, const AttnPlan& p, hipStream_t stream) {
+  if (int rc = c.dtype == AFFT_F32 ? launch_short_lm<float>(c, p, stream) : launch_short_lm<bf16_t>(c, p, stream)) return rc;
+  AFFT_LAUNCH_CHECK();
+  return 0;
+}
+
+int run_attention(const char* who, const AttnCall& c, unsigned which, unsigned late, hipStream_t stream) {
+  if (int rc = check_attention(who, c, which)) return rc;
+  if (c.nseq == 0) return 0;
+  const AttnTraffic t = attention_traffic(c);
+  AfftKernelScope ktrace(c.dir == kFwd ? AFFT_K_ATTN_FWD : AFFT_K_ATTN_BWD, c.nseq * c.L, c.H * c.hd, t.bytes, t.flops, stream);
+  if (int rc = check_attention(who, c, late)) return rc;
+  const AttnPlan p = plan_attention(c);
+  AFFT_CHECK(!p.refusal[0], "%s", p.refusal);
+  if (p.family == kGenericShort) return launch_attention_generic(c, p, stream);
+  return p.family <= kSlicedBwd ? launch_attention_mfma(c, p, stream) : launch_attention_long(c, p, stream);
+}
+
+// the plan of a dense problem as its arguments describe it: one sequence, one head, rows of hd elements (rounded up to whole
+// 16-byte units) at 16-byte aligned addresses -- or, pitch_alignment_ok = 0, rows that no 16-byte load can take
+extern "C" int afft_attention_plan_for(int32_t direction, int32_t dtype, int32_t L, int32_t hd, int32_t planes, int32_t in_lo,
+                                       int32_t pitch_alignment_ok) {
+  const int64_t ld = (hd + 7) / 8 * 8 + (pitch_alignment_ok ? 0 : 1);
+  void* x = reinterpret_cast<void*>(uintptr_t{4096});      // never dereferenced
+  AttnCall c = direction == kFwd ? attn_fwd_call(x, ld, x, ld, x, ld, dtype, 1, L, 1, hd, 1.f, 0.f, 0u, x, ld, nullptr)
+                                 : attn_bwd_call(x, ld, x, ld, x, ld, x, ld, dtype, (const float*)x, 1, L, 1, hd, 1.f, 0.f, 0u, x, ld, x, ld, x, ld);
+  c.dir = direction;
+  if (direction == kBiasBwd) { c.q = c.k = nullptr; c.dq = c.dk = c.dv = nullptr; c.ldq = c.ldk = c.lddq = c.lddk = c.lddv = 0; }
+  c.planes = planes != 0;
+  c.in_lo = in_lo ? 8 * ld : 0;
+  const AttnPlan p = direction >= kFwd && direction <= kBiasBwd ? plan_attention(c) : AttnPlan{};
+  if (!p.family) { afft_set_error("%s", p.refusal[0] ? p.refusal : "afft_attention_plan_for: bad direction"); return -1; }
+  return p.family * 10000 + p.p0 * 10 + p.p1;
 }
 
 extern "C" int afft_attention_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
                                   int32_t dtype, int32_t nseq, int32_t L, int32_t H, int32_t hd, float scale,
                                   int32_t mask, int32_t mask_period, float drop_p, uint32_t drop_key, void* out,
                                   int64_t ldo, float* probs, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  AFFT_CHECK(q && k && v && out, "attention_fwd: null pointer");
-  AFFT_CHECK(L >= 1 && L <= LMAX, "attention_fwd: sequence length %d outside 1..%d", L, LMAX);
-  AFFT_CHECK(mask >= AFFT_MASK_NONE && mask <= AFFT_MASK_BLOCKCAUSAL, "attention_fwd: bad mask %d", mask);
-  AFFT_CHECK(mask != AFFT_MASK_BLOCKCAUSAL || (mask_period >= 1 && L % mask_period == 0),
-             "attention_fwd: block-causal mask needs a period that divides L (L=%d, period=%d)", L, mask_period);
-  AFFT_CHECK(!(mask == AFFT_MASK_DIAG && L == 1), "attention_fwd: diagonal mask with L=1 masks every key");
-  AFFT_CHECK(drop_p >= 0.f && drop_p < 1.f, "attention_fwd: dropout p outside [0,1)");
-  AFFT_CHECK(hd >= 1 && hd <= 1024, "attention_fwd: head dimension %d outside 1..1024", hd);
-  if (nseq == 0) return 0;
-  const int64_t es_ = dtype == AFFT_F32 ? 4 : 2, rw_ = (int64_t)nseq * L * H * hd, pb_ = probs ? (int64_t)nseq * H * L * L * 4 : 0;
-  AfftKernelScope ktrace(AFFT_K_ATTN_FWD, nseq * L, H * hd, 4 * es_ * rw_ + pb_, 4 * (int64_t)nseq * H * L * L * hd, stream);
-  if (dtype == AFFT_BF16 && use_mfma_attention()) {
-    const int rc = afft_attention_mfma(false, nullptr, 0, q, ldq, k, ldk, v, ldv, probs, nseq, L, H, hd, scale,
-                                       mask | (mask == AFFT_MASK_BLOCKCAUSAL ? mask_period << 8 : 0),
-                                       drop_p, drop_key, out, ldo, nullptr, 0, nullptr, 0, nullptr, 0, stream);
-    if (rc >= 0) return rc;
-  }
-  afft_dropout_t dd = {drop_p, drop_key, 0.f, 0u, 1};
-  const DropParams dp = make_drop(&dd);
-  const dim3 grid(nseq * H);
-  AFFT_CHECK(dtype == AFFT_F32 || dtype == AFFT_BF16, "attention_fwd: bad dtype %d", dtype);
-  int rc;
-#define FWD(T, LM) launch_fwd<T, LM>(grid, stream, q, ldq, k, ldk, v, ldv, L, H, hd, scale, mask, mask_period, dp, out, ldo, probs)
-  if (dtype == AFFT_F32) rc = L <= 32 ? FWD(float, 32) : L <= 64 ? FWD(float, 64) : FWD(float, 128);
-  else rc = L <= 32 ? FWD(bf16_t, 32) : L <= 64 ? FWD(bf16_t, 64) : FWD(bf16_t, 128);
-#undef FWD
-  if (rc) return rc;
-  AFFT_LAUNCH_CHECK();
-  return 0;
+  AttnCall c = attn_fwd_call(q, ldq, k, ldk, v, ldv, dtype, nseq, L, H, hd, scale, drop_p, drop_key, out, ldo, probs);
+  c.mask = mask; c.period = mask_period;
+  return run_attention("attention_fwd", c, kChkPtrs | kLenShort | kChkMask | kChkDiag | kChkDrop | kChkHd, kChkDtype, (hipStream_t)stream_);
 }
 
-// the arbitrary additive bias, generic kernel: element (seq, h, i, j) at bias[seq*sb + h*sh + i*si + j]
-static int attention_fwd_bias_impl(const char* who, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
-                                   int32_t dtype, int32_t nseq, int32_t L, int32_t H, int32_t hd, float scale, const float* bias,
-                                   int64_t sb, int64_t sh, int64_t si, float drop_p, uint32_t drop_key, void* out, int64_t ldo,
-                                   float* probs, hipStream_t stream) {
-  AFFT_CHECK(q && k && v && out && bias, "%s: null pointer", who);
-  AFFT_CHECK(L >= 1 && L <= LMAX, "%s: sequence length %d outside 1..%d", who, L, LMAX);
-  AFFT_CHECK(drop_p >= 0.f && drop_p < 1.f, "%s: dropout p outside [0,1)", who);
-  AFFT_CHECK(hd >= 1 && hd <= 1024, "%s: head dimension %d outside 1..1024", who, hd);
-  AFFT_CHECK(dtype == AFFT_F32 || dtype == AFFT_BF16, "%s: bad dtype %d", who, dtype);
-  if (nseq == 0) return 0;
-  const int64_t es_ = dtype == AFFT_F32 ? 4 : 2, rw_ = (int64_t)nseq * L * H * hd, pb_ = probs ? (int64_t)nseq * H * L * L * 4 : 0;
-  AfftKernelScope ktrace(AFFT_K_ATTN_FWD, nseq * L, H * hd, 4 * es_ * rw_ + pb_, 4 * (int64_t)nseq * H * L * L * hd, stream);
-  afft_dropout_t dd = {drop_p, drop_key, 0.f, 0u, 1};
-  const DropParams dp = make_drop(&dd);
-  const dim3 grid(nseq * H);
-  int rc;
-#define FWD(T, LM) launch_fwd<T, LM>(grid, stream, q, ldq, k, ldk, v, ldv, L, H, hd, scale, AFFT_MASK_NONE, 0, dp, out, ldo, probs, bias, sb, sh, si)
-  if (dtype == AFFT_F32) rc = L <= 32 ? FWD(float, 32) : L <= 64 ? FWD(float, 64) : FWD(float, 128);
-  else rc = L <= 32 ? FWD(bf16_t, 32) : L <= 64 ? FWD(bf16_t, 64) : FWD(bf16_t, 128);
-#undef FWD
-  if (rc) return rc;
-  AFFT_LAUNCH_CHECK();
-  return 0;
+// the arbitrary additive bias: element (seq, h, i, j) at bias[seq*sb + h*sh + i*si + j]; the generic kernel at every shape
+static int attention_fwd_bias_impl(const char* who, const AttnCall& c, hipStream_t stream) {
+  return run_attention(who, c, kChkPtrs | kChkBias | kLenShort | kChkDrop | kChkHd | kChkDtype, 0, stream);
 }
 
 extern "C" int afft_attention_fwd_table(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
                                         int32_t dtype, int32_t nseq, int32_t L, int32_t H, int32_t hd, float scale,
                                         const float* mask_table, float drop_p, uint32_t drop_key, void* out, int64_t ldo,
                                         float* probs, void* stream_) {
-  return attention_fwd_bias_impl("attention_fwd_table", q, ldq, k, ldk, v, ldv, dtype, nseq, L, H, hd, scale, mask_table, 0, 0, L,
-                                 drop_p, drop_key, out, ldo, probs, (hipStream_t)stream_);
+  AttnCall c = attn_fwd_call(q, ldq, k, ldk, v, ldv, dtype, nseq, L, H, hd, scale, drop_p, drop_key, out, ldo, probs);
+  c.bias = mask_table; c.si = L;
+  return attention_fwd_bias_impl("attention_fwd_table", c, (hipStream_t)stream_);
 }
 
 extern "C" int afft_attention_fwd_bias(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
                                        int32_t dtype, int32_t nseq, int32_t L, int32_t H, int32_t hd, float scale,
                                        const float* bias, int64_t sb, int64_t sh, int64_t si, float drop_p, uint32_t drop_key,
                                        void* out, int64_t ldo, float* probs, void* stream_) {
-  AFFT_CHECK(sb >= 0 && sh >= 0 && si >= 0, "attention_fwd_bias: negative bias stride (sb=%lld, sh=%lld, si=%lld)", (long long)sb,
-             (long long)sh, (long long)si);
-  AFFT_CHECK((((uintptr_t)bias) & 3) == 0, "attention_fwd_bias: bias pointer %p is not 4-byte aligned", (const void*)bias);
-  return attention_fwd_bias_impl("attention_fwd_bias", q, ldq, k, ldk, v, ldv, dtype, nseq, L, H, hd, scale, bias, sb, sh, si, drop_p,
-                                 drop_key, out, ldo, probs, (hipStream_t)stream_);
+  AttnCall c = attn_fwd_call(q, ldq, k, ldk, v, ldv, dtype, nseq, L, H, hd, scale, drop_p, drop_key, out, ldo, probs);
+  c.bias = bias; c.sb = sb; c.sh = sh; c.si = si;
+  if (int rc = check_attention("attention_fwd_bias", c, kChkBiasArgs)) return rc;
+  return attention_fwd_bias_impl("attention_fwd_bias", c, (hipStream_t)stream_);
 }
 
 extern "C" int afft_attention_fwd_split(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, int64_t in_lo,
                                         int32_t nseq, int32_t L, int32_t H, int32_t hd, float scale, int32_t mask, int32_t mask_period,
                                         float drop_p, uint32_t drop_key, void* out_hi, int64_t ldo, int64_t out_lo, void* out_bf16,
                                         int64_t ldob, float* probs, void* out_lo8, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  AFFT_CHECK(q && k && v && out_hi, "attention_fwd_split: null pointer");
-  AFFT_CHECK(L >= 1 && L <= 64, "attention_fwd_split: sequence length %d outside 1..64 (MFMA path only)", L);
-  AFFT_CHECK(mask >= AFFT_MASK_NONE && mask <= AFFT_MASK_BLOCKCAUSAL, "attention_fwd_split: bad mask %d", mask);
-  AFFT_CHECK(mask != AFFT_MASK_BLOCKCAUSAL || (mask_period >= 1 && L % mask_period == 0),
-             "attention_fwd_split: block-causal mask needs a period that divides L (L=%d, period=%d)", L, mask_period);
-  AFFT_CHECK(!(mask == AFFT_MASK_DIAG && L == 1), "attention_fwd_split: diagonal mask with L=1 masks every key");
-  AFFT_CHECK(drop_p >= 0.f && drop_p < 1.f, "attention_fwd_split: dropout p outside [0,1)");
-  AFFT_CHECK(in_lo >= 0, "attention_fwd_split: in_lo is the distance to the inputs' lo planes (0: one fp16 plane each)");
-  AFFT_CHECK(!out_lo8 || (out_lo == 0 && (((uintptr_t)out_lo8) & 3) == 0), "attention_fwd_split: out_lo8 excludes out_lo and must be 4-byte aligned");
-  if (nseq == 0) return 0;
-  const int64_t rw_ = (int64_t)nseq * L * H * hd, pb_ = probs ? (int64_t)nseq * H * L * L * 4 : 0;
-  AfftKernelScope ktrace(AFFT_K_ATTN_FWD, nseq * L, H * hd, (3 * (in_lo ? 4 : 2) + (out_lo ? 4 : out_lo8 ? 3 : 2) + (out_bf16 ? 2 : 0)) * rw_ + pb_,
-                         3 * 4 * (int64_t)nseq * H * L * L * hd, stream);
-  const int rc = afft_attention_mfma(false, nullptr, 0, q, ldq, k, ldk, v, ldv, probs, nseq, L, H, hd, scale,
-                                     mask | (mask == AFFT_MASK_BLOCKCAUSAL ? mask_period << 8 : 0), drop_p, drop_key, out_hi, ldo,
-                                     nullptr, 0, nullptr, 0, nullptr, 0, stream, 1, in_lo, out_lo, out_bf16, ldob, out_lo8);
-  AFFT_CHECK(rc >= 0, "attention_fwd_split: shape not handled by the MFMA path (hd %d must be a multiple of 64 and <= 1024, 16-byte aligned rows)", hd);
-  return rc;
+  AttnCall c = attn_fwd_call(q, ldq, k, ldk, v, ldv, AFFT_F16, nseq, L, H, hd, scale, drop_p, drop_key, out_hi, ldo, probs);
+  c.mask = mask; c.period = mask_period;
+  c.planes = 1; c.in_lo = in_lo; c.out_lo = out_lo; c.out_b = out_bf16; c.ldob = ldob; c.out_lo8 = out_lo8;
+  return run_attention("attention_fwd_split", c, kChkPtrs | kLenSplit | kChkMask | kChkDiag | kChkDrop | kChkPlanes, 0, (hipStream_t)stream_);
 }
 
 extern "C" int afft_attention_bwd(const void* dout, int64_t lddo, const void* q, int64_t ldq, const void* k, int64_t ldk,
                                   const void* v, int64_t ldv, int32_t dtype, const float* probs, int32_t nseq, int32_t L,
                                   int32_t H, int32_t hd, float scale, float drop_p, uint32_t drop_key, void* dq,
                                   int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  AFFT_CHECK(dout && q && k && v && probs && dq && dk && dv, "attention_bwd: null pointer");
-  AFFT_CHECK(L >= 1 && L <= LMAX, "attention_bwd: sequence length %d outside 1..%d", L, LMAX);
-  AFFT_CHECK(drop_p >= 0.f && drop_p < 1.f, "attention_bwd: dropout p outside [0,1)");
-  AFFT_CHECK(hd >= 1 && hd <= 1024, "attention_bwd: head dimension %d outside 1..1024", hd);
-  if (nseq == 0) return 0;
-  const int64_t es_ = dtype == AFFT_F32 ? 4 : 2, rw_ = (int64_t)nseq * L * H * hd, pb_ = (int64_t)nseq * H * L * L * 4;
-  AfftKernelScope ktrace(AFFT_K_ATTN_BWD, nseq * L, H * hd, 7 * es_ * rw_ + pb_, 8 * (int64_t)nseq * H * L * L * hd, stream);
-  if (dtype == AFFT_BF16 && use_mfma_attention()) {
-    const int rc = afft_attention_mfma(true, dout, lddo, q, ldq, k, ldk, v, ldv, const_cast<float*>(probs), nseq, L, H, hd,
-                                       scale, 0, drop_p, drop_key, nullptr, 0, dq, lddq, dk, lddk, dv, lddv, stream);
-    if (rc >= 0) return rc;
-  }
-  afft_dropout_t dd = {drop_p, drop_key, 0.f, 0u, 1};
-  const DropParams dp = make_drop(&dd);
-  const dim3 grid(nseq * H);
-  AFFT_CHECK(dtype == AFFT_F32 || dtype == AFFT_BF16, "attention_bwd: bad dtype %d", dtype);
-  int rc;
-#define BWD(T, LM) launch_bwd<T, LM>(grid, stream, dout, lddo, q, ldq, k, ldk, v, ldv, probs, L, H, hd, scale, dp, dq, lddq, dk, lddk, dv, lddv)
-  if (dtype == AFFT_F32) rc = L <= 32 ? BWD(float, 32) : L <= 64 ? BWD(float, 64) : BWD(float, 128);
-  else rc = L <= 32 ? BWD(bf16_t, 32) : L <= 64 ? BWD(bf16_t, 64) : BWD(bf16_t, 128);
-#undef BWD
-  if (rc) return rc;
-  AFFT_LAUNCH_CHECK();
-  return 0;
+  const AttnCall c = attn_bwd_call(dout, lddo, q, ldq, k, ldk, v, ldv, dtype, probs, nseq, L, H, hd, scale, drop_p, drop_key, dq, lddq, dk, lddk, dv, lddv);
+  return run_attention("attention_bwd", c, kChkPtrs | kLenShort | kChkDrop | kChkHd, kChkDtype, (hipStream_t)stream_);
 }

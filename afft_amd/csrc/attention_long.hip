@@ -14,21 +14,18 @@
 //
 // fp32 storage: fp32 arithmetic throughout (lanes stride the head dimension, as attention.hip).  bf16 storage with hd % 64 == 0 and
 // 16-byte aligned rows: both primitives on v_mfma_f32_16x16x32_bf16, operands staged in LDS in hd chunks of <= 256 channels with the
-// swizzle of attention_mfma.hip (row fragments by ds_read_b128, transposed fragments by ds_read_b64_tr_b16); any other bf16 shape, or
-// AFFT_ATTN_GENERIC=1, takes the generic form with bf16 loads.
+// swizzle of attention_tiles.h (row fragments by ds_read_b128, transposed fragments by ds_read_b64_tr_b16); any other bf16 shape, or
+// AFFT_ATTN_GENERIC=1, takes the generic form with bf16 loads (attn_plan.h decides; it also holds QT, KB and the length band).
 // Semantics are those of attention.hip: probs = PRE-dropout probabilities, masked entries exactly 0, dropout mask from (key, index).
 // The additive bias of the forward pass is read through element strides (0 = broadcast over batch / head / row: afft_attention_long_fwd_bias);
 // its gradient, for every L from 1 to 512, is the first half of the dQ pass without the score scale plus an ordered sum over the
 // broadcast dimensions (afft_attention_bias_bwd: bias_bwd_ds_kernel, bias_bwd_reduce_kernel).
-#include <stdlib.h>
+#include "attention_tiles.h"
+#include "attn_plan.h"
 
-#include "common.h"
+using namespace afft_attn_detail;
 
 namespace {
-
-constexpr int LLO = 129, LHI = 512;
-constexpr int QT = 32;            // rows of a tile
-constexpr int KB = 64;            // rows of the other operand staged at a time (MFMA form)
 
 struct LongArgs {
   const void *q, *k, *v, *dout;
@@ -49,42 +46,6 @@ struct LongArgs {
   const unsigned* salt;
 };
 
-__device__ __forceinline__ bool masked(int mask, int period, int i, int j) {
-  return (mask == AFFT_MASK_DIAG && i == j) || (mask == AFFT_MASK_CAUSAL && j > i) ||
-         (mask == AFFT_MASK_BLOCKCAUSAL && (j % period) > (i % period));
-}
-
-// ---- LDS operand tiles [R][hc] bf16, 32-byte unit u of row r stored at unit u ^ (r & 7) (the layout of attention_mfma.hip)
-__device__ __forceinline__ int swz(int row, int row_bytes) { return row & 7 & ((row_bytes >> 5) - 1); }
-__device__ __forceinline__ int tile_off(int row, int chunk16, int row_bytes) {
-  return row * row_bytes + ((chunk16 ^ (swz(row, row_bytes) << 1)) << 4);
-}
-// rows [0, R) of src (offset by the caller to its first row, head and hd chunk); rows >= rows_valid are staged as zeros, never read
-__device__ __forceinline__ void load_tile(const bf16_t* __restrict__ src, int64_t ld, int rows_valid, int R, int hc, char* lds) {
-  const int cpr = hc >> 3;
-  for (int idx = threadIdx.x; idx < R * cpr; idx += 256) {
-    const int row = idx / cpr, ch = idx - row * cpr;
-    uint4 val = make_uint4(0u, 0u, 0u, 0u);
-    if (row < rows_valid) val = *(const uint4*)(src + (int64_t)row * ld + ch * 8);
-    *(uint4*)(lds + tile_off(row, ch, hc * 2)) = val;
-  }
-}
-__device__ __forceinline__ bf16x8 row_frag(const char* lds, int row, int chunk16, int row_bytes) {
-  return *(const bf16x8*)(lds + tile_off(row, chunk16, row_bytes));
-}
-// lane (g, i) gets tile[row0 + 4g + j][16 cb + i], j = 0..3
-__device__ __forceinline__ bf16x4 tr_frag(const char* lds, int row0, int cb, int lane, int row_bytes) {
-  const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-  const int r = row0 + 4 * g + q;
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((AFFT_LDS bf16x4*)(lds + r * row_bytes + ((cb ^ swz(r, row_bytes)) << 5) + p * 8));
-}
-__device__ __forceinline__ void store_o4(bf16_t* dst, const f32x4& a) {
-  uint2 u;
-  u.x = (unsigned)f2bf(a[0]) | ((unsigned)f2bf(a[1]) << 16);
-  u.y = (unsigned)f2bf(a[2]) | ((unsigned)f2bf(a[3]) << 16);
-  *(uint2*)dst = u;
-}
-
 // ---- dots, MFMA: strip[r][j] = A[r] . B[j], r < 32, j < Lp.  A, B point at (first row, head); rows >= a_valid / b_valid count as zero.
 // S^T tiles: the 16 B rows of a wave are the MFMA's A operand (rows on (lane >> 4, register)), the tile rows its B operand (lane & 15).
 // The A chunk is staged once per hd chunk, the B rows pass in blocks of 64 (16 per wave); all Lp / 64 <= 8 accumulator pairs stay in
@@ -100,12 +61,12 @@ __device__ __forceinline__ void dots_mfma(const bf16_t* __restrict__ A, int64_t 
   for (int kb = 0; kb < LHI / KB; ++kb) { acc[kb][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[kb][1] = acc[kb][0]; }
   for (int c = 0; c < hd; c += hc) {
     __syncthreads();                       // whoever used the stage before is done
-    load_tile(A + c, lda, a_valid, QT, hc, As);
+    load_tile(A + c, lda, 0, a_valid, QT, hc, As);
 #pragma unroll
     for (int kb = 0; kb < LHI / KB; ++kb) {
       if (kb * KB < Lp) {
         if (kb) __syncthreads();           // the previous block has been consumed by every wave
-        load_tile(B + (int64_t)kb * KB * ldb + c, ldb, b_valid - kb * KB, KB, hc, Bs);
+        load_tile(B + (int64_t)kb * KB * ldb + c, ldb, 0, b_valid - kb * KB, KB, hc, Bs);
         __syncthreads();
         for (int ks = 0; ks < hc / 32; ++ks) {
           const int ch = ks * 4 + g;
@@ -140,7 +101,7 @@ __device__ __forceinline__ void matmul_mfma(const float* strip, int sld, int Lp,
     for (int u = 0; u < 4; ++u) { o[u][0] = f32x4{0.f, 0.f, 0.f, 0.f}; o[u][1] = o[u][0]; }
     for (int kb = 0; kb < Lp; kb += KB) {
       __syncthreads();
-      load_tile(B + (int64_t)kb * ldb + c, ldb, b_valid - kb, KB, hc, stage);
+      load_tile(B + (int64_t)kb * ldb + c, ldb, 0, b_valid - kb, KB, hc, stage);
       __syncthreads();
 #pragma unroll
       for (int kk = 0; kk < KB; kk += 32) {
@@ -442,156 +403,101 @@ __global__ __launch_bounds__(256) void bias_bwd_reduce_kernel(const float* __res
   if (wave == 0 && j < L) dbias[bo * ob + ho * oh + io * oi + j] = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
 }
 
-bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-bool al8(const void* p) { return (((uintptr_t)p) & 7) == 0; }
-bool use_mfma_attention() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("AFFT_ATTN_GENERIC"); v = (e && e[0] == '1') ? 0 : 1; }
-  return v == 1;
-}
-
+// one kernel of a long plan: the attribute is set once per (kernel, device): ask for the most any shape needs (L = 512, hd chunks of 256: 112.5 KiB)
 template <typename KernT>
-int launch_long(KernT kern, std::atomic<uint64_t>* attr_done, const LongArgs& a, int nseq, bool mfma, hipStream_t stream) {
-  const size_t lds = (size_t)QT * (a.Lp + 4) * sizeof(float) + (mfma ? (size_t)(QT + KB) * a.hc * 2 : 0);
-  // the attribute is set once per (kernel, device): ask for the most any shape needs (L = 512, hd chunks of 256: 112.5 KiB)
+int launch_long(KernT kern, std::atomic<uint64_t>* attr_done, const LongArgs& a, const AttnPlan& p, hipStream_t stream) {
   constexpr size_t lds_max = (size_t)QT * (LHI + 4) * sizeof(float) + (size_t)(QT + KB) * 256 * 2;
   if (int rc = afft_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds_max, attr_done)) return rc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)nseq * a.H * a.ntiles)), dim3(256), lds, stream, a);
+  hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), p.lds, stream, a);
   return 0;
 }
-#define LONG_LAUNCH(KERN)                                                      \
-  do {                                                                         \
-    static std::atomic<uint64_t> attr_done{0};                                 \
-    if (int rc_ = launch_long(KERN, &attr_done, a, nseq, mfma, stream)) return rc_; \
+#define LONG_LAUNCH(KERN)                                                       \
+  do {                                                                          \
+    static std::atomic<uint64_t> attr_done{0};                                  \
+    if (int rc_ = launch_long(KERN, &attr_done, a, p, stream)) return rc_;      \
   } while (0)
-
-void fill_common(LongArgs& a, int L, int H, int hd, float scale, float drop_p, unsigned drop_key) {
-  a.L = L; a.Lp = (L + KB - 1) / KB * KB; a.H = H; a.hd = hd; a.ntiles = (L + QT - 1) / QT;
-  a.hc = hd % 256 == 0 ? 256 : hd % 128 == 0 ? 128 : 64;
-  a.scale = scale;
-  afft_dropout_t dd = {drop_p, drop_key, 0.f, 0u, 1};
-  const DropParams dp = make_drop(&dd);
-  a.dthresh = dp.thresh; a.dkey = dp.key; a.dinv = dp.inv_keep; a.salt = dp.salt;
-}
 
 }  // namespace
 
-static int attention_long_fwd_impl(const char* who, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
-                                   int32_t dtype, int32_t nseq, int32_t L, int32_t H, int32_t hd, float scale, int32_t mask,
-                                   int32_t mask_period, const float* bias, int64_t sb, int64_t sh, int64_t si, float drop_p,
-                                   uint32_t drop_key, void* out, int64_t ldo, float* probs, hipStream_t stream) {
-  AFFT_CHECK(q && k && v && out, "%s: null pointer", who);
-  AFFT_CHECK(L >= LLO && L <= LHI, "%s: sequence length %d outside %d..%d", who, L, LLO, LHI);
-  AFFT_CHECK(mask >= AFFT_MASK_NONE && mask <= AFFT_MASK_BLOCKCAUSAL, "%s: bad mask %d", who, mask);
-  AFFT_CHECK(mask != AFFT_MASK_BLOCKCAUSAL || (mask_period >= 1 && L % mask_period == 0),
-             "%s: block-causal mask needs a period that divides L (L=%d, period=%d)", who, L, mask_period);
-  AFFT_CHECK(drop_p >= 0.f && drop_p < 1.f, "%s: dropout p outside [0,1)", who);
-  AFFT_CHECK(hd >= 1 && hd <= 1024, "%s: head dimension %d outside 1..1024", who, hd);
-  AFFT_CHECK(dtype == AFFT_F32 || dtype == AFFT_BF16, "%s: bad dtype %d", who, dtype);
-  AFFT_CHECK(nseq >= 0 && H >= 1, "%s: bad nseq %d / H %d", who, nseq, H);
-  if (nseq == 0) return 0;
-  const int64_t es_ = dtype == AFFT_F32 ? 4 : 2, rw_ = (int64_t)nseq * L * H * hd, pb_ = probs ? (int64_t)nseq * H * L * L * 4 : 0;
-  AfftKernelScope ktrace(AFFT_K_ATTN_FWD, nseq * L, H * hd, 4 * es_ * rw_ + pb_, 4 * (int64_t)nseq * H * L * L * hd, stream);
+int launch_attention_long(const AttnCall& c, const AttnPlan& p, hipStream_t stream) {
+  const bool reduce = c.dir == kBiasBwd && bias_grad_reduces(c);
   LongArgs a = {};
-  a.q = q; a.k = k; a.v = v; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
-  a.out = out; a.ldo = ldo; a.probs = probs; a.addm = bias; a.sb = sb; a.sh = sh; a.si = si;
-  a.mask = mask; a.period = mask == AFFT_MASK_BLOCKCAUSAL ? mask_period : 1;
-  fill_common(a, L, H, hd, scale, drop_p, drop_key);
-  const bool mfma = dtype == AFFT_BF16 && use_mfma_attention() && hd % 64 == 0 && ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 &&
-                    al16(q) && al16(k) && al16(v) && ldo % 4 == 0 && al8(out);
-  if (dtype == AFFT_F32) LONG_LAUNCH((long_fwd_kernel<float, false>));
-  else if (mfma) LONG_LAUNCH((long_fwd_kernel<bf16_t, true>));
-  else LONG_LAUNCH((long_fwd_kernel<bf16_t, false>));
+  a.q = c.q; a.k = c.k; a.v = c.v; a.dout = c.dout; a.ldq = c.ldq; a.ldk = c.ldk; a.ldv = c.ldv; a.lddo = c.lddo;
+  a.out = c.out; a.dq = c.dq; a.dk = c.dk; a.dv = c.dv; a.ldo = c.ldo; a.lddq = c.lddq; a.lddk = c.lddk; a.lddv = c.lddv;
+  a.probs = c.probs; a.addm = c.bias; a.sb = c.sb; a.sh = c.sh; a.si = c.si; a.row_term = c.row_term;
+  if (reduce) { a.dbias = c.scratch; a.ob = (int64_t)c.H * c.L * c.L; a.oh = (int64_t)c.L * c.L; a.oi = c.L; }      // every (seq, h, i, j) first
+  else { a.dbias = c.dbias; a.ob = c.dsb; a.oh = c.dsh; a.oi = c.dsi; }
+  a.L = c.L; a.Lp = p.Lp; a.H = c.H; a.hd = c.hd; a.hc = p.hc; a.ntiles = p.ntiles;
+  a.scale = c.scale;
+  a.mask = c.mask; a.period = c.mask == AFFT_MASK_BLOCKCAUSAL ? c.period : 1;
+  afft_dropout_t dd = {c.drop_p, c.drop_key, 0.f, 0u, 1};
+  const DropParams dp = make_drop(&dd);
+  a.dthresh = dp.thresh; a.dkey = dp.key; a.dinv = dp.inv_keep; a.salt = dp.salt;
+  switch (p.family) {
+    case kLongF32:
+      if (c.dir == kFwd) LONG_LAUNCH((long_fwd_kernel<float, false>));
+      else { LONG_LAUNCH((long_bwd_q_kernel<float, false>)); LONG_LAUNCH((long_bwd_kv_kernel<float, false>)); }
+      break;
+    case kLongBf16:
+      if (c.dir == kFwd) LONG_LAUNCH((long_fwd_kernel<bf16_t, false>));
+      else { LONG_LAUNCH((long_bwd_q_kernel<bf16_t, false>)); LONG_LAUNCH((long_bwd_kv_kernel<bf16_t, false>)); }
+      break;
+    case kLongMfma:
+      if (c.dir == kFwd) LONG_LAUNCH((long_fwd_kernel<bf16_t, true>));
+      else { LONG_LAUNCH((long_bwd_q_kernel<bf16_t, true>)); LONG_LAUNCH((long_bwd_kv_kernel<bf16_t, true>)); }
+      break;
+    case kBiasF32: LONG_LAUNCH((bias_bwd_ds_kernel<float, false>)); break;
+    case kBiasBf16: LONG_LAUNCH((bias_bwd_ds_kernel<bf16_t, false>)); break;
+    default: LONG_LAUNCH((bias_bwd_ds_kernel<bf16_t, true>)); break;
+  }
+  if (reduce) {
+    const int64_t rows = (int64_t)(c.dsb ? c.nseq : 1) * (c.dsh ? c.H : 1) * (c.dsi ? c.L : 1);
+    hipLaunchKernelGGL(bias_bwd_reduce_kernel, dim3((unsigned)rows, (unsigned)((c.L + 63) / 64)), dim3(256), 0, stream, c.scratch, c.dbias,
+                       c.nseq, c.H, c.L, (int)(c.dsb == 0), (int)(c.dsh == 0), (int)(c.dsi == 0), c.dsb, c.dsh, c.dsi);
+  }
   AFFT_LAUNCH_CHECK();
   return 0;
 }
+
+constexpr unsigned kLongChecks = kChkPtrs | kLenLong | kChkMask | kChkDrop | kChkHd | kChkDtype | kChkBatch;
 
 extern "C" int afft_attention_long_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
                                        int32_t dtype, int32_t nseq, int32_t L, int32_t H, int32_t hd, float scale, int32_t mask,
                                        int32_t mask_period, const float* mask_table, float drop_p, uint32_t drop_key, void* out,
                                        int64_t ldo, float* probs, void* stream_) {
-  return attention_long_fwd_impl("attention_long_fwd", q, ldq, k, ldk, v, ldv, dtype, nseq, L, H, hd, scale, mask, mask_period,
-                                 mask_table, 0, 0, L, drop_p, drop_key, out, ldo, probs, (hipStream_t)stream_);
+  AttnCall c = attn_fwd_call(q, ldq, k, ldk, v, ldv, dtype, nseq, L, H, hd, scale, drop_p, drop_key, out, ldo, probs);
+  c.mask = mask; c.period = mask_period;
+  c.bias = mask_table; c.si = L;
+  return run_attention("attention_long_fwd", c, kLongChecks, 0, (hipStream_t)stream_);
 }
 
 extern "C" int afft_attention_long_fwd_bias(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
                                             int32_t dtype, int32_t nseq, int32_t L, int32_t H, int32_t hd, float scale,
                                             const float* bias, int64_t sb, int64_t sh, int64_t si, float drop_p, uint32_t drop_key,
                                             void* out, int64_t ldo, float* probs, void* stream_) {
-  AFFT_CHECK(bias, "attention_long_fwd_bias: null pointer");
-  AFFT_CHECK(sb >= 0 && sh >= 0 && si >= 0, "attention_long_fwd_bias: negative bias stride (sb=%lld, sh=%lld, si=%lld)", (long long)sb,
-             (long long)sh, (long long)si);
-  AFFT_CHECK((((uintptr_t)bias) & 3) == 0, "attention_long_fwd_bias: bias pointer %p is not 4-byte aligned", (const void*)bias);
-  return attention_long_fwd_impl("attention_long_fwd_bias", q, ldq, k, ldk, v, ldv, dtype, nseq, L, H, hd, scale, AFFT_MASK_NONE, 0, bias,
-                                 sb, sh, si, drop_p, drop_key, out, ldo, probs, (hipStream_t)stream_);
+  AttnCall c = attn_fwd_call(q, ldq, k, ldk, v, ldv, dtype, nseq, L, H, hd, scale, drop_p, drop_key, out, ldo, probs);
+  c.bias = bias; c.sb = sb; c.sh = sh; c.si = si;
+  if (int rc = check_attention("attention_long_fwd_bias", c, kChkBias | kChkBiasArgs)) return rc;
+  return run_attention("attention_long_fwd_bias", c, kLongChecks, 0, (hipStream_t)stream_);
 }
 
 extern "C" int afft_attention_long_bwd(const void* dout, int64_t lddo, const void* q, int64_t ldq, const void* k, int64_t ldk,
                                        const void* v, int64_t ldv, int32_t dtype, const float* probs, int32_t nseq, int32_t L,
                                        int32_t H, int32_t hd, float scale, float drop_p, uint32_t drop_key, void* dq,
                                        int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv, float* row_term, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  AFFT_CHECK(dout && q && k && v && probs && dq && dk && dv && row_term, "attention_long_bwd: null pointer");
-  AFFT_CHECK(L >= LLO && L <= LHI, "attention_long_bwd: sequence length %d outside %d..%d", L, LLO, LHI);
-  AFFT_CHECK(drop_p >= 0.f && drop_p < 1.f, "attention_long_bwd: dropout p outside [0,1)");
-  AFFT_CHECK(hd >= 1 && hd <= 1024, "attention_long_bwd: head dimension %d outside 1..1024", hd);
-  AFFT_CHECK(dtype == AFFT_F32 || dtype == AFFT_BF16, "attention_long_bwd: bad dtype %d", dtype);
-  AFFT_CHECK(nseq >= 0 && H >= 1, "attention_long_bwd: bad nseq %d / H %d", nseq, H);
-  if (nseq == 0) return 0;
-  // bytes: the algorithmic ones of attention_bwd; flops: the four products (dP is formed twice here, once per pass: 10 L^2 hd are executed)
-  const int64_t es_ = dtype == AFFT_F32 ? 4 : 2, rw_ = (int64_t)nseq * L * H * hd, pb_ = (int64_t)nseq * H * L * L * 4;
-  AfftKernelScope ktrace(AFFT_K_ATTN_BWD, nseq * L, H * hd, 7 * es_ * rw_ + pb_, 8 * (int64_t)nseq * H * L * L * hd, stream);
-  LongArgs a = {};
-  a.dout = dout; a.q = q; a.k = k; a.v = v; a.lddo = lddo; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
-  a.dq = dq; a.dk = dk; a.dv = dv; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
-  a.probs = const_cast<float*>(probs); a.row_term = row_term;
-  a.mask = AFFT_MASK_NONE; a.period = 1;
-  fill_common(a, L, H, hd, scale, drop_p, drop_key);
-  const bool mfma = dtype == AFFT_BF16 && use_mfma_attention() && hd % 64 == 0 && lddo % 8 == 0 && ldq % 8 == 0 && ldk % 8 == 0 &&
-                    ldv % 8 == 0 && al16(dout) && al16(q) && al16(k) && al16(v) && lddq % 4 == 0 && lddk % 4 == 0 && lddv % 4 == 0 &&
-                    al8(dq) && al8(dk) && al8(dv);
-  if (dtype == AFFT_F32) { LONG_LAUNCH((long_bwd_q_kernel<float, false>)); LONG_LAUNCH((long_bwd_kv_kernel<float, false>)); }
-  else if (mfma) { LONG_LAUNCH((long_bwd_q_kernel<bf16_t, true>)); LONG_LAUNCH((long_bwd_kv_kernel<bf16_t, true>)); }
-  else { LONG_LAUNCH((long_bwd_q_kernel<bf16_t, false>)); LONG_LAUNCH((long_bwd_kv_kernel<bf16_t, false>)); }
-  AFFT_LAUNCH_CHECK();
-  return 0;
+  AttnCall c = attn_bwd_call(dout, lddo, q, ldq, k, ldk, v, ldv, dtype, probs, nseq, L, H, hd, scale, drop_p, drop_key, dq, lddq, dk, lddk, dv, lddv);
+  c.row_term = row_term;
+  return run_attention("attention_long_bwd", c, (kLongChecks & ~kChkMask) | kChkRowTerm, 0, (hipStream_t)stream_);
 }
 
 extern "C" int afft_attention_bias_bwd(const void* dout, int64_t lddo, const void* v, int64_t ldv, int32_t dtype, const float* probs,
                                        int32_t nseq, int32_t L, int32_t H, int32_t hd, float drop_p, uint32_t drop_key, float* dbias,
                                        int64_t sb, int64_t sh, int64_t si, float* scratch, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  AFFT_CHECK(dout && v && probs && dbias, "attention_bias_bwd: null pointer");
-  AFFT_CHECK(L >= 1 && L <= LHI, "attention_bias_bwd: sequence length %d outside 1..%d", L, LHI);
-  AFFT_CHECK(drop_p >= 0.f && drop_p < 1.f, "attention_bias_bwd: dropout p outside [0,1)");
-  AFFT_CHECK(hd >= 1 && hd <= 1024, "attention_bias_bwd: head dimension %d outside 1..1024", hd);
-  AFFT_CHECK(dtype == AFFT_F32 || dtype == AFFT_BF16, "attention_bias_bwd: bad dtype %d", dtype);
-  AFFT_CHECK(nseq >= 0 && H >= 1, "attention_bias_bwd: bad nseq %d / H %d", nseq, H);
-  AFFT_CHECK(sb >= 0 && sh >= 0 && si >= 0, "attention_bias_bwd: negative bias stride (sb=%lld, sh=%lld, si=%lld)", (long long)sb,
-             (long long)sh, (long long)si);
-  AFFT_CHECK((((uintptr_t)dbias) & 3) == 0, "attention_bias_bwd: dbias pointer %p is not 4-byte aligned", (void*)dbias);
-  const bool reduce = sb == 0 || sh == 0 || si == 0;
-  AFFT_CHECK(!reduce || (scratch && (((uintptr_t)scratch) & 3) == 0),
-             "attention_bias_bwd: a broadcast bias needs 4-byte aligned scratch of nseq*H*L*L floats (scratch=%p)", (void*)scratch);
-  if (nseq == 0) return 0;
-  const int64_t es_ = dtype == AFFT_F32 ? 4 : 2, rw_ = (int64_t)nseq * L * H * hd, pb_ = (int64_t)nseq * H * L * L * 4;
-  AfftKernelScope ktrace(AFFT_K_ATTN_BWD, nseq * L, H * hd, 2 * es_ * rw_ + (reduce ? 3 : 2) * pb_, 2 * (int64_t)nseq * H * L * L * hd, stream);
-  LongArgs a = {};
-  a.dout = dout; a.v = v; a.lddo = lddo; a.ldv = ldv;
-  a.probs = const_cast<float*>(probs);
-  a.mask = AFFT_MASK_NONE; a.period = 1;
-  if (reduce) { a.dbias = scratch; a.ob = (int64_t)H * L * L; a.oh = (int64_t)L * L; a.oi = L; }
-  else { a.dbias = dbias; a.ob = sb; a.oh = sh; a.oi = si; }
-  fill_common(a, L, H, hd, 1.0f, drop_p, drop_key);
-  const bool mfma = dtype == AFFT_BF16 && use_mfma_attention() && hd % 64 == 0 && lddo % 8 == 0 && ldv % 8 == 0 && al16(dout) && al16(v);
-  if (dtype == AFFT_F32) LONG_LAUNCH((bias_bwd_ds_kernel<float, false>));
-  else if (mfma) LONG_LAUNCH((bias_bwd_ds_kernel<bf16_t, true>));
-  else LONG_LAUNCH((bias_bwd_ds_kernel<bf16_t, false>));
-  if (reduce) {
-    const int64_t rows = (int64_t)(sb ? nseq : 1) * (sh ? H : 1) * (si ? L : 1);
-    hipLaunchKernelGGL(bias_bwd_reduce_kernel, dim3((unsigned)rows, (unsigned)((L + 63) / 64)), dim3(256), 0, stream, scratch, dbias,
-                       nseq, H, L, (int)(sb == 0), (int)(sh == 0), (int)(si == 0), sb, sh, si);
-  }
-  AFFT_LAUNCH_CHECK();
-  return 0;
+  AttnCall c = {};
+  c.dir = kBiasBwd; c.dtype = dtype;
+  c.dout = dout; c.lddo = lddo; c.v = v; c.ldv = ldv; c.probs = const_cast<float*>(probs);
+  c.nseq = nseq; c.L = L; c.H = H; c.hd = hd; c.scale = 1.0f; c.drop_p = drop_p; c.drop_key = drop_key;      // the bias is added after the score scale
+  c.dbias = dbias; c.dsb = sb; c.dsh = sh; c.dsi = si; c.scratch = scratch;
+  return run_attention("attention_bias_bwd", c, kChkPtrs | kLenAll | kChkDrop | kChkHd | kChkDtype | kChkBatch | kChkBiasArgs | kChkScratch, 0,
+                       (hipStream_t)stream_);
 }

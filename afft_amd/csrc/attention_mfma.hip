@@ -16,10 +16,15 @@
 // HBM-bound by construction (attention is < 0.2 % of the path's FLOPs): q, k, v are read once and
 // out written once per head; what this kernel buys over the generic VALU kernel (attention.hip) is the removal of
 // ~100 us of latency-bound per-pair dot products per launch.
+// The operand tiles and the mask rule are attention_tiles.h's; which shapes come here, with which NT, chunk and LDS bytes, is
+// attn_plan.h's decision (plan_short_mfma).
 //
 // Reference semantics: models/transformerblock.py:24-33,64-73 ; HF GPT-2 eager attention (causal, masked
 // probabilities exactly 0).  probs output holds the PRE-dropout probabilities (see include/afft_hip.h).
-#include "common.h"
+#include "attention_tiles.h"
+#include "attn_plan.h"
+
+using namespace afft_attn_detail;
 
 namespace {
 
@@ -48,55 +53,18 @@ __device__ __forceinline__ bool pair_valid(int mask, int period, int L, int rows
   const int sq = qi / L, sk = kj / L;
   if (sq != sk) return false;                    // block-diagonal: tokens of different packed sequences never mix
   const int i = qi - sq * L, j = kj - sk * L;
+  // the rule of masked() (attention_tiles.h), kept in this form: as a call it costs these kernels another register allocation
   if (mask == AFFT_MASK_DIAG && i == j) return false;
   if (mask == AFFT_MASK_CAUSAL && j > i) return false;
   if (mask == AFFT_MASK_BLOCKCAUSAL && (j % period) > (i % period)) return false;   // T-SA-Fuser: causal T x T tiled
   return true;
 }
 
-// LDS tile [R][hd] bf16; 32-byte unit u of row r is stored at unit u ^ (r & 7): conflict-free transposed reads,
-// 2-way (harmless here) ds_read_b128 row reads.
-__device__ __forceinline__ int swz(int row, int row_bytes) {   // XOR stays inside the row: rows hold row_bytes/32 units
-  return row & 7 & ((row_bytes >> 5) - 1);
-}
-__device__ __forceinline__ int tile_off(int row, int chunk16, int row_bytes) {
-  return row * row_bytes + ((chunk16 ^ (swz(row, row_bytes) << 1)) << 4);
-}
-
-// stages columns [0, hd) of rows row0.. of src (the caller offsets src to the head and head-dimension chunk)
-__device__ __forceinline__ void load_tile(const bf16_t* __restrict__ src, int64_t ld, int64_t row0, int rows_valid,
-                                          int R, int hd, char* lds) {
-  const int cpr = hd >> 3;  // 16-byte chunks per row
-  for (int idx = threadIdx.x; idx < R * cpr; idx += 256) {
-    const int row = idx / cpr, ch = idx - row * cpr;
-    uint4 val = make_uint4(0u, 0u, 0u, 0u);
-    if (row < rows_valid) val = *(const uint4*)(src + (row0 + row) * ld + ch * 8);
-    *(uint4*)(lds + tile_off(row, ch, hd * 2)) = val;
-  }
-}
-
-__device__ __forceinline__ bf16x8 row_frag(const char* lds, int row, int chunk16, int row_bytes) {
-  return *(const bf16x8*)(lds + tile_off(row, chunk16, row_bytes));
-}
-// A operand of 16x16x16 for X^T: lane (g, i) gets tile[row0 + 4g + j][16*cb + i], j = 0..3
-__device__ __forceinline__ bf16x4 tr_frag(const char* lds, int row0, int cb, int lane, int row_bytes) {
-  const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-  const int r = row0 + 4 * g + q;
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (AFFT_LDS bf16x4*)(lds + r * row_bytes + ((cb ^ swz(r, row_bytes)) << 5) + p * 8));
-}
 __device__ __forceinline__ bf16x4 pack4(const float (&v)[4]) {
   bf16x4 r;
   r[0] = (short)f2bf(v[0]); r[1] = (short)f2bf(v[1]); r[2] = (short)f2bf(v[2]); r[3] = (short)f2bf(v[3]);
   return r;
 }
-__device__ __forceinline__ void store_o4(bf16_t* dst, const f32x4& a) {
-  uint2 u;
-  u.x = (unsigned)f2bf(a[0]) | ((unsigned)f2bf(a[1]) << 16);
-  u.y = (unsigned)f2bf(a[2]) | ((unsigned)f2bf(a[3]) << 16);
-  *(uint2*)dst = u;
-}
-
 typedef __attribute__((ext_vector_type(8))) _Float16 h8;
 typedef __attribute__((ext_vector_type(4))) _Float16 h4;
 __device__ __forceinline__ f32x4 mfma32_h(bf16x8 a, bf16x8 b, f32x4 c) {
@@ -490,8 +458,6 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(const AttnArgs a) {
   }
 }
 
-bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 // ---------------------------------------------------------------------------------------------------------------------
 // Round 5 backward: every wave owns a COLUMN SLICE of the head (SL = hd / 4 channels) from start to end.
 //   * its slices of V, dO, Q, K are fetched with fully coalesced 16-byte loads issued back to back at kernel start (64 registers
@@ -746,80 +712,44 @@ __global__ __launch_bounds__(256) void attn_bwd_sliced_kernel(const AttnArgs a) 
 
 }  // namespace
 
-#ifndef AFFT_ATTN_PL_LDS_KB
-#define AFFT_ATTN_PL_LDS_KB 48
-#endif
-// Returns 0 when launched, -1 when the shape is not handled by the MFMA path (caller falls back), >0 on error.
-int afft_attention_mfma(bool backward, const void* dout, int64_t lddo, const void* q, int64_t ldq, const void* k,
-                        int64_t ldk, const void* v, int64_t ldv, float* probs, int nseq, int L, int H, int hd,
-                        float scale, int mask, float drop_p, unsigned drop_key, void* out, int64_t ldo, void* dq,
-                        int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv, hipStream_t stream,
-                        int planes, int64_t in_lo, int64_t out_lo, void* out_b, int64_t ldob, void* out_lo8) {
-  if (L > 64 || hd % 64 != 0 || hd > 1024) return -1;
-  if (planes && (backward || in_lo % 8 || in_lo < 0 || out_lo % 4 || ldob % 4 || (((uintptr_t)out_b) & 7))) return -1;
-  if (ldq % 8 || ldk % 8 || ldv % 8 || !al16(q) || !al16(k) || !al16(v)) return -1;
-  if (!backward && (ldo % 4 || (((uintptr_t)out) & 7))) return -1;
-  if (backward && (lddo % 8 || !al16(dout) || lddq % 4 || lddk % 4 || lddv % 4 || (((uintptr_t)dq) & 7) ||
-                   (((uintptr_t)dk) & 7) || (((uintptr_t)dv) & 7) || !probs)) return -1;
-  const int NT = L > 32 ? 4 : L > 16 ? 2 : 1;
-  // the whole head dimension in LDS when it fits (3 tiles forward, 4 backward); else chunks of the head dimension,
-  // the scores / dP accumulate over the chunks and the operand tiles are re-staged (2 tiles forward, 3 backward)
-  int hc = hd;
-  const int np = (planes && in_lo) ? 2 : 1;       // fp16x2 forward: every operand tile is two planes (in_lo = 0: the hi plane alone)
-  size_t lds = (size_t)(backward ? 4 : 3) * np * 16 * NT * hd * 2;
-  // planes (fp16x2 forward): the two-plane tiles of a whole head (96 KiB at hd = 512) leave ONE workgroup per CU, whose load -> barrier ->
-  // compute -> store runs with nothing beside it (2.75 TB/s); chunks that fit 48 KiB keep three workgroups per CU in flight
-  const size_t budget = (planes && !backward) ? (size_t)(AFFT_ATTN_PL_LDS_KB) * 1024 : (size_t)160 * 1024;
-  if (lds > budget) {
-    hc = 0;
-    for (int cand = hd / 2; cand >= 64; cand /= 2)
-      if (hd % cand == 0 && cand % 64 == 0 && (size_t)(backward ? 3 : 2) * np * 16 * NT * cand * 2 <= budget) { hc = cand; break; }
-    if (!hc) return -1;
-    lds = (size_t)(backward ? 3 : 2) * np * 16 * NT * hc * 2;
-  }
+// the plan's family and template parameters -> the instantiation; every kernel may be asked for the CU's whole 160 KiB
+int launch_attention_mfma(const AttnCall& c, const AttnPlan& p, hipStream_t stream) {
   AttnArgs a;
-  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.dout = (const bf16_t*)dout;
-  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.lddo = lddo;
-  a.out = (bf16_t*)out; a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv;
-  a.ldo = ldo; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
-  a.probs = probs;
-  a.in_lo = in_lo; a.out_lo = out_lo; a.out_b = (bf16_t*)out_b; a.ldob = ldob; a.out_lo8 = (unsigned char*)out_lo8;
-  a.nseq = nseq; a.L = L; a.H = H; a.hd = hd; a.G = (16 * NT) / L; a.hc = hc;
-  a.scale = scale; a.mask = mask & 0xff; a.period = mask >> 8;   // block-causal period rides in the upper bits
-  afft_dropout_t dd = {drop_p, drop_key, 0.f, 0u, 1};
+  a.q = (const bf16_t*)c.q; a.k = (const bf16_t*)c.k; a.v = (const bf16_t*)c.v; a.dout = (const bf16_t*)c.dout;
+  a.ldq = c.ldq; a.ldk = c.ldk; a.ldv = c.ldv; a.lddo = c.lddo;
+  a.out = (bf16_t*)c.out; a.dq = (bf16_t*)c.dq; a.dk = (bf16_t*)c.dk; a.dv = (bf16_t*)c.dv;
+  a.ldo = c.ldo; a.lddq = c.lddq; a.lddk = c.lddk; a.lddv = c.lddv;
+  a.probs = c.probs;
+  a.in_lo = c.in_lo; a.out_lo = c.out_lo; a.out_b = (bf16_t*)c.out_b; a.ldob = c.ldob; a.out_lo8 = (unsigned char*)c.out_lo8;
+  a.nseq = c.nseq; a.L = c.L; a.H = c.H; a.hd = c.hd; a.G = p.G; a.hc = p.hc;
+  a.scale = c.scale; a.mask = c.mask; a.period = c.mask == AFFT_MASK_BLOCKCAUSAL ? c.period : 0;
+  afft_dropout_t dd = {c.drop_p, c.drop_key, 0.f, 0u, 1};
   const DropParams dp = make_drop(&dd);
   a.dthresh = dp.thresh; a.dkey = dp.key; a.dinv = dp.inv_keep; a.salt = dp.salt;
-  const int groups = (nseq + a.G - 1) / a.G;
-  const dim3 grid(groups * H), block(256);
-#define AFFT_ATTN_LAUNCH(KERN)                                                                              \
-  do {                                                                                                      \
-    static std::atomic<uint64_t> attr_done{0};                                                              \
-    if (afft_ensure_dynamic_lds(reinterpret_cast<const void*>(KERN), 160 * 1024, &attr_done)) return -1;    \
-    hipLaunchKernelGGL(KERN, grid, block, lds, stream, a);                                                  \
+#define AFFT_ATTN_LAUNCH(KERN)                                                                                \
+  do {                                                                                                        \
+    static std::atomic<uint64_t> attr_done{0};                                                                \
+    if (int rc = afft_ensure_dynamic_lds(reinterpret_cast<const void*>(KERN), 160 * 1024, &attr_done)) return rc; \
+    hipLaunchKernelGGL(KERN, dim3(p.grid), dim3(256), p.lds, stream, a);                                      \
   } while (0)
-  if (!backward && planes && in_lo) {
-    if (NT == 1) AFFT_ATTN_LAUNCH((attn_fwd_mfma_kernel<1, 1>));
-    else if (NT == 2) AFFT_ATTN_LAUNCH((attn_fwd_mfma_kernel<2, 1>));
-    else AFFT_ATTN_LAUNCH((attn_fwd_mfma_kernel<4, 1>));
-  } else if (!backward && planes) {
-    if (NT == 1) AFFT_ATTN_LAUNCH((attn_fwd_mfma_kernel<1, 2>));
-    else if (NT == 2) AFFT_ATTN_LAUNCH((attn_fwd_mfma_kernel<2, 2>));
-    else AFFT_ATTN_LAUNCH((attn_fwd_mfma_kernel<4, 2>));
-  } else if (!backward) {
-    if (NT == 1) AFFT_ATTN_LAUNCH((attn_fwd_mfma_kernel<1, 0>));
-    else if (NT == 2) AFFT_ATTN_LAUNCH((attn_fwd_mfma_kernel<2, 0>));
-    else AFFT_ATTN_LAUNCH((attn_fwd_mfma_kernel<4, 0>));
-  } else {
-    if (NT <= 2 && hd % 128 == 0 && hd <= 512 && lddq % 8 == 0 && lddk % 8 == 0 && lddv % 8 == 0 && al16(dq) && al16(dk) && al16(dv)) {
-      // column-sliced backward (attn_bwd_sliced_kernel): 2 wave-private buffers of [16 NT][hd / 4] bf16 per wave + the partial dP tiles
-      lds = (size_t)4 * 2 * 16 * NT * (hd / 4) * 2 + (size_t)4 * 2 * NT * NT * 64 * 16;
-      if (NT == 1) AFFT_ATTN_LAUNCH(attn_bwd_sliced_kernel<1>);
-      else AFFT_ATTN_LAUNCH(attn_bwd_sliced_kernel<2>);
-    }
-    else if (NT == 1) AFFT_ATTN_LAUNCH(attn_bwd_mfma_kernel<1>);
-    else if (NT == 2) AFFT_ATTN_LAUNCH(attn_bwd_mfma_kernel<2>);
-    else AFFT_ATTN_LAUNCH(attn_bwd_mfma_kernel<4>);
+#define AFFT_ATTN_FWD(PL)                                                      \
+  do {                                                                         \
+    if (p.p0 == 1) AFFT_ATTN_LAUNCH((attn_fwd_mfma_kernel<1, PL>));            \
+    else if (p.p0 == 2) AFFT_ATTN_LAUNCH((attn_fwd_mfma_kernel<2, PL>));       \
+    else AFFT_ATTN_LAUNCH((attn_fwd_mfma_kernel<4, PL>));                      \
+  } while (0)
+  if (p.family == kMfmaFwd) {
+    if (p.p1 == 1) AFFT_ATTN_FWD(1);
+    else if (p.p1 == 2) AFFT_ATTN_FWD(2);
+    else AFFT_ATTN_FWD(0);
+  } else if (p.family == kSlicedBwd) {
+    if (p.p0 == 1) AFFT_ATTN_LAUNCH(attn_bwd_sliced_kernel<1>);
+    else AFFT_ATTN_LAUNCH(attn_bwd_sliced_kernel<2>);
   }
+  else if (p.p0 == 1) AFFT_ATTN_LAUNCH(attn_bwd_mfma_kernel<1>);
+  else if (p.p0 == 2) AFFT_ATTN_LAUNCH(attn_bwd_mfma_kernel<2>);
+  else AFFT_ATTN_LAUNCH(attn_bwd_mfma_kernel<4>);
+#undef AFFT_ATTN_FWD
 #undef AFFT_ATTN_LAUNCH
   AFFT_LAUNCH_CHECK();
   return 0;

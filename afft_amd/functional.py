@@ -612,13 +612,23 @@ def _composite_ok(x: Tensor, pre_ln: bool, *widths: int, f16x2: bool = True) -> 
             and x.stride(0) == x.shape[1] and all(w % 64 == 0 for w in widths))
 
 
+_split_core = {}      # (L, hd) -> bool: one ctypes call per shape, none per step
+
+
+def _attn_core_ok(L: int, hd: int) -> bool:
+    """the attention core at the current precision: 'fp16x2' runs on hi + lo planes, which only the MFMA kernels take (afft_attention_plan_for)"""
+    if rt.precision() != "fp16x2":
+        return True
+    if (L, hd) not in _split_core:
+        _split_core[L, hd] = L_.lib().afft_attention_plan_for(0, L_.F16, L, hd, 1, 1, 1) > 0
+    return _split_core[L, hd]
+
+
 def attn_take_ok(x: Tensor, L: int, H: int, pre_ln: bool = True) -> bool:
     """AttnSublayer(take=L) -- the output projection on token 0 of every sequence only -- exists on the composite path, for row
     counts whose quotient by L is a multiple of 64 (the weight-gradient GEMM reduces over whole 64-row K-tiles of the strided rows)"""
     R, d = x.shape
-    hd = d // H
-    return (1 < L <= ATTN_SHORT_MAX and R % L == 0 and (R // L) % 64 == 0 and _composite_ok(x, pre_ln, d)
-            and (rt.precision() != "fp16x2" or (L <= 64 and hd % 64 == 0 and hd <= 1024)))
+    return 1 < L <= ATTN_SHORT_MAX and R % L == 0 and (R // L) % 64 == 0 and _composite_ok(x, pre_ln, d) and _attn_core_ok(L, d // H)
 
 
 def _lo8_ok(conv1d: bool, *gemms) -> bool:
@@ -1037,10 +1047,9 @@ class AttnSublayer(torch.autograd.Function):
         # probs is returned for the caller's attention maps and takes no gradient: without this autograd hands backward a
         # freshly ZERO-FILLED tensor of its shape for it on every call (a fill kernel per attention sub-layer and step)
         ctx.set_materialize_grads(False)
-        # fp16x2: the attention core on hi + lo planes exists on the MFMA path only (L <= 64, head dimension a multiple of 64)
         if bias is None:
             bias = mask_bias(mask)
-        if not _mask_is_tensor(mask) and L <= ATTN_SHORT_MAX and _composite_ok(x, pre_ln, d) and (rt.precision() != "fp16x2" or (L <= 64 and hd % 64 == 0 and hd <= 1024)):
+        if not _mask_is_tensor(mask) and L <= ATTN_SHORT_MAX and _composite_ok(x, pre_ln, d) and _attn_core_ok(L, hd):
             return _attn_fwd_c(ctx, x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, L, H, mask, eps, conv1d, scale, drop, probs_out, take)
         ctx.up = _upstream_of(x) if pre_ln else None
         mean, rstd = _stats(R if pre_ln else 0, dev)

@@ -315,6 +315,15 @@ int afft_attention_bias_bwd(const void* dout, int64_t lddo, const void* v, int64
                             int32_t nseq, int32_t L, int32_t H, int32_t hd, float drop_p, uint32_t drop_key, float* dbias,
                             int64_t sb, int64_t sh, int64_t si, float* scratch, void* stream);
 
+/* Which attention kernel a call gets (the plan the nine entry points above launch from, csrc/attn_plan.h); launches nothing and needs
+ * no device.  direction: 0 forward, 1 backward, 2 bias gradient; dtype: AFFT_F32 / AFFT_BF16; planes != 0: the fp16x2 forward
+ * (afft_attention_fwd_split; in_lo != 0: two planes per input); pitch_alignment_ok: rows and pointers take 16-byte loads.
+ * Returns family * 10000 + p0 * 10 + p1 -- family 1: generic short kernels, p0 = LM (32 / 64 / 128); 2: MFMA short forward, p0 = NT,
+ * p1 = PL; 3: MFMA short backward, p0 = NT; 4: column-sliced backward, p0 = NT; 5 / 6 / 7: long (129..512) generic fp32 / generic
+ * bf16 / MFMA; 8 / 9 / 10: the same three forms of the bias-gradient stage -- or a negative value when no kernel takes the shape
+ * (afft_last_error says why).  AFFT_ATTN_GENERIC=1 in the environment keeps bf16 off the MFMA kernels (the fp16x2 forward has no other). */
+int afft_attention_plan_for(int32_t direction, int32_t dtype, int32_t L, int32_t hd, int32_t planes, int32_t in_lo, int32_t pitch_alignment_ok);
+
 /* afft_layernorm_bwd whose incoming residual gradient dx_in is [rows / in_take, d] (row pitch lddx_in) and belongs to rows 0, in_take,
  * 2 in_take, ..: the other rows take no residual gradient (afft_attn_sublayer_t.take; in_take = 1: every row). */
 int afft_layernorm_bwd_take(const void* dy, int64_t lddy, int32_t dy_dtype, const float* x, int64_t ldx, const float* w, const float* mean,
