@@ -589,7 +589,9 @@ def _attention_bwd(dout, q, k, v, probs, nseq, L, H, hd, scale, dq, dk, dv, drop
 
 def _attention_bias_bwd(bias, dout, v, probs, nseq, L, H, hd, drop):
     """the gradient of an additive attention bias, in the bias's own shape: into the gradient sink for a leaf (the way AddRowTable's table
-    gets its gradient), else returned to autograd"""
+    gets its gradient), else returned to autograd.  bias None (no bias, or one that takes no gradient): nothing"""
+    if bias is None:
+        return None
     if rt.grad_mode() == "sink" and bias.is_leaf:
         g, acc = rt.SINK.grad_buffer(bias)
         if acc:      # the same mask in several sub-layers (DecoderBlock: self- and cross-attention): the kernel overwrites, later uses add
@@ -878,10 +880,9 @@ def _attn_bwd_c(ctx, dy):
     keep = _fuse_updates(s, (("sgd_w_qkv", w_qkv, s.acc_w_qkv), ("sgd_w_proj", w_proj, s.acc_w_proj)))
     if _TAP is not None:
         _TAP("attn_bwd_pre", dict(R=R, d=d, w_qkv=w_qkv, w_proj=w_proj))
-    out = _bwd_finish(b, s, ctx, saved, L_.lib().afft_attn_sublayer_bwd, "attn_sublayer_bwd",
-                      ready=(w_proj, b.bias_ready, w_qkv, b_qkv, ln_w, ln_b), grads=(g_lw, g_lb, g_wq, g_bq, g_wp, b.g_bias),
-                      tap=("attn_bwd", dict(w_qkv=w_qkv, w_proj=w_proj, x=x)))
-    return out + (None,) * 9      # L, H, mask, eps, conv1d, pre_ln, scale, drop, probs_out (AttnSublayer.backward adds take)
+    return _bwd_finish(b, s, ctx, saved, L_.lib().afft_attn_sublayer_bwd, "attn_sublayer_bwd",
+                       ready=(w_proj, b.bias_ready, w_qkv, b_qkv, ln_w, ln_b), grads=(g_lw, g_lb, g_wq, g_bq, g_wp, b.g_bias),
+                       tap=("attn_bwd", dict(w_qkv=w_qkv, w_proj=w_proj, x=x)))
 
 
 def _mlp_fwd_c(ctx, x, ln_w, ln_b, w1, b1, w2, b2, eps, gelu, conv1d, hidden, drop):
@@ -946,10 +947,9 @@ def _mlp_bwd_c(ctx, dy):
     g_lw, g_lb, s.acc_ln = _ln_grad_slots(ln_w, ln_b, b.fresh)
     s.g_w1, s.g_b1, s.g_w2, s.g_ln_w, s.g_ln_b = _ptr(g_w1), _ptr(g_b1), _ptr(g_w2), _ptr(g_lw), _ptr(g_lb)
     keep = _fuse_updates(s, (("sgd_w1", w1, s.acc_w1), ("sgd_w2", w2, s.acc_w2)))
-    out = _bwd_finish(b, s, ctx, saved, L_.lib().afft_mlp_sublayer_bwd, "mlp_sublayer_bwd",
-                      ready=(w2, b.bias_ready, w1, b1, ln_w, ln_b), grads=(g_lw, g_lb, g_w1, g_b1, g_w2, b.g_bias),
-                      tap=("mlp_bwd", dict(hidden=hidden, w1=w1, w2=w2, x=x)))
-    return out + (None,) * 5      # eps, gelu, conv1d, pre_ln, drop
+    return _bwd_finish(b, s, ctx, saved, L_.lib().afft_mlp_sublayer_bwd, "mlp_sublayer_bwd",
+                       ready=(w2, b.bias_ready, w1, b1, ln_w, ln_b), grads=(g_lw, g_lb, g_w1, g_b1, g_w2, b.g_bias),
+                       tap=("mlp_bwd", dict(hidden=hidden, w1=w1, w2=w2, x=x)))
 
 
 def _cross_fwd_c(ctx, x, mem, nq_w, nq_b, nkv_w, nkv_b, w_q, w_k, w_v, w_proj, b_proj, L, H, mask, eps, scale, drop):
@@ -1021,7 +1021,80 @@ def _cross_bwd_c(ctx, dy):
     out = _bwd_finish(b, s, ctx, saved, L_.lib().afft_cross_attn_sublayer_bwd, "cross_attn_sublayer_bwd",
                       ready=(w_proj, b.bias_ready, w_q, w_k, w_v, nkv_w, nkv_b, nq_w, nq_b),
                       grads=(g_qw, g_qb, g_kw, g_kb, g_q, g_k, g_v, g_wp, b.g_bias))
-    return out[:1] + (dmem,) + out[1:] + (None,) * 10      # L, H, mask, eps, pre_ln, scale, drop, b_q, b_k, b_v
+    return out[:1] + (dmem,) + out[1:]
+
+
+# --------------------------------------------------------------------------- call-by-call path: one ops.* call at a time
+# The same sequences for what the composite entry points do not take (tensor masks, more than ATTN_SHORT_MAX tokens, post-LN and bare
+# modules, widths off the 64 grid, fp32 / bf16x3, the CPU double of afft_amd.ops).  The helpers below are the halves the three Functions
+# share, as _fwd_call / _bwd_begin / _bwd_finish are for the composite path; the order of steps inside each carries meaning, see there.
+_ATTN_NARGS, _ATTN_BIAS_AT = 18, 17       # AttnSublayer.forward: how many arguments, and which of them is `bias`
+_MLP_NARGS = 12                           # MLPSublayer.forward
+_CROSS_NARGS, _CROSS_BIAS_AT = 22, 21     # CrossAttnSublayer.forward (b_q, b_k, b_v sit right before `bias`)
+
+
+def _pad(grads: tuple, n: int) -> tuple:
+    """the gradients a backward computed (either path), padded with None to the n forward arguments of its Function"""
+    return grads + (None,) * (n - len(grads))
+
+
+def _cbc_ln_in(ctx, x: Tensor, w, b, eps, pre_ln: bool):
+    """The opening of a call-by-call forward: (LN(x) as a GEMM operand, mean, rstd); a bare module (no norm, no residual) gets x itself.
+    ctx: the Function's context when x is the residual stream (who produced x is looked up now), None for cross-attention's memory."""
+    R, d = x.shape
+    if ctx is not None:
+        ctx.up = _upstream_of(x) if pre_ln else None
+    mean, rstd = _stats(R if pre_ln else 0, x.device)
+    if not pre_ln:
+        return to_act(x), mean, rstd
+    xn = Act(R, d, x.device)
+    ops.layernorm_fwd(x, w, b, eps, xn.live, mean, rstd)
+    return xn, mean, rstd
+
+
+def _cbc_out(x: Tensor, a: Act, W: Tensor, conv1d: bool, bias, pre_ln: bool, drop, d_out: int) -> Tensor:
+    """The close of a call-by-call forward: y = x + drop(a W + bias) (bare module: no residual), and who produced y (_note_output)"""
+    y = torch.empty(a.rows, d_out, dtype=torch.float32, device=x.device)
+    od = _out_drop(drop)
+    _lin_fwd(a, W, conv1d, y, bias=bias, residual=x if pre_ln else None, drop=od)
+    _note_output(y, od, bias)
+    return y
+
+
+def _cbc_bwd_open(dy: Tensor, drop, bias, a_out: Act, W_out: Tensor, conv1d: bool):
+    """The opening of a call-by-call backward: (dy, its GEMM operand dya, gradient of W_out, gradient of the output bias).  The hand-over
+    for dy is taken BEFORE the side stream is entered: the cast that stands in for a missing one belongs on the main stream, where the
+    dgrad chain reads it; the output projection's weight and bias gradients then run beside that chain."""
+    dy = dy.contiguous()
+    od = _out_drop(drop)
+    sh = _take_shadow(dy, od, bias)
+    dya = sh.act if sh is not None else to_act(dy, od)
+    with _Side(dy.device):
+        g_w = _wgrad(dya, a_out, W_out, conv1d)
+        g_b = _accept_bias(sh) if sh is not None else _bgrad(dy if od is None else dya.live, bias)
+    return dy, dya, g_w, g_b
+
+
+def _cbc_bwd_close(ctx, dz: Act, W_in: Tensor, conv1d: bool, x: Tensor, ln_w, ln_b, mean, rstd, dy: Tensor, pre_ln: bool, mem_ln=None):
+    """The close of a call-by-call backward, from dz, the gradient of the input projection's output: (dx, gradient of ln_w, of ln_b).
+    mem_ln = (dmkv, mem, nkv_w, nkv_b, mean, rstd) of cross-attention's memory: (dmem, gradient of nkv_w, of nkv_b) follow.  The memory
+    LayerNorm's backward comes BEFORE the one of x: that one adds dy, leaves the hand-over for the sub-layer upstream (ctx.up) in the slot
+    and notifies last (first norm of the forward, last in bucket order).  Then the side stream is joined and the notifications go out."""
+    R, d = x.shape
+    if pre_ln:
+        dxn = Act(R, d, x.device)
+        _lin_dgrad(dz, W_in, conv1d, dxn.live)
+        dmem = _ln_bwd(*mem_ln, dx_in=None) if mem_ln is not None else ()
+        dx, g_lw, g_lb = _ln_bwd(dxn.live, x, ln_w, ln_b, mean, rstd, dx_in=dy, up=ctx.up)
+    else:
+        dx = torch.empty(R, d, dtype=torch.float32, device=x.device)
+        _lin_dgrad(dz, W_in, conv1d, dx)
+        g_lw = g_lb = None
+        dmem = (mem_ln[0], None, None) if mem_ln is not None else ()
+    join_side(x.device)
+    ctx.acts = None
+    flush_ready()
+    return (dx, g_lw, g_lb) + dmem
 
 
 # --------------------------------------------------------------------------- pre-LN self-attention sub-layer
@@ -1051,27 +1124,19 @@ class AttnSublayer(torch.autograd.Function):
             bias = mask_bias(mask)
         if not _mask_is_tensor(mask) and L <= ATTN_SHORT_MAX and _composite_ok(x, pre_ln, d) and _attn_core_ok(L, hd):
             return _attn_fwd_c(ctx, x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, L, H, mask, eps, conv1d, scale, drop, probs_out, take)
-        ctx.up = _upstream_of(x) if pre_ln else None
-        mean, rstd = _stats(R if pre_ln else 0, dev)
-        if pre_ln:
-            xn = Act(R, d, dev)
-            ops.layernorm_fwd(x, ln_w, ln_b, eps, xn.live, mean, rstd)
-        else:  # bare Attention module (models/transformerblock.py:19-36): no norm, no residual
-            xn = to_act(x)
+        xn, mean, rstd = _cbc_ln_in(ctx, x, ln_w, ln_b, eps, pre_ln)
         qkv = Act(R, 3 * d, dev)
         _lin_fwd(xn, w_qkv, conv1d, qkv.live, bias=b_qkv)
         ao = Act(R, d, dev)
         probs = probs_out if probs_out is not None else torch.empty(nseq, H, L, L, dtype=torch.float32, device=dev)
         scale = float(scale) if scale else float(hd) ** -0.5
         _attention_fwd(qkv.cols(0, d), qkv.cols(d, 2 * d), qkv.cols(2 * d, 3 * d), nseq, L, H, hd, scale, mask, ao.live, probs, drop, bias)
-        ctx.attn_bias = bias if len(ctx.needs_input_grad) > 17 and ctx.needs_input_grad[17] else None
-        y = torch.empty(R, d, dtype=torch.float32, device=dev)
-        _lin_fwd(ao, w_proj, conv1d, y, bias=b_proj, residual=x if pre_ln else None, drop=_out_drop(drop))
+        ctx.attn_bias = bias if len(ctx.needs_input_grad) > _ATTN_BIAS_AT and ctx.needs_input_grad[_ATTN_BIAS_AT] else None
+        y = _cbc_out(x, ao, w_proj, conv1d, b_proj, pre_ln, drop, d)
         ctx.save_for_backward(x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, mean, rstd, probs)
         ctx.acts = (xn, qkv, ao)
         ctx.cfg = (L, H, scale, conv1d, pre_ln, drop)
         ctx.mark_non_differentiable(probs)
-        _note_output(y, _out_drop(drop), b_proj)
         return y, probs
 
     @staticmethod
@@ -1080,45 +1145,27 @@ class AttnSublayer(torch.autograd.Function):
         if dy is None:          # (set_materialize_grads(False)) nobody used y
             _drop_shadow()      # a hand-over meant for this backward and queued notifications must not outlive it
             flush_ready()
-            return (None,) * 18
+            return _pad((), _ATTN_NARGS)
         if ctx.composite:
-            return _attn_bwd_c(ctx, dy) + (None, None)
+            return _pad(_attn_bwd_c(ctx, dy), _ATTN_NARGS)
         x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, mean, rstd, probs = ctx.saved_tensors
         xn, qkv, ao = (_b16(t) for t in ctx.acts)
         L, H, scale, conv1d, pre_ln, drop = ctx.cfg
         R, d = x.shape
         nseq, hd = R // L, d // H
         dev = x.device
-        dy = dy.contiguous()
-        od = _out_drop(drop)
-        sh = _take_shadow(dy, od, b_proj)
-        dya = sh.act if sh is not None else to_act(dy, od)
-        with _Side(dev):
-            g_wp = _wgrad(dya, ao, w_proj, conv1d)
-            g_bp = _accept_bias(sh) if sh is not None else _bgrad(dy if od is None else dya.live, b_proj)
+        dy, dya, g_wp, g_bp = _cbc_bwd_open(dy, drop, b_proj, ao, w_proj, conv1d)
         dao = Act(R, d, dev)
         _lin_dgrad(dya, w_proj, conv1d, dao.live)
         dqkv = Act(R, 3 * d, dev)
         _attention_bwd(dao.live, qkv.cols(0, d), qkv.cols(d, 2 * d), qkv.cols(2 * d, 3 * d), probs, nseq, L, H, hd,
                        scale, dqkv.cols(0, d), dqkv.cols(d, 2 * d), dqkv.cols(2 * d, 3 * d), drop)
-        g_bias = None
-        if ctx.attn_bias is not None:
-            g_bias = _attention_bias_bwd(ctx.attn_bias, dao.live, qkv.cols(2 * d, 3 * d), probs, nseq, L, H, hd, drop)
+        g_bias = _attention_bias_bwd(ctx.attn_bias, dao.live, qkv.cols(2 * d, 3 * d), probs, nseq, L, H, hd, drop)
         with _Side(dev):
             g_wq = _wgrad(dqkv, xn, w_qkv, conv1d)
             g_bq = _bgrad(dqkv.live, b_qkv)
-        if pre_ln:
-            dxn = Act(R, d, dev)
-            _lin_dgrad(dqkv, w_qkv, conv1d, dxn.live)
-            dx, g_lw, g_lb = _ln_bwd(dxn.live, x, ln_w, ln_b, mean, rstd, dx_in=dy, up=ctx.up)
-        else:
-            dx = torch.empty(R, d, dtype=torch.float32, device=dev)
-            _lin_dgrad(dqkv, w_qkv, conv1d, dx)
-            g_lw = g_lb = None
-        join_side(dev)
-        ctx.acts = None
-        flush_ready()
-        return dx, g_lw, g_lb, g_wq, g_bq, g_wp, g_bp, None, None, None, None, None, None, None, None, None, None, g_bias
+        dx, g_lw, g_lb = _cbc_bwd_close(ctx, dqkv, w_qkv, conv1d, x, ln_w, ln_b, mean, rstd, dy, pre_ln)
+        return _pad((dx, g_lw, g_lb, g_wq, g_bq, g_wp, g_bp), _ATTN_BIAS_AT) + (g_bias,)
 
 
 # --------------------------------------------------------------------------- pre-LN MLP sub-layer
@@ -1134,57 +1181,33 @@ class MLPSublayer(torch.autograd.Function):
         ctx.composite = False
         if d_out == d and _composite_ok(x, pre_ln, d, hidden):
             return _mlp_fwd_c(ctx, x, ln_w, ln_b, w1, b1, w2, b2, eps, gelu, conv1d, hidden, drop)
-        ctx.up = _upstream_of(x) if pre_ln else None
-        mean, rstd = _stats(R if pre_ln else 0, dev)
-        if pre_ln:
-            xn = Act(R, d, dev)
-            ops.layernorm_fwd(x, ln_w, ln_b, eps, xn.live, mean, rstd)
-        else:  # bare MLP module (models/transformerblock.py:84-93)
-            xn = to_act(x)
+        xn, mean, rstd = _cbc_ln_in(ctx, x, ln_w, ln_b, eps, pre_ln)
         u, h = Act(R, hidden, dev), Act(R, hidden, dev)
         _lin_fwd(xn, w1, conv1d, h.live, bias=b1, act=_GELU[gelu][0], pre=u.live)
-        y = torch.empty(R, d_out, dtype=torch.float32, device=dev)
-        _lin_fwd(h, w2, conv1d, y, bias=b2, residual=x if pre_ln else None, drop=_out_drop(drop))
+        y = _cbc_out(x, h, w2, conv1d, b2, pre_ln, drop, d_out)
         ctx.save_for_backward(x, ln_w, ln_b, w1, b1, w2, b2, mean, rstd)
         ctx.acts = (xn, u, h)
         ctx.cfg = (gelu, conv1d, hidden, pre_ln, drop)
-        _note_output(y, _out_drop(drop), b2)
         return y
 
     @staticmethod
     @_in_backward_precision
     def backward(ctx, dy):
         if ctx.composite:
-            return _mlp_bwd_c(ctx, dy)
+            return _pad(_mlp_bwd_c(ctx, dy), _MLP_NARGS)
         x, ln_w, ln_b, w1, b1, w2, b2, mean, rstd = ctx.saved_tensors
         xn, u, h = (_b16(t) for t in ctx.acts)
         gelu, conv1d, hidden, pre_ln, drop = ctx.cfg
         R, d = x.shape
         dev = x.device
-        dy = dy.contiguous()
-        od = _out_drop(drop)
-        sh = _take_shadow(dy, od, b2)
-        dya = sh.act if sh is not None else to_act(dy, od)
-        with _Side(dev):
-            g_w2 = _wgrad(dya, h, w2, conv1d)
-            g_b2 = _accept_bias(sh) if sh is not None else _bgrad(dy if od is None else dya.live, b2)
+        dy, dya, g_w2, g_b2 = _cbc_bwd_open(dy, drop, b2, h, w2, conv1d)
         du = Act(R, hidden, dev)
         _lin_dgrad(dya, w2, conv1d, du.live, act=_GELU[gelu][1], aux=u.live)
         with _Side(dev):
             g_w1 = _wgrad(du, xn, w1, conv1d)
             g_b1 = _bgrad(du.live, b1)
-        if pre_ln:
-            dxn = Act(R, d, dev)
-            _lin_dgrad(du, w1, conv1d, dxn.live)
-            dx, g_lw, g_lb = _ln_bwd(dxn.live, x, ln_w, ln_b, mean, rstd, dx_in=dy, up=ctx.up)
-        else:
-            dx = torch.empty(R, d, dtype=torch.float32, device=dev)
-            _lin_dgrad(du, w1, conv1d, dx)
-            g_lw = g_lb = None
-        join_side(dev)
-        ctx.acts = None
-        flush_ready()
-        return dx, g_lw, g_lb, g_w1, g_b1, g_w2, g_b2, None, None, None, None, None
+        dx, g_lw, g_lb = _cbc_bwd_close(ctx, du, w1, conv1d, x, ln_w, ln_b, mean, rstd, dy, pre_ln)
+        return _pad((dx, g_lw, g_lb, g_w1, g_b1, g_w2, g_b2), _MLP_NARGS)
 
 
 # --------------------------------------------------------------------------- pre-LN cross-attention sub-layer
@@ -1209,15 +1232,8 @@ class CrossAttnSublayer(torch.autograd.Function):
                 and mem.stride(0) == d):
             return _cross_fwd_c(ctx, x, mem, nq_w, nq_b, nkv_w, nkv_b, w_q, w_k, w_v, w_proj, b_proj, L, H, mask, eps, scale,
                                 drop)
-        ctx.up = _upstream_of(x) if pre_ln else None
-        mq, rq = _stats(R if pre_ln else 0, dev)
-        mk, rk = _stats(R if pre_ln else 0, dev)
-        if pre_ln:
-            xq, mkv = Act(R, d, dev), Act(R, dm, dev)
-            ops.layernorm_fwd(x, nq_w, nq_b, eps, xq.live, mq, rq)
-            ops.layernorm_fwd(mem, nkv_w, nkv_b, eps, mkv.live, mk, rk)
-        else:  # bare CrossAttention module (models/transformerblock.py:56-76)
-            xq, mkv = to_act(x), to_act(mem)
+        xq, mq, rq = _cbc_ln_in(ctx, x, nq_w, nq_b, eps, pre_ln)
+        mkv, mk, rk = _cbc_ln_in(None, mem, nkv_w, nkv_b, eps, pre_ln)
         q, k, v = Act(R, d, dev), Act(R, d, dev), Act(R, d, dev)
         _lin_fwd(xq, w_q, False, q.live, bias=b_q)
         _lin_fwd(mkv, w_k, False, k.live, bias=b_k)
@@ -1226,41 +1242,31 @@ class CrossAttnSublayer(torch.autograd.Function):
         probs = torch.empty(nseq, H, L, L, dtype=torch.float32, device=dev)
         scale = float(scale) if scale else float(hd) ** -0.5
         _attention_fwd(q.live, k.live, v.live, nseq, L, H, hd, scale, mask, ao.live, probs, drop, bias)
-        ctx.attn_bias = bias if len(ctx.needs_input_grad) > 21 and ctx.needs_input_grad[21] else None
-        y = torch.empty(R, d, dtype=torch.float32, device=dev)
-        _lin_fwd(ao, w_proj, False, y, bias=b_proj, residual=x if pre_ln else None, drop=_out_drop(drop))
+        ctx.attn_bias = bias if len(ctx.needs_input_grad) > _CROSS_BIAS_AT and ctx.needs_input_grad[_CROSS_BIAS_AT] else None
+        y = _cbc_out(x, ao, w_proj, False, b_proj, pre_ln, drop, d)
         ctx.save_for_backward(x, mem, nq_w, nq_b, nkv_w, nkv_b, w_q, w_k, w_v, w_proj, b_proj, mq, rq, mk, rk, probs)
         ctx.acts = (xq, mkv, q, k, v, ao)
         ctx.cfg = (L, H, scale, pre_ln, drop)
         ctx.qkv_b = (b_q, b_k, b_v)
-        _note_output(y, _out_drop(drop), b_proj)
         return y
 
     @staticmethod
     @_in_backward_precision
     def backward(ctx, dy):
         if ctx.composite:
-            return _cross_bwd_c(ctx, dy) + (None,)
+            return _pad(_cross_bwd_c(ctx, dy), _CROSS_NARGS)
         (x, mem, nq_w, nq_b, nkv_w, nkv_b, w_q, w_k, w_v, w_proj, b_proj, mq, rq, mk, rk, probs) = ctx.saved_tensors
         xq, mkv, q, k, v, ao = (_b16(t) for t in ctx.acts)
         L, H, scale, pre_ln, drop = ctx.cfg
         R, d = x.shape
         nseq, hd = R // L, d // H
         dev = x.device
-        dy = dy.contiguous()
-        od = _out_drop(drop)
-        sh = _take_shadow(dy, od, b_proj)
-        dya = sh.act if sh is not None else to_act(dy, od)
-        with _Side(dev):
-            g_wp = _wgrad(dya, ao, w_proj, False)
-            g_bp = _accept_bias(sh) if sh is not None else _bgrad(dy if od is None else dya.live, b_proj)
+        dy, dya, g_wp, g_bp = _cbc_bwd_open(dy, drop, b_proj, ao, w_proj, False)
         dao = Act(R, d, dev)
         _lin_dgrad(dya, w_proj, False, dao.live)
         dq, dk, dv = Act(R, d, dev), Act(R, d, dev), Act(R, d, dev)
         _attention_bwd(dao.live, q.live, k.live, v.live, probs, nseq, L, H, hd, scale, dq.live, dk.live, dv.live, drop)
-        g_bias = None
-        if ctx.attn_bias is not None:
-            g_bias = _attention_bias_bwd(ctx.attn_bias, dao.live, v.live, probs, nseq, L, H, hd, drop)
+        g_bias = _attention_bias_bwd(ctx.attn_bias, dao.live, v.live, probs, nseq, L, H, hd, drop)
         b_q, b_k, b_v = ctx.qkv_b
         with _Side(dev):
             g_q = _wgrad(dq, xq, w_q, False)
@@ -1272,19 +1278,10 @@ class CrossAttnSublayer(torch.autograd.Function):
         dmkv = torch.empty(R, mem.shape[1], dtype=torch.float32, device=dev)
         _lin_dgrad(dk, w_k, False, dmkv)
         _lin_dgrad(dv, w_v, False, dmkv, accumulate=True)
-        if pre_ln:
-            dxq = Act(R, d, dev)
-            _lin_dgrad(dq, w_q, False, dxq.live)
-            dmem, g_kw, g_kb = _ln_bwd(dmkv, mem, nkv_w, nkv_b, mk, rk, dx_in=None)
-            dx, g_qw, g_qb = _ln_bwd(dxq.live, x, nq_w, nq_b, mq, rq, dx_in=dy, up=ctx.up)
-        else:
-            dx = torch.empty(R, d, dtype=torch.float32, device=dev)
-            _lin_dgrad(dq, w_q, False, dx)
-            dmem, g_qw, g_qb, g_kw, g_kb = dmkv, None, None, None, None
-        join_side(dev)
-        ctx.acts = None
-        flush_ready()
-        return dx, dmem, g_qw, g_qb, g_kw, g_kb, g_q, g_k, g_v, g_wp, g_bp, None, None, None, None, None, None, None, g_bq, g_bk, g_bv, g_bias
+        dx, g_qw, g_qb, dmem, g_kw, g_kb = _cbc_bwd_close(ctx, dq, w_q, False, x, nq_w, nq_b, mq, rq, dy, pre_ln,
+                                                          mem_ln=(dmkv, mem, nkv_w, nkv_b, mk, rk))
+        grads = (dx, dmem, g_qw, g_qb, g_kw, g_kb, g_q, g_k, g_v, g_wp, g_bp)
+        return _pad(grads, _CROSS_BIAS_AT - 3) + (g_bq, g_bk, g_bv, g_bias)
 
 
 # --------------------------------------------------------------------------- plain linear (mapping, enc/dec, classifier)
