@@ -103,7 +103,7 @@ class FlatParams:
                 p.data = self.flat_p[o:o + n].view(p.shape)
                 p.grad = self.flat_g[o:o + n].view(p.shape)
             if self.flat_p16 is not None:
-                ops.cast(self.flat_p.view(off // 64, 64), self.flat_p16.view(off // 64, 64))
+                self._derive(self.flat_p16)
                 for p, o in zip(self.params, self.offsets):
                     if self.owns_image(p):
                         pk = None
@@ -127,20 +127,24 @@ class FlatParams:
         """the FP16 images exist once the precision is 'fp16x2' (called at construction and when a step begins)"""
         if self.flat_h16 is not None or rt.precision() != "fp16x2" or not self.flat_p.is_cuda:
             return
-        n = self.total
-        self.flat_h16 = torch.zeros(n, dtype=torch.float16, device=self.flat_p.device)
-        with torch.no_grad():
-            ops.cast(self.flat_p.view(n // 64, 64), self.flat_h16.view(n // 64, 64))
+        self.flat_h16 = torch.zeros(self.total, dtype=torch.float16, device=self.flat_p.device)
+        self._derive(self.flat_h16)
         if rt.lo8():
-            self.flat_p8 = torch.zeros(n, dtype=torch.uint8, device=self.flat_p.device)
-            with torch.no_grad():
-                ops.quant_e4m3(self.flat_p.view(n // 64, 64), 256.0, self.flat_p8.view(n // 64, 64))
+            self.flat_p8 = torch.zeros(self.total, dtype=torch.uint8, device=self.flat_p.device)
+            self._derive(self.flat_p8)
         for p, o in zip(self.params, self.offsets):
-            img = getattr(p, "_afft_img", None)
-            if img is not None and img.external and p.dim() == 2:
+            if rt.image_external(p) and p.dim() == 2:
                 rt.adopt_weight_f16(p, self.flat_h16[o:o + p.numel()].view(p.shape))
                 if self.flat_p8 is not None:
                     rt.adopt_weight_f8(p, self.flat_p8[o:o + p.numel()].view(p.shape))
+
+    def _derive(self, image: Optional[Tensor]):
+        """fill one flat image buffer (None: there is none) from the fp32 masters: a cast for the 16-bit kinds, e4m3(2^8 p) for the bytes"""
+        with torch.no_grad():
+            if image is not None and image.dtype == torch.uint8:
+                ops.quant_e4m3(self.flat_p.view(-1, 64), 256.0, image.view(-1, 64))
+            elif image is not None:
+                ops.cast(self.flat_p.view(-1, 64), image.view(-1, 64))
 
     def h16(self, s: int = 0, e: Optional[int] = None) -> Optional[Tensor]:
         return None if self.flat_h16 is None else self.flat_h16[s:self.total if e is None else e]
@@ -152,14 +156,9 @@ class FlatParams:
         """Re-derive every bf16 image from the fp32 masters (after the masters were written from outside: a parameter
         broadcast, a checkpoint load into the flat buffer)."""
         if self.flat_p16 is not None:
-            n = self.total
-            with torch.no_grad():
-                ops.cast(self.flat_p.view(n // 64, 64), self.flat_p16.view(n // 64, 64))
-                if self.flat_h16 is not None:
-                    ops.cast(self.flat_p.view(n // 64, 64), self.flat_h16.view(n // 64, 64))
-                if self.flat_p8 is not None:
-                    ops.quant_e4m3(self.flat_p.view(n // 64, 64), 256.0, self.flat_p8.view(n // 64, 64))
-            self.refresh_packed(0, n)
+            for image in (self.flat_p16, self.flat_h16, self.flat_p8):
+                self._derive(image)
+            self.refresh_packed(0, self.total)
         rt.invalidate_weight_images()
 
     def refresh_packed(self, s: int, e: int, skip=()):
@@ -654,9 +653,8 @@ class _FusedEpilogue:
         from . import _lib as L_
         flat, fused = self.flat, {}
         for p, o in zip(flat.params, flat.offsets):
-            img = getattr(p, "_afft_img", None)
             if (p.dim() == 2 and id(p) in rt.SINK.composite_weights and rt.SINK.touch_count.get(id(p), 0) == 1
-                    and img is not None and img.external and p.numel() >= rt.fuse_min_elems()):
+                    and rt.image_external(p) and p.numel() >= rt.fuse_min_elems()):
                 d = L_.SgdFused()
                 d.p, d.buf, d.p_bf16 = flat.flat_p.data_ptr() + 4 * o, self.opt.buf.data_ptr() + 4 * o, flat.flat_p16.data_ptr() + 2 * o
                 fused[id(p)] = d
@@ -737,7 +735,7 @@ class _FusedEpilogue:
         d = self._fused.get(id(p))
         if d is not None:
             lr, wd = self.opt.hyper_of(self._index[id(p)])
-            d.p_pk16 = p._afft_img.pk.data_ptr() if rt.packed_live(p) else None      # only images a forward GEMM uses are kept fresh
+            d.p_pk16 = rt.packed_ptr(p)     # only images a forward GEMM uses are kept fresh
             h16 = self.flat.flat_h16
             d.p_f16 = (h16.data_ptr() + 2 * self._offset_of(p)) if h16 is not None else None
             d.p_f8 = (self.flat.flat_p8.data_ptr() + self._offset_of(p)) if self.flat.flat_p8 is not None else None

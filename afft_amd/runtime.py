@@ -21,7 +21,7 @@ from typing import Dict, Optional
 
 import torch
 
-from . import ops
+from . import _lib as L_, ops
 
 Tensor = torch.Tensor
 
@@ -100,12 +100,32 @@ def pad64(n: int) -> int:
     return (n + 63) // 64 * 64
 
 
-# --------------------------------------------------------------------------- bf16 weight images
+# --------------------------------------------------------------------------- weight images
+class _Slot:
+    """One derived image of a parameter: `t` the tensor (None: none yet), `version` the parameter version it was derived at (-1:
+    stale), `external`: it is a view of the flat buffers that the optimizer kernels keep fresh (parallel.FlatParams), so only a
+    write from outside -- which moves the version counter -- makes it stale.  The packed slot is also `live` once a forward GEMM
+    wanted it."""
+    __slots__ = ("t", "version", "external", "live")
+
+    def __init__(self):
+        self.t, self.version, self.external, self.live = None, -1, False, False
+
+
 class _WImage:
-    __slots__ = ("version", "ptr", "w", "external", "pk", "pk_live", "pk_version", "h", "h_version", "h_external", "e", "e_version",
-                 "e_external")
+    """The record a parameter carries as `_afft_img`: the storage it was built for and one slot per image kind, all empty."""
+    __slots__ = ("ptr", "bf16", "f16", "e4m3", "packed")
+
+    def __init__(self, p: Tensor):
+        self.ptr = p.data_ptr()
+        self.bf16, self.f16, self.e4m3, self.packed = _Slot(), _Slot(), _Slot(), _Slot()
 
 
+_ROW_MAJOR = {      # kind: dtype of its zero-filled buffer [pad64(rows), pad64(cols)], and the kernel that fills it from the master
+    "bf16": (torch.bfloat16, lambda p, t: ops.cast(p.detach(), t[:p.shape[0], :p.shape[1]])),
+    "f16": (torch.float16, lambda p, t: ops.cast(p.detach(), t[:p.shape[0], :p.shape[1]])),
+    "e4m3": (torch.uint8, lambda p, t: ops.quant_e4m3(p.detach(), 256.0, t)),       # (zero-fills the padding itself)
+}
 _wlist: list = []   # weak references to parameters that own an image (for invalidate_weight_images)
 
 
@@ -117,60 +137,60 @@ def _register(p: Tensor):
         p._afft_listed = True
 
 
+def _new_record(p: Tensor) -> _WImage:
+    p._afft_img = img = _WImage(p)
+    _register(p)
+    return img
+
+
+def _fill(p: Tensor, s: _Slot, kind: str):
+    dtype, fill = _ROW_MAJOR[kind]
+    if s.t is None:
+        s.t = torch.zeros(pad64(p.shape[0]), pad64(p.shape[1]), dtype=dtype, device=p.device)
+    with torch.no_grad():
+        fill(p, s.t)
+    s.version = p._version
+
+
+def _row_major(p: Tensor, kind: str) -> Tensor:
+    """THE refresh rule.  The record is replaced, every slot with it, when the parameter has none or has moved (storage, device).
+    Then the bf16 image -- the backward pass reads it whatever the forward's format -- and the image asked for are each brought
+    up to date, in that order: a slot whose version lags the parameter's is filled again from the fp32 master, into a zeroed
+    padded buffer of its own if it has no tensor yet.  An external slot is never behind after an optimizer kernel (they write
+    through raw pointers); when it is, the parameter was written from outside (load_state_dict, p.copy_) and the adopted view
+    itself is re-derived."""
+    img = getattr(p, "_afft_img", None)
+    if img is None or img.ptr != p.data_ptr() or img.bf16.t is None or img.bf16.t.device != p.device:
+        img = _new_record(p)
+    s = img.bf16
+    if s.version != p._version:
+        _fill(p, s, "bf16")
+    if kind != "bf16":
+        s = getattr(img, kind)
+        if s.version != p._version:
+            _fill(p, s, kind)
+    return s.t
+
+
+def _adopt(p: Tensor, kind: str, view: Tensor):
+    s = getattr(p._afft_img, kind)
+    s.t, s.version, s.external = view, p._version, True
+
+
 def weight_images(p: Tensor) -> Tensor:
     """w16: the bf16 image [pad64(rows), pad64(cols)] of a 2-D fp32 parameter, zero padded (the k-contiguous "NT" operand of
     the forward GEMM of nn.Linear / the data-gradient GEMM of HF Conv1D, the k-strided "NN" operand of the other two).
     Refreshed by one cast kernel when the parameter's version counter or storage changes; parameters re-homed by
     afft_amd.parallel.FlatParams have it written by the optimizer kernels (`external`)."""
-    img = getattr(p, "_afft_img", None)
-    ver = p._version
-    if img is None or img.ptr != p.data_ptr() or img.w.device != p.device:
-        img = _WImage()
-        rows, cols = p.shape
-        img.w = torch.zeros(pad64(rows), pad64(cols), dtype=torch.bfloat16, device=p.device)
-        img.version = -1
-        img.external = False
-        img.pk = None
-        img.pk_live = False
-        img.pk_version = -1
-        img.h = None
-        img.h_version = -1
-        img.h_external = False
-        img.e = None
-        img.e_version = -1
-        img.e_external = False
-        img.ptr = p.data_ptr()
-        p._afft_img = img
-        _register(p)
-    if img.version != ver:
-        with torch.no_grad():
-            ops.cast(p.detach(), img.w[:p.shape[0], :p.shape[1]])
-        img.version = ver
-    return img.w
+    return _row_major(p, "bf16")
 
 
 def weight_f16(p: Tensor) -> Tensor:
     """FP16 image [pad64(rows), pad64(cols)] of a 2-D fp32 parameter: the B operand of the fp16 two-pass forward GEMMs ('fp16x2'
     precision; the weight is rounded ONCE to fp16, the activation side carries hi + lo).  A parameter homed in the flat buffers
-    (parallel.FlatParams) has its image there, written by the optimizer kernels beside the bf16 one (FlatParams.f16_images);
+    (parallel.FlatParams) has its image there, written by the optimizer kernels beside the bf16 one (FlatParams.ensure_f16);
     any other parameter gets a cast image that is redone when its version counter or storage changes."""
-    weight_images(p)                      # creates / validates the record (and the bf16 image the backward pass reads)
-    img = p._afft_img
-    if img.h_external:
-        if img.h_version != p._version:   # written from outside (load_state_dict, p.copy_): re-derive, as weight_images does
-            with torch.no_grad():
-                ops.cast(p.detach(), img.h)
-            img.h_version = p._version
-        return img.h
-    if img.h is None:
-        rows, cols = p.shape
-        img.h = torch.zeros(pad64(rows), pad64(cols), dtype=torch.float16, device=p.device)
-        img.h_version = -1
-    if img.h_version != p._version:
-        with torch.no_grad():
-            ops.cast(p.detach(), img.h[:p.shape[0], :p.shape[1]])
-        img.h_version = p._version
-    return img.h
+    return _row_major(p, "f16")
 
 
 _LO8 = True
@@ -247,34 +267,16 @@ def one_pass_flags(conv1d: bool, width: int, first: str, second: str, core: str 
 def weight_f8(p: Tensor) -> Tensor:
     """e4m3 byte image e4m3(2^8 p) [pad64(rows), pad64(cols)] of a 2-D parameter (afft_gemm_t.b8): in the flat buffers when the parameter
     is homed there (written by the optimizer kernels), else a quantised copy redone when the parameter changes"""
-    weight_images(p)
-    img = p._afft_img
-    if img.e_external:
-        if img.e_version != p._version:
-            with torch.no_grad():
-                ops.quant_e4m3(p.detach(), 256.0, img.e)
-            img.e_version = p._version
-        return img.e
-    if img.e is None:
-        rows, cols = p.shape
-        img.e = torch.zeros(pad64(rows), pad64(cols), dtype=torch.uint8, device=p.device)
-        img.e_version = -1
-    if img.e_version != p._version:
-        with torch.no_grad():
-            ops.quant_e4m3(p.detach(), 256.0, img.e)
-        img.e_version = p._version
-    return img.e
+    return _row_major(p, "e4m3")
 
 
 def adopt_weight_f8(p: Tensor, view8: Tensor):
-    img = p._afft_img
-    img.e, img.e_version, img.e_external = view8, p._version, True
+    _adopt(p, "e4m3", view8)
 
 
 def adopt_weight_f16(p: Tensor, view16: Tensor):
     """use `view16` (fp16, the shape of p, kept fresh by the optimizer kernels) as p's FP16 image"""
-    img = p._afft_img
-    img.h, img.h_version, img.h_external = view16, p._version, True
+    _adopt(p, "f16", view16)
 
 
 def weight_split(p: Tensor):
@@ -310,71 +312,61 @@ def weight_packed(p: Tensor, rows: Optional[int] = None) -> Optional[Tensor]:
     dispatcher says it would use it for a problem of this size (afft_gemm_packed_wanted: at cfg2 the fuser's projection and fc2
     weights, a fifth of the parameters).  rows = None: only report a live image."""
     img = getattr(p, "_afft_img", None)
-    if img is None or not img.external or img.pk is None:
+    if img is None or not img.bf16.external or img.packed.t is None:
         return None
-    if not img.pk_live:
-        if rows is None or p.dim() != 2:
+    s = img.packed
+    if not s.live:
+        if rows is None or p.dim() != 2 or not L_.lib().afft_gemm_packed_wanted(int(rows), int(p.shape[0]), int(p.shape[1])):
             return None
-        from . import _lib as L_, ops
-        if not L_.lib().afft_gemm_packed_wanted(int(rows), int(p.shape[0]), int(p.shape[1])):
-            return None
+        s.live = True                                # its version is -1: packed just below
+    if s.version != p._version:
+        # first use (forward pass, current stream: the parameter is at rest), or the parameter was written from outside the
+        # optimizer kernels, exactly as for the row-major images
         with torch.no_grad():
-            ops.pack_weight(p.detach(), img.pk)      # forward pass, current stream: the parameter is at rest
-        img.pk_live = True
-        img.pk_version = p._version
-    elif img.pk_version != p._version:
-        # the parameter was written from outside the optimizer kernels (model.load_state_dict, p.copy_ into the flat views: they
-        # bump the version counter; the optimizer kernels write through raw pointers and keep every image fresh themselves):
-        # re-pack, exactly as weight_images() re-casts the row-major image
-        from . import ops
-        with torch.no_grad():
-            ops.pack_weight(p.detach(), img.pk)
-        img.pk_version = p._version
-    return img.pk
+            ops.pack_weight(p.detach(), s.t)
+        s.version = p._version
+    return s.t
 
 
 def packed_live(p: Tensor) -> bool:
     img = getattr(p, "_afft_img", None)
-    return bool(img is not None and img.external and img.pk is not None and img.pk_live)
+    return img is not None and img.packed.live        # (only weight_packed sets it: the record is external and has the slot)
+
+
+def packed_ptr(p: Tensor) -> Optional[int]:
+    """device address of p's packed image when it is live (what the fused optimizer epilogue keeps fresh), else None"""
+    return p._afft_img.packed.t.data_ptr() if packed_live(p) else None
+
+
+def image_external(p: Tensor) -> bool:
+    """p's images are views of the flat buffers, kept fresh by the optimizer kernels (adopt_weight_image)"""
+    img = getattr(p, "_afft_img", None)
+    return img is not None and img.bf16.external
 
 
 def adopt_weight_image(p: Tensor, view16: Tensor, packed: Optional[Tensor] = None):
     """Use `view16` (bf16, same shape as p, both dims multiples of 64, kept fresh by the optimizer kernel) as p's MFMA image;
     `packed`: the fragment-packed copy of view16 (ops.pack_weight, afft_gemm_t.b_packed), kept fresh by the same optimizer paths
-    (parallel.FlatParams.refresh_packed)."""
-    img = _WImage()
-    img.w = view16
-    img.pk = packed
-    img.pk_live = False
-    img.pk_version = -1
-    img.h = None
-    img.h_version = -1
-    img.h_external = False
-    img.e = None
-    img.e_version = -1
-    img.e_external = False
-    img.version = p._version
-    img.external = True
-    img.ptr = p.data_ptr()
-    p._afft_img = img
-    _register(p)
+    (parallel.FlatParams.refresh_packed) once it is live.  Starts a fresh record: the other images are adopted after this one."""
+    img = _new_record(p)
+    _adopt(p, "bf16", view16)
+    if packed is not None:
+        img.packed.t, img.packed.external = packed, True
 
 
 def invalidate_weight_images(include_external: bool = False):
+    """Mark the images stale that nobody else keeps fresh -- the cast ones, after an update through raw pointers -- or, with
+    include_external, every image (the masters were written behind the version counter); drop the bf16x3 / fp16x2 splits; forget
+    parameters that died or own nothing any more."""
     alive = []
     for r in _wlist:
         p = r()
         if p is None:
             continue
         img = getattr(p, "_afft_img", None)
-        if img is not None and (include_external or not img.external):
-            img.version = -1
-        if img is not None and (include_external or not img.h_external):
-            img.h_version = -1
-        if img is not None and (include_external or not img.e_external):
-            img.e_version = -1
-        if img is not None and include_external:
-            img.pk_version = -1
+        for s in (img.bf16, img.f16, img.e4m3, img.packed) if img is not None else ():
+            if include_external or not s.external:
+                s.version = -1
         if getattr(p, "_afft_split", None) is not None:
             p._afft_split = None
         if img is not None or hasattr(p, "_afft_split"):

@@ -271,6 +271,23 @@ def cast(src, dst, dst_t=None, zero_pad=False, drop=None):
 
 
 @torch.no_grad()
+def quant_e4m3(src, scale, dst, hi=None):
+    """stand-in: the e4m3 bytes of scale * src in the corner of dst, zero outside (rounding and saturation are torch's, not the kernel's)"""
+    assert hi is None
+    rows, cols = src.shape
+    dst.zero_()
+    dst[:rows, :cols].copy_((scale * src).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).view(torch.uint8))
+    return dst
+
+
+@torch.no_grad()
+def pack_weight(w, dst):
+    """stand-in: the bf16 elements of w in row-major order (the fragment order of the kernel is not modelled)"""
+    dst.view(-1).copy_(w.reshape(-1))
+    return dst
+
+
+@torch.no_grad()
 def assemble_tokens(feats, token, tok_stride_t, mod_embed, BT, T, d, X):
     if tok_stride_t:
         X[:, 0].copy_(token.reshape(-1, d)[torch.arange(BT) % T])
@@ -439,7 +456,7 @@ def softmax_rows(x, y):
     return y
 
 
-_NAMES = ["Split", "gemm", "layernorm_fwd", "layernorm_bwd", "attention_fwd", "attention_fwd_table", "attention_bwd", "softmax_ce", "softmax_ce_frames", "mse", "mse_loss", "mse_frames_bwd", "cast",
+_NAMES = ["Split", "gemm", "layernorm_fwd", "layernorm_bwd", "attention_fwd", "attention_fwd_table", "attention_bwd", "softmax_ce", "softmax_ce_frames", "mse", "mse_loss", "mse_frames_bwd", "cast", "quant_e4m3", "pack_weight",
           "assemble_tokens", "colsum", "gather_frames", "add_rows_periodic", "reduce_rows_periodic", "sgd_nesterov", "sgd_nesterov_runs", "loss_reduce", "loss_reduce_bwd", "sumsq", "clip_coef",
           "group_sum", "group_bcast", "act_bwd", "softmax_small_fwd", "softmax_small_bwd", "weighted_sum_fwd",
           "weighted_sum_bwd", "softmax_rows"]
