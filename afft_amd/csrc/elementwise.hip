@@ -420,10 +420,6 @@ extern "C" int afft_sgd_nesterov_runs2(float* p, const float* g, float* buf, voi
   AFFT_LAUNCH_CHECK();
   return 0;
 }
-extern "C" int afft_sgd_nesterov_runs(float* p, const float* g, float* buf, void* p_bf16, const int64_t* runs, int32_t nruns,
-                                      float lr, float mom, float wd, float gscale, int32_t first_step, void* stream_) {
-  return afft_sgd_nesterov_runs2(p, g, buf, p_bf16, nullptr, nullptr, runs, nruns, lr, mom, wd, gscale, first_step, nullptr, stream_);
-}
 
 namespace {
 // fp32 [rows, cols] -> fragment-packed bf16 image (include/afft_hip.h: afft_pack_weight).  One thread per 8-element fragment:
@@ -1114,8 +1110,4 @@ extern "C" int afft_sgd_nesterov2(float* p, const void* g, int32_t g_dtype, floa
                      gscale, gscale_dev, first_step, ok);
   AFFT_LAUNCH_CHECK();
   return 0;
-}
-extern "C" int afft_sgd_nesterov(float* p, const void* g, int32_t g_dtype, float* buf, void* p_bf16, int64_t n, float lr, float mom,
-                                 float wd, float gscale, const float* gscale_dev, int32_t first_step, void* stream_) {
-  return afft_sgd_nesterov2(p, g, g_dtype, buf, p_bf16, nullptr, nullptr, n, lr, mom, wd, gscale, gscale_dev, first_step, nullptr, stream_);
 }

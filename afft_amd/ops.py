@@ -561,6 +561,12 @@ def reduce_rows_periodic(src: Tensor, period: int, out: Tensor):
     return out
 
 
+def _check_images(p: Tensor, p_bf16: Optional[Tensor], p_f16: Optional[Tensor], p_f8: Optional[Tensor]):
+    """the optional bf16 / fp16 / e4m3 images of a flat parameter slice: one element per parameter, same offsets"""
+    for img, dtype in ((p_bf16, torch.bfloat16), (p_f16, torch.float16), (p_f8, torch.uint8)):
+        assert img is None or (img.dtype == dtype and img.numel() == p.numel() and img.is_contiguous())
+
+
 def sgd_nesterov(p: Tensor, g: Tensor, buf: Tensor, lr: float, mom: float, wd: float, gscale: float, first,
                  p_bf16: Optional[Tensor] = None, gscale_dev: Optional[Tensor] = None, p_f16: Optional[Tensor] = None,
                  p_f8: Optional[Tensor] = None, ok: Optional[Tensor] = None):
@@ -568,12 +574,7 @@ def sgd_nesterov(p: Tensor, g: Tensor, buf: Tensor, lr: float, mom: float, wd: f
     first: bool (first step) or the AFFT_SGD_* flag word (1 = first step, 2 = plain momentum instead of Nesterov);
     p_bf16 / p_f16: the bf16 / fp16 images of the updated weights (same element offsets as p)"""
     assert p.is_contiguous() and g.is_contiguous() and buf.is_contiguous()
-    if p_bf16 is not None:
-        assert p_bf16.dtype == torch.bfloat16 and p_bf16.numel() == p.numel() and p_bf16.is_contiguous()
-    if p_f16 is not None:
-        assert p_f16.dtype == torch.float16 and p_f16.numel() == p.numel() and p_f16.is_contiguous()
-    if p_f8 is not None:
-        assert p_f8.dtype == torch.uint8 and p_f8.numel() == p.numel() and p_f8.is_contiguous()
+    _check_images(p, p_bf16, p_f16, p_f8)
     L.check(L.lib().afft_sgd_nesterov2(_p(p), _p(g), _dt(g), _p(buf), _p(p_bf16), _p(p_f16), _p(p_f8), p.numel(), lr, mom, wd, gscale,
                                        _p(gscale_dev), int(first), _p(ok), _stream()), "sgd_nesterov")
 
@@ -596,12 +597,7 @@ def adam(p: Tensor, g: Tensor, m: Tensor, v: Tensor, lr: float, beta1: float, be
     in sgd_nesterov"""
     assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()
     assert p.dtype == m.dtype == v.dtype == step.dtype == torch.float32 and m.numel() == v.numel() == g.numel() == p.numel()
-    if p_bf16 is not None:
-        assert p_bf16.dtype == torch.bfloat16 and p_bf16.numel() == p.numel() and p_bf16.is_contiguous()
-    if p_f16 is not None:
-        assert p_f16.dtype == torch.float16 and p_f16.numel() == p.numel() and p_f16.is_contiguous()
-    if p_f8 is not None:
-        assert p_f8.dtype == torch.uint8 and p_f8.numel() == p.numel() and p_f8.is_contiguous()
+    _check_images(p, p_bf16, p_f16, p_f8)
     L.check(L.lib().afft_adam(_p(p), _p(g), _dt(g), _p(m), _p(v), _p(p_bf16), _p(p_f16), _p(p_f8), p.numel(), lr, beta1, beta2, eps,
                               wd, gscale, _p(gscale_dev), _p(step), L.ADAM_DECOUPLED if decoupled else 0, _p(ok), _stream()), "adam")
 

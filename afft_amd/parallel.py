@@ -22,7 +22,7 @@ import os
 import torch
 import torch.distributed as dist
 
-from . import ops, runtime as rt
+from . import _lib as L_, ops, runtime as rt
 
 Tensor = torch.Tensor
 
@@ -581,7 +581,7 @@ class FusedSGD(_FlatUpdate):
 
     def flags(self) -> int:
         """AFFT_SGD_* flag word of the update kernels (include/afft_hip.h)"""
-        return (1 if self.steps == 0 else 0) | (0 if self.nesterov else 2)
+        return (L_.SGD_FIRST_STEP if self.steps == 0 else 0) | (0 if self.nesterov else L_.SGD_PLAIN_MOMENTUM)
 
     def _update(self, s, e, grad, lr, wd, gscale, gscale_dev):
         flat = self.flat
@@ -650,7 +650,6 @@ class _FusedEpilogue:
         updated in the epilogue of its own weight-gradient GEMM (afft_sgd_fused_t): its gradient never goes to HBM and the
         per-bucket update kernel only walks what is left of the bucket (`runs`).  N = 1 only: with more ranks the summed
         gradient has to exist before the update."""
-        from . import _lib as L_
         flat, fused = self.flat, {}
         for p, o in zip(flat.params, flat.offsets):
             if (p.dim() == 2 and id(p) in rt.SINK.composite_weights and rt.SINK.touch_count.get(id(p), 0) == 1
@@ -739,7 +738,7 @@ class _FusedEpilogue:
             h16 = self.flat.flat_h16
             d.p_f16 = (h16.data_ptr() + 2 * self._offset_of(p)) if h16 is not None else None
             d.p_f8 = (self.flat.flat_p8.data_ptr() + self._offset_of(p)) if self.flat.flat_p8 is not None else None
-            d.lr, d.mom, d.wd, d.gscale, d.first_step = lr, self.opt.momentum, wd, 1.0, self.opt.flags() & 2
+            d.lr, d.mom, d.wd, d.gscale, d.first_step = lr, self.opt.momentum, wd, 1.0, self.opt.flags() & L_.SGD_PLAIN_MOMENTUM
             d.ok = self.opt.ok.data_ptr() if self.opt.ok is not None else None
         return d
 

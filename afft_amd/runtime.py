@@ -260,8 +260,8 @@ def one_pass_flags(conv1d: bool, width: int, first: str, second: str, core: str 
     if width < _ONE_PASS_MIN_DIM:
         return 0
     kind = "conv1d." if conv1d else "linear."
-    return ((4 if kind + first in _ONE_PASS else 0) | (8 if kind + second in _ONE_PASS else 0)      # AFFT_F16X2_ONE_PASS_1 | _2 | _ATTN
-            | (16 if core and kind + core in _ONE_PASS else 0))
+    return ((L_.F16X2_ONE_PASS_1 if kind + first in _ONE_PASS else 0) | (L_.F16X2_ONE_PASS_2 if kind + second in _ONE_PASS else 0)
+            | (L_.F16X2_ONE_PASS_ATTN if core and kind + core in _ONE_PASS else 0))
 
 
 def weight_f8(p: Tensor) -> Tensor:

@@ -15,6 +15,15 @@
  *     the calling thread's current HIP device); a workspace must not be shared by two streams;
  *   - return value 0 = success; non-zero = error, text via afft_last_error() (thread-local);
  *   - matrices are row-major with explicit element strides; dtype codes below.
+ *
+ * This header is the single statement of the ABI: afft_amd/_cabi.py reads it and the ctypes binding is derived from what it
+ * finds, so a new entry point needs no second declaration.  Outside comments and the preprocessor frame the reader accepts
+ * exactly three forms, and raises on anything else:
+ *   enum { AFFT_NAME = <integer>, ... };            and   #define AFFT_NAME <integer>
+ *   typedef struct [tag] { <field>; ... } name_t;   field = [const] type [*..] a, b, c   (no arrays, bit-fields, nested bodies)
+ *   <type> afft_*(<type> arg, ...);                 every argument named; (void) for none
+ * type = int | int32_t | int64_t | uint32_t | float | a struct defined above (by value), or a pointer to one of these, to void,
+ * uint8_t, a struct of this header (by name or `struct tag`) or to such a pointer; `const char*` as a return type only.
  */
 #ifndef AFFT_HIP_H
 #define AFFT_HIP_H
@@ -125,7 +134,7 @@ int afft_gemm_lo8_ok(int M, int N, int K);
 /* Nesterov-SGD update fused into the epilogue of the weight-gradient GEMM that produces the gradient (single-GPU training, no
  * gradient clipping, a weight that receives exactly one gradient contribution per step): element [m, n] of the result is the
  * gradient g of p[m * ldo + n] and is never stored;  g' = gscale*g + wd*p ; buf = mom*buf + g' (g' on the first step) ;
- * p -= lr*(g' + mom*buf) ; p_bf16 = bf16(p)  -- bit for bit what afft_sgd_nesterov computes from a stored gradient (one shared
+ * p -= lr*(g' + mom*buf) ; p_bf16 = bf16(p)  -- bit for bit what afft_sgd_nesterov2 computes from a stored gradient (one shared
  * device function).  p / buf / p_bf16 have the layout of the GEMM output (row stride ldo).  Saves the gradient's round trip
  * through HBM (8 of 26 bytes per parameter and step) and the separate update kernels.  The caller orders the launch behind the
  * kernels of the same step that still read p_bf16 (the data-gradient GEMM of the same layer). */
@@ -519,18 +528,14 @@ int afft_group_bcast(const float* dy, int32_t G, int32_t S, int64_t W, float sca
  *   g = gscale*g + wd*p ; buf = mom*buf + g ; p -= lr*(g + mom*buf) ; gscale = 1/world after a summing
  *   all-reduce; g may be fp32 or bf16 (bf16 gradient exchange).  p_bf16 (optional, same element offsets as p)
  *   receives the bf16 image of the updated weights: the GEMM operand copy is refreshed by the update itself.
- *   gscale_dev (optional device scalar) multiplies gscale: the gradient-clipping coefficient of afft_clip_coef. */
-int afft_sgd_nesterov(float* p, const void* g, int32_t g_dtype, float* buf, void* p_bf16, int64_t n, float lr, float mom,
-                      float wd, float gscale, const float* gscale_dev, int32_t first_step, void* stream);
-/* p_f16 (optional, same element offsets as p): the FP16 image of the updated weights ("fp16x2" forward operands), written
- * beside p_bf16 by afft_sgd_nesterov2 / afft_sgd_nesterov_runs2 -- otherwise the functions above. */
+ *   gscale_dev (optional device scalar) multiplies gscale: the gradient-clipping coefficient of afft_clip_coef.
+ *   p_f16 (optional, same element offsets as p): the FP16 image of the updated weights ("fp16x2" forward operands), written
+ *   beside p_bf16. */
 int afft_sgd_nesterov2(float* p, const void* g, int32_t g_dtype, float* buf, void* p_bf16, void* p_f16, void* p_f8, int64_t n, float lr,
                        float mom, float wd, float gscale, const float* gscale_dev, int32_t first_step, const float* ok, void* stream);      /* p_f8: e4m3(2^8 p) bytes; ok: see afft_sgd_fused_t.ok (NULL = always) */
 /* The same update over `nruns` separate runs of ONE set of flat buffers: runs = device array of nruns x {start, length}
  * (int64 elements, starts multiples of 4).  One launch for all the small parameters of a gradient bucket (LayerNorm
  * weights, biases, tokens) whose big neighbours are updated in their weight-gradient epilogues (afft_sgd_fused_t). */
-int afft_sgd_nesterov_runs(float* p, const float* g, float* buf, void* p_bf16, const int64_t* runs, int32_t nruns, float lr,
-                           float mom, float wd, float gscale, int32_t first_step, void* stream);
 int afft_sgd_nesterov_runs2(float* p, const float* g, float* buf, void* p_bf16, void* p_f16, void* p_f8, const int64_t* runs, int32_t nruns,
                             float lr, float mom, float wd, float gscale, int32_t first_step, const float* ok, void* stream);
 /* Adam / AdamW over one flat fp32 parameter buffer (conf/opt/optimizer/adam.yaml, adamW.yaml: torch.optim.Adam / AdamW with
