@@ -4,7 +4,7 @@
 // the scores are produced.  HBM-bound by construction (reads q,k,v once
 // through L1/L2, writes out once): attention is < 0.2 % of the path's FLOPs.
 //   softmax(q k^T * hd^-0.5 + mask) v : models/transformerblock.py:24-33,64-73 ; HF GPT-2 eager attention.
-// The mask rule is attention_tiles.h's; which kernel runs a call is attn_plan.h's decision.  The nine entry points' shared body
+// The mask rule is attention_tiles.h's; which kernel runs a call is attn_plan.h's decision.  The ten entry points' shared body
 // (run_attention) and the short ones are at the end of this file.
 #include "attention_tiles.h"
 #include "attn_plan.h"
@@ -235,11 +235,13 @@ int run_attention(const char* who, const AttnCall& c, unsigned which, unsigned l
   if (int rc = check_attention(who, c, which)) return rc;
   if (c.nseq == 0) return 0;
   const AttnTraffic t = attention_traffic(c);
-  AfftKernelScope ktrace(c.dir == kFwd ? AFFT_K_ATTN_FWD : AFFT_K_ATTN_BWD, c.nseq * c.L, c.H * c.hd, t.bytes, t.flops, stream);
+  AfftKernelScope ktrace(c.dir == kFwd || c.dir == kStep ? AFFT_K_ATTN_FWD : AFFT_K_ATTN_BWD, c.nseq * (c.dir == kStep ? c.Lq : c.L), c.H * c.hd, t.bytes,
+                         t.flops, stream);
   if (int rc = check_attention(who, c, late)) return rc;
   const AttnPlan p = plan_attention(c);
   AFFT_CHECK(!p.refusal[0], "%s", p.refusal);
   if (p.family == kGenericShort) return launch_attention_generic(c, p, stream);
+  if (p.family == kStepVec) return launch_attention_step(c, p, stream);
   return p.family <= kSlicedBwd ? launch_attention_mfma(c, p, stream) : launch_attention_long(c, p, stream);
 }
 

@@ -1,0 +1,263 @@
+// Causal attention of Lq new rows per sequence against a key / value cache, and the append of those rows to the cache, in one launch:
+// the step of a GPT-2 roll-out (models/future_prediction.py:395-412 -- the first pass runs the T observed frames and keeps every layer's
+// keys and values, each further frame is one new row per clip attending to them).  Query row i sits at position past + i, past = Lk - Lq,
+// and sees keys 0 .. past + i: rows [0, past) of the cache, then the new rows themselves.
+// One workgroup per (sequence, head, tile of STEP_QT new rows).  A workgroup writes rows [past + i0, past + i0 + rows) of ITS head's hd
+// columns of both caches and reads the new keys and values from k_new / v_new, never back from the cache: no workgroup reads what
+// another one writes, so the append needs no ordering.  fp32 VALU arithmetic (one query row is a sixteenth of an MFMA tile; the kernel
+// is bound by the Lk x hd bytes it reads): K and V go straight to registers in 16-byte loads, lanes stride the head dimension, sums run
+// in a fixed order (per lane front to back, the wave's xor tree, waves 0..3) -- no atomics, two runs give the same bits.
+// Which form runs (16-byte or element loads), LDS bytes and grid are attn_plan.h's decision (plan_attention_step).
+#include "common.h"
+#include "attn_plan.h"
+
+using namespace afft_attn_detail;
+
+namespace {
+
+struct StepArgs {
+  const void *q, *kn, *vn;
+  int64_t ldq, ldk, ldv;
+  void *kc, *vc;
+  int64_t ldc, cseq;
+  void* out;
+  int64_t ldo;
+  float* probs;
+  int Lq, Lk, H, hd, ntiles, LkP;
+  float scale;
+};
+
+template <typename T> struct StepElem;      // N: elements of one 16-byte access
+template <> struct StepElem<float> { static constexpr int N = 4; };
+template <> struct StepElem<bf16_t> { static constexpr int N = 8; };
+
+// x = p[c .. c + N) as fp32: one 16-byte load (V: hd is a multiple of N), else element loads that stop at hd
+template <typename T, bool V>
+__device__ __forceinline__ void ld_cols(const T* p, int c, int hd, float (&x)[StepElem<T>::N]) {
+  if constexpr (V) {
+    if constexpr (StepElem<T>::N == 4) load4(p, c, AFFT_F32, x); else load8(p, c, AFFT_BF16, x);
+  } else {
+#pragma unroll
+    for (int e = 0; e < StepElem<T>::N; ++e) x[e] = c + e < hd ? Elem<T>::ld(p + c + e) : 0.f;
+  }
+}
+template <typename T, bool V>
+__device__ __forceinline__ void st_cols(T* p, int c, int hd, const float (&x)[StepElem<T>::N]) {
+  if constexpr (V) {
+    if constexpr (StepElem<T>::N == 4) store4(p, c, AFFT_F32, x); else store8(p, c, AFFT_BF16, x);
+  } else {
+#pragma unroll
+    for (int e = 0; e < StepElem<T>::N; ++e)
+      if (c + e < hd) Elem<T>::st(p + c + e, x[e]);
+  }
+}
+// dst[c .. c + N) = src[c .. c + N), the bits as they are
+template <typename T, bool V>
+__device__ __forceinline__ void copy_cols(T* dst, const T* src, int c, int hd) {
+  if constexpr (V) {
+    *(uint4*)(dst + c) = *(const uint4*)(src + c);
+  } else {
+#pragma unroll
+    for (int e = 0; e < StepElem<T>::N; ++e)
+      if (c + e < hd) dst[c + e] = src[c + e];
+  }
+}
+
+template <typename T, bool V>
+__global__ __launch_bounds__(256) void attn_step_kernel(const StepArgs a) {
+  constexpr int N = StepElem<T>::N, NT = 1024 / (64 * N);      // a lane owns columns (lane + 64 t) N .. + N, t < NT: hd <= 1024
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const int tile = blockIdx.x % a.ntiles, sh = blockIdx.x / a.ntiles, h = sh % a.H, seq = sh / a.H;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int Lq = a.Lq, Lk = a.Lk, hd = a.hd, LkP = a.LkP, past = Lk - Lq;
+  const int i0 = tile * STEP_QT, nr = min(STEP_QT, Lq - i0);      // this workgroup's new rows i0 .. i0 + nr
+  const int rows = min(STEP_QT, Lq), hdP = (hd + 7) & ~7;         // the LDS carve is the plan's: the same for every tile
+  float* sc = reinterpret_cast<float*>(smem_raw);                 // [rows][LkP] scores, then probabilities
+  float* part = sc + rows * LkP;                                  // [3][rows][hdP] P V partial sums of waves 1..3
+
+  const int64_t new0 = (int64_t)seq * Lq, hcol = (int64_t)h * hd;
+  const T* qh = (const T*)a.q + new0 * a.ldq + hcol;
+  const T* knh = (const T*)a.kn + new0 * a.ldk + hcol;
+  const T* vnh = (const T*)a.vn + new0 * a.ldv + hcol;
+  T* kch = (T*)a.kc + seq * a.cseq + hcol;
+  T* vch = (T*)a.vc + seq * a.cseq + hcol;
+
+  // the append: rows past + i of both caches become rows i of k_new / v_new (i < Lq, so past + i < Lk <= cap)
+  const int nv = (hd + N - 1) / N;
+  for (int idx = tid; idx < nr * nv; idx += 256) {
+    const int i = i0 + idx / nv, c = (idx % nv) * N;
+    copy_cols<T, V>(kch + (int64_t)(past + i) * a.ldc, knh + (int64_t)i * a.ldk, c, hd);
+    copy_cols<T, V>(vch + (int64_t)(past + i) * a.ldc, vnh + (int64_t)i * a.ldv, c, hd);
+  }
+
+  // scores: a wave takes (row, 4 keys) at a time -- the row in registers, the 4 x NT loads of the keys independent of each other
+  const int nchunk = (Lk + 3) / 4;
+  for (int item = wave; item < nr * nchunk; item += 4) {
+    const int r = item / nchunk, j0 = (item % nchunk) * 4, i = i0 + r, last = past + i;      // row i sees keys 0 .. last
+    if (j0 > last) continue;
+    float qv[NT][N];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const int c = (lane + 64 * t) * N;
+      if (c < hd) {
+        ld_cols<T, V>(qh + (int64_t)i * a.ldq, c, hd, qv[t]);
+      } else {
+#pragma unroll
+        for (int e = 0; e < N; ++e) qv[t][e] = 0.f;
+      }
+    }
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int j = j0 + u;
+      if (j <= last) {
+        const T* kr = j < past ? kch + (int64_t)j * a.ldc : knh + (int64_t)(j - past) * a.ldk;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          const int c = (lane + 64 * t) * N;
+          if (c < hd) {
+            float kx[N];
+            ld_cols<T, V>(kr, c, hd, kx);
+#pragma unroll
+            for (int e = 0; e < N; ++e) acc[u] += qv[t][e] * kx[e];
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int j = j0 + u;
+      if (j <= last) {
+        const float s = wave_sum(acc[u]) * a.scale;
+        if (lane == 0) sc[r * LkP + j] = s;
+      }
+    }
+  }
+  __syncthreads();
+
+  // softmax over the whole row in fp32, one wave per row; keys behind `last` are masked: probability exactly 0
+  if (wave < nr) {
+    const int i = i0 + wave, last = past + i;
+    float* row = sc + wave * LkP;
+    float m = -INFINITY;
+    for (int j = lane; j <= last; j += 64) m = fmaxf(m, row[j]);
+    m = wave_max(m);
+    float sum = 0.f;
+    for (int j = lane; j <= last; j += 64) {
+      const float e = expf(row[j] - m);
+      row[j] = e;
+      sum += e;
+    }
+    const float inv = 1.0f / wave_sum(sum);
+    float* pr = a.probs ? a.probs + ((((int64_t)seq * a.H + h) * Lq + i) * Lk) : nullptr;
+    for (int j = lane; j < Lk; j += 64) {
+      const float p = j <= last ? row[j] * inv : 0.f;
+      row[j] = p;
+      if (pr) pr[j] = p;
+    }
+  }
+  __syncthreads();
+
+  // P V: wave w takes keys w, w + 4, .. for every row of the tile (a masked key has p = 0 and a finite, new value row)
+  float acc[STEP_QT][NT][N];
+#pragma unroll
+  for (int r = 0; r < STEP_QT; ++r)
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int e = 0; e < N; ++e) acc[r][t][e] = 0.f;
+  const int jend = past + i0 + nr;      // the keys the tile's last row sees
+#pragma unroll 2
+  for (int j = wave; j < jend; j += 4) {
+    const T* vr = j < past ? vch + (int64_t)j * a.ldc : vnh + (int64_t)(j - past) * a.ldv;
+    float pj[STEP_QT];
+#pragma unroll
+    for (int r = 0; r < STEP_QT; ++r) pj[r] = r < nr ? sc[r * LkP + j] : 0.f;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const int c = (lane + 64 * t) * N;
+      if (c < hd) {
+        float vx[N];
+        ld_cols<T, V>(vr, c, hd, vx);
+#pragma unroll
+        for (int r = 0; r < STEP_QT; ++r)
+#pragma unroll
+          for (int e = 0; e < N; ++e) acc[r][t][e] += pj[r] * vx[e];
+      }
+    }
+  }
+  if (wave > 0) {
+#pragma unroll
+    for (int r = 0; r < STEP_QT; ++r)
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const int c = (lane + 64 * t) * N;
+        if (r < nr && c < hd) {
+          float* dst = part + ((wave - 1) * rows + r) * hdP + c;
+#pragma unroll
+          for (int e = 0; e < N; ++e) dst[e] = acc[r][t][e];
+        }
+      }
+  }
+  __syncthreads();
+  if (wave == 0) {
+#pragma unroll
+    for (int r = 0; r < STEP_QT; ++r)
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const int c = (lane + 64 * t) * N;
+        if (r < nr && c < hd) {
+          for (int w = 0; w < 3; ++w) {
+            const float* src = part + (w * rows + r) * hdP + c;
+#pragma unroll
+            for (int e = 0; e < N; ++e) acc[r][t][e] += src[e];
+          }
+          st_cols<T, V>((T*)a.out + (new0 + i0 + r) * a.ldo + hcol, c, hd, acc[r][t]);
+        }
+      }
+  }
+}
+
+template <typename T, bool V>
+int launch_step(const StepArgs& a, const AttnPlan& p, hipStream_t stream) {
+  auto kern = attn_step_kernel<T, V>;
+  static std::atomic<uint64_t> attr{0};
+  if (p.lds > 48 * 1024)
+    if (int rc = afft_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), p.lds, &attr)) return rc;
+  hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), p.lds, stream, a);
+  return 0;
+}
+
+}  // namespace
+
+int launch_attention_step(const AttnCall& c, const AttnPlan& p, hipStream_t stream) {
+  const StepArgs a = {c.q, c.k, c.v, c.ldq, c.ldk, c.ldv, c.k_cache, c.v_cache, c.ldc, c.cache_seq, c.out, c.ldo, c.probs,
+                      c.Lq, c.L, c.H, c.hd, p.ntiles, p.Lp, c.scale};
+  const bool f32 = c.dtype == AFFT_F32;
+  if (int rc = f32 ? (p.p0 ? launch_step<float, true>(a, p, stream) : launch_step<float, false>(a, p, stream))
+                   : (p.p0 ? launch_step<bf16_t, true>(a, p, stream) : launch_step<bf16_t, false>(a, p, stream)))
+    return rc;
+  AFFT_LAUNCH_CHECK();
+  return 0;
+}
+
+// the step plan of a dense problem as its arguments describe it (one sequence, one head, rows of hd elements rounded up to whole
+// 16-byte units at 16-byte aligned addresses -- or, pitch_alignment_ok = 0, rows that no 16-byte load can take)
+extern "C" int afft_attention_step_plan_for(int32_t dtype, int32_t Lq, int32_t Lk, int32_t hd, int32_t pitch_alignment_ok, int64_t* lds_and_tiles) {
+  const int64_t ld = (hd + 7) / 8 * 8 + (pitch_alignment_ok ? 0 : 1);
+  void* x = reinterpret_cast<void*>(uintptr_t{4096});      // never dereferenced
+  const AttnCall c = attn_step_call(x, ld, x, ld, x, ld, x, x, ld, ld * (Lk > 0 ? Lk : 1), dtype, 1, Lq, Lk, Lk, 1, hd, 1.f, x, ld, nullptr);
+  const AttnPlan p = plan_attention(c);
+  if (!p.family) { afft_set_error("%s", p.refusal); return -1; }
+  if (lds_and_tiles) { lds_and_tiles[0] = (int64_t)p.lds; lds_and_tiles[1] = p.ntiles; }
+  return p.family * 10000 + p.p0 * 10 + p.p1;
+}
+
+extern "C" int afft_attention_step_fwd(const void* q, int64_t ldq, const void* k_new, int64_t ldk, const void* v_new, int64_t ldv,
+                                       void* k_cache, void* v_cache, int64_t ldc, int64_t cache_seq, int32_t dtype, int32_t nseq,
+                                       int32_t Lq, int32_t Lk, int32_t cap, int32_t H, int32_t hd, float scale, void* out, int64_t ldo,
+                                       float* probs, void* stream_) {
+  const AttnCall c = attn_step_call(q, ldq, k_new, ldk, v_new, ldv, k_cache, v_cache, ldc, cache_seq, dtype, nseq, Lq, Lk, cap, H, hd, scale,
+                                    out, ldo, probs);
+  return run_attention("attention_step", c, kChkPtrs | kLenAll | kChkBatch | kChkHd | kChkDtype | kChkStep, 0, (hipStream_t)stream_);
+}

@@ -1,8 +1,8 @@
 // The dispatch plan of attention: what an entry point was asked (AttnCall), whether the arguments are acceptable (check_attention),
 // which kernel instantiation runs it with which launch geometry (plan_attention), and what the kernel trace records (attention_traffic).
 // Pure host arithmetic over shapes, pitches and pointer alignments -- no HIP runtime call, no global state but the one cached read of
-// AFFT_ATTN_GENERIC (compiles with the plain host compiler) -- and the ONE place that decides: the nine entry points (attention.hip,
-// attention_long.hip) check, plan, open the trace scope and hand the plan to the launcher of the family's file, which only maps it to
+// AFFT_ATTN_GENERIC (compiles with the plain host compiler) -- and the ONE place that decides: the ten entry points (attention.hip,
+// attention_long.hip, attention_step.hip) check, plan, open the trace scope and hand the plan to the launcher of the family's file, which only maps it to
 // a template instantiation; afft_attention_plan_for reports it.
 #pragma once
 #include <stdint.h>
@@ -23,8 +23,9 @@ constexpr int LMAX = 128;              // the short kernels: a whole sequence pe
 constexpr int LLO = 129, LHI = 512;    // the long kernels (attention_long.hip)
 constexpr int QT = 32;                 //   rows of a tile
 constexpr int KB = 64;                 //   rows of the other operand staged at a time (MFMA form)
+constexpr int STEP_QT = 4;             // the cached step (attention_step.hip): query rows of a workgroup, one per wave in its softmax
 
-enum AttnDir { kFwd = 0, kBwd = 1, kBiasBwd = 2 };
+enum AttnDir { kFwd = 0, kBwd = 1, kBiasBwd = 2, kStep = 3 };
 
 // what an entry point was asked to do; fields an entry point does not have stay zero
 struct AttnCall {
@@ -49,6 +50,11 @@ struct AttnCall {
   float* dbias;                        // bias gradient, element strides dsb / dsh / dsi (0: summed over that dimension, through scratch)
   int64_t dsb, dsh, dsi;
   float *scratch, *row_term;
+  // the cached step (kStep): Lq new rows per sequence -- q / k / v above are their rows [nseq * Lq, .] -- against L keys, of which the
+  // first L - Lq are rows of the caches [nseq, cap, H * hd] (row pitch ldc, sequence stride cache_seq, elements) and the rest are appended
+  void *k_cache, *v_cache;
+  int64_t ldc, cache_seq;
+  int Lq, cap;
 };
 
 inline AttnCall attn_fwd_call(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, int dtype, int nseq, int L,
@@ -67,6 +73,15 @@ inline AttnCall attn_bwd_call(const void* dout, int64_t lddo, const void* q, int
   c.dir = kBwd;
   c.dout = dout; c.lddo = lddo;
   c.dq = dq; c.dk = dk; c.dv = dv; c.lddq = lddq; c.lddk = lddk; c.lddv = lddv;
+  return c;
+}
+
+inline AttnCall attn_step_call(const void* q, int64_t ldq, const void* k_new, int64_t ldk, const void* v_new, int64_t ldv, void* k_cache,
+                               void* v_cache, int64_t ldc, int64_t cache_seq, int dtype, int nseq, int Lq, int Lk, int cap, int H, int hd,
+                               float scale, void* out, int64_t ldo, float* probs) {
+  AttnCall c = attn_fwd_call(q, ldq, k_new, ldk, v_new, ldv, dtype, nseq, Lk, H, hd, scale, 0.f, 0u, out, ldo, probs);
+  c.dir = kStep;
+  c.k_cache = k_cache; c.v_cache = v_cache; c.ldc = ldc; c.cache_seq = cache_seq; c.Lq = Lq; c.cap = cap;
   return c;
 }
 
@@ -89,6 +104,7 @@ enum : unsigned {
   kChkBiasArgs = 1u << 10,  // strides and alignment of the bias (bias gradient: of dbias)
   kChkScratch = 1u << 11,   // a bias gradient that sums needs scratch
   kLenShort = 1u << 12, kLenSplit = 1u << 13, kLenLong = 1u << 14, kLenAll = 1u << 15,      // the entry point's length band
+  kChkStep = 1u << 16,      // the cached step: new rows, keys and capacity in order, pitches that hold a row and a sequence's rows
 };
 
 #define AFFT_ATTN_CHECK(cond, ...) \
@@ -101,6 +117,7 @@ enum : unsigned {
 
 inline int check_attention(const char* who, const AttnCall& c, unsigned which) {
   const bool ptrs = c.dir == kFwd ? c.q && c.k && c.v && c.out
+                    : c.dir == kStep ? c.q && c.k && c.v && c.out && c.k_cache && c.v_cache
                     : c.dir == kBwd ? c.dout && c.q && c.k && c.v && c.probs && c.dq && c.dk && c.dv
                                     : c.dout && c.v && c.probs && c.dbias;
   AFFT_ATTN_CHECK((!(which & kChkPtrs) || ptrs) && (!(which & kChkBias) || c.bias) && (!(which & kChkRowTerm) || c.row_term),
@@ -123,6 +140,14 @@ inline int check_attention(const char* who, const AttnCall& c, unsigned which) {
   if (which & kChkHd) AFFT_ATTN_CHECK(c.hd >= 1 && c.hd <= 1024, "%s: head dimension %d outside 1..1024", who, c.hd);
   if (which & kChkDtype) AFFT_ATTN_CHECK(c.dtype == AFFT_F32 || c.dtype == AFFT_BF16, "%s: bad dtype %d", who, c.dtype);
   if (which & kChkBatch) AFFT_ATTN_CHECK(c.nseq >= 0 && c.H >= 1, "%s: bad nseq %d / H %d", who, c.nseq, c.H);
+  if (which & kChkStep) {
+    AFFT_ATTN_CHECK(c.Lq >= 1 && c.Lq <= c.L, "%s: %d new rows against %d keys (1 <= Lq <= Lk)", who, c.Lq, c.L);
+    AFFT_ATTN_CHECK(c.L <= c.cap, "%s: %d keys do not fit a cache of %d rows", who, c.L, c.cap);
+    const int64_t w = (int64_t)c.H * c.hd;
+    AFFT_ATTN_CHECK(c.ldq >= w && c.ldk >= w && c.ldv >= w && c.ldo >= w && c.ldc >= w, "%s: a row pitch is below H * hd = %lld", who, (long long)w);
+    AFFT_ATTN_CHECK(c.cache_seq >= (int64_t)(c.cap - 1) * c.ldc + w, "%s: cache sequence stride %lld does not hold %d rows of pitch %lld", who,
+                    (long long)c.cache_seq, c.cap, (long long)c.ldc);
+  }
   if (which & kChkBiasArgs) {
     const bool grad = c.dir == kBiasBwd;
     const int64_t sb = grad ? c.dsb : c.sb, sh = grad ? c.dsh : c.sh, si = grad ? c.dsi : c.si;
@@ -143,6 +168,10 @@ struct AttnTraffic { int64_t bytes, flops; };
 inline AttnTraffic attention_traffic(const AttnCall& c) {
   const int64_t es = c.dtype == AFFT_F32 ? 4 : 2, rw = (int64_t)c.nseq * c.L * c.H * c.hd, pb = (int64_t)c.nseq * c.H * c.L * c.L * 4;
   const int64_t product = 2 * (int64_t)c.nseq * c.H * c.L * c.L * c.hd;      // one L x L x hd product
+  if (c.dir == kStep) {      // q, k_new, v_new read, both appended, the past read, out and probs written
+    const int64_t row = es * c.nseq * c.H * c.hd, past = c.L - c.Lq;
+    return {row * (6 * c.Lq + 2 * past) + (c.probs ? (int64_t)c.nseq * c.H * c.Lq * c.L * 4 : 0), 4 * (int64_t)c.nseq * c.H * c.Lq * c.L * c.hd};
+  }
   if (c.dir == kBiasBwd) return {2 * es * rw + (bias_grad_reduces(c) ? 3 : 2) * pb, product};
   // backward: the four products (the long form makes dP twice, once per pass: 10 L^2 hd are executed)
   if (c.dir == kBwd) return {7 * es * rw + pb, 4 * product};
@@ -159,6 +188,7 @@ enum AttnFamily {
   kSlicedBwd = 4,           //                    attn_bwd_sliced_kernel<NT = p0>
   kLongF32 = 5, kLongBf16 = 6, kLongMfma = 7,      // attention_long.hip long_fwd_kernel / long_bwd_q_kernel + long_bwd_kv_kernel
   kBiasF32 = 8, kBiasBf16 = 9, kBiasMfma = 10,     //                    bias_bwd_ds_kernel (+ bias_bwd_reduce_kernel)
+  kStepVec = 11,            // attention_step.hip attn_step_kernel<T, V = p0>: p0 = 1, 16-byte loads; 0, element loads
 };
 
 struct AttnPlan {
@@ -166,7 +196,7 @@ struct AttnPlan {
   int p0, p1;               // template parameters: LM or NT; PL
   int hc;                   // head-dimension chunk staged in LDS at a time (MFMA families)
   int G;                    // short MFMA: sequences packed into one workgroup's 16 NT rows
-  int Lp, ntiles;           // long: L rounded up to KB; tiles of QT rows
+  int Lp, ntiles;           // long: L rounded up to KB; tiles of QT rows.  step: L rounded up to 4; tiles of STEP_QT query rows
   size_t lds;               // dynamic LDS bytes of the launch
   unsigned grid;
   char refusal[160];        // not empty: the call fails with this message (the fp16x2 forward is the only one without a fallback)
@@ -226,7 +256,29 @@ inline bool plan_short_mfma(const AttnCall& c, AttnPlan& p) {
   return true;
 }
 
+// the cached step: one workgroup per (sequence, head, tile of STEP_QT new rows); LDS = the tile's fp32 scores [rows][Lp] and the P V
+// partial sums of waves 1..3, [3][rows][hd rounded up to 8]
+inline AttnPlan plan_attention_step(const AttnCall& c) {
+  AttnPlan p = {};
+  const bool f32 = c.dtype == AFFT_F32;
+  if (c.Lq < 1 || c.Lq > c.L || c.L > LHI || c.hd < 1 || c.hd > 1024 || (!f32 && c.dtype != AFFT_BF16)) {
+    snprintf(p.refusal, sizeof p.refusal, "attention_step: no kernel for Lq = %d, Lk = %d, head dimension %d, dtype %d", c.Lq, c.L, c.hd, c.dtype);
+    return p;
+  }
+  const int vec = f32 ? 4 : 8;      // elements of a 16-byte load
+  const bool pitches = c.ldq % vec == 0 && c.ldk % vec == 0 && c.ldv % vec == 0 && c.ldc % vec == 0 && c.cache_seq % vec == 0 && c.ldo % vec == 0;
+  p.family = kStepVec;
+  p.p0 = c.hd % vec == 0 && pitches && al16(c.q) && al16(c.k) && al16(c.v) && al16(c.k_cache) && al16(c.v_cache) && al16(c.out);
+  const int rows = c.Lq < STEP_QT ? c.Lq : STEP_QT;
+  p.Lp = (c.L + 3) / 4 * 4;
+  p.ntiles = (c.Lq + STEP_QT - 1) / STEP_QT;
+  p.lds = sizeof(float) * rows * ((size_t)p.Lp + 3 * (size_t)((c.hd + 7) / 8 * 8));
+  p.grid = (unsigned)((int64_t)c.nseq * c.H * p.ntiles);
+  return p;
+}
+
 inline AttnPlan plan_attention(const AttnCall& c) {
+  if (c.dir == kStep) return plan_attention_step(c);
   AttnPlan p = {};
   const bool f32 = c.dtype == AFFT_F32, bf16 = c.dtype == AFFT_BF16;
   if (c.L < 1 || c.L > LHI || (!c.planes && (c.hd < 1 || c.hd > 1024 || (!f32 && !bf16)))) {
@@ -259,10 +311,11 @@ inline AttnPlan plan_attention(const AttnCall& c) {
 
 }  // namespace afft_attn_detail
 
-#ifdef __HIPCC__      // the launchers of the three files: a switch from plan to template instantiation each
+#ifdef __HIPCC__      // the launchers of the four files: a switch from plan to template instantiation each
 int launch_attention_generic(const afft_attn_detail::AttnCall& c, const afft_attn_detail::AttnPlan& p, hipStream_t stream);      // attention.hip
 int launch_attention_mfma(const afft_attn_detail::AttnCall& c, const afft_attn_detail::AttnPlan& p, hipStream_t stream);         // attention_mfma.hip
 int launch_attention_long(const afft_attn_detail::AttnCall& c, const afft_attn_detail::AttnPlan& p, hipStream_t stream);         // attention_long.hip
+int launch_attention_step(const afft_attn_detail::AttnCall& c, const afft_attn_detail::AttnPlan& p, hipStream_t stream);         // attention_step.hip
 // check -> nseq == 0 -> trace scope -> `late` checks -> plan -> launch: the body of every entry point (attention.hip)
 int run_attention(const char* who, const afft_attn_detail::AttnCall& c, unsigned which, unsigned late, hipStream_t stream);
 #endif

@@ -1210,6 +1210,50 @@ class MLPSublayer(torch.autograd.Function):
         return _pad((dx, g_lw, g_lb, g_w1, g_b1, g_w2, g_b2), _MLP_NARGS)
 
 
+# --------------------------------------------------------------------------- cached roll-out: the two sub-layers on NEW rows only
+# Inference only (no autograd graph, nothing saved, no side stream): the forward halves of the call-by-call sequences above, with the
+# attention core replaced by afft_attention_step_fwd -- the new rows attend to the keys and values the earlier calls left in the cache,
+# and are appended to it by the same launch.
+class KVCache:
+    """Keys and values of every layer of a causal model for `B` sequences of up to `cap` positions: per layer two [B, cap, D] buffers
+    (one allocation from torch's allocator) in the storage dtype the current precision gives its call-by-call attention core (bf16 in
+    'bf16', else fp32), and `len`, the positions filled so far -- advanced by the model once all its layers have appended."""
+    __slots__ = ("kv", "cap", "len")
+
+    def __init__(self, n_layer: int, B: int, cap: int, D: int, device):
+        self.kv = torch.empty(n_layer, 2, B, cap, D, dtype=rt.act_dtype(), device=device)
+        self.cap, self.len = cap, 0
+
+    def layer(self, i: int) -> Tuple[Tensor, Tensor]:
+        return self.kv[i, 0], self.kv[i, 1]
+
+
+def attn_step(x: Tensor, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, Lq: int, H: int, eps: float, conv1d: bool, k_cache: Tensor,
+              v_cache: Tensor, past: int, want_probs: bool) -> Tuple[Tensor, Optional[Tensor]]:
+    """AttnSublayer's forward (pre-LN, causal, no dropout) on the Lq new rows per sequence of x fp32 [nseq * Lq, d], which sit at positions
+    past .. past + Lq - 1.  Returns (y, probs fp32 [nseq, H, Lq, past + Lq] or None)."""
+    R, d = x.shape
+    nseq, hd, Lk = R // Lq, d // H, past + Lq
+    xn, _, _ = _cbc_ln_in(None, x, ln_w, ln_b, eps, True)
+    qkv = Act(R, 3 * d, x.device)
+    _lin_fwd(xn, w_qkv, conv1d, qkv.live, bias=b_qkv)
+    ao = Act(R, d, x.device)
+    probs = torch.empty(nseq, H, Lq, Lk, dtype=torch.float32, device=x.device) if want_probs else None
+    ops.attention_step(qkv.cols(0, d), qkv.cols(d, 2 * d), qkv.cols(2 * d, 3 * d), k_cache, v_cache, nseq, Lq, Lk, H, hd, float(hd) ** -0.5,
+                       ao.live, probs)
+    return _cbc_out(x, ao, w_proj, conv1d, b_proj, True, None, d), probs
+
+
+def mlp_step(x: Tensor, ln_w, ln_b, w1, b1, w2, b2, eps: float, gelu: str, conv1d: bool) -> Tensor:
+    """MLPSublayer's forward (pre-LN, no dropout) without the saved pre-activation"""
+    R, d = x.shape
+    hidden = w1.shape[1] if conv1d else w1.shape[0]
+    xn, _, _ = _cbc_ln_in(None, x, ln_w, ln_b, eps, True)
+    h = Act(R, hidden, x.device)
+    _lin_fwd(xn, w1, conv1d, h.live, bias=b1, act=_GELU[gelu][0])
+    return _cbc_out(x, h, w2, conv1d, b2, True, None, w2.shape[1] if conv1d else w2.shape[0])
+
+
 # --------------------------------------------------------------------------- pre-LN cross-attention sub-layer
 class CrossAttnSublayer(torch.autograd.Function):
     """y = x + proj(attn(q = w_q LN_q(x), k = w_k LN_kv(mem), v = w_v LN_kv(mem)))

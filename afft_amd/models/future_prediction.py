@@ -83,6 +83,15 @@ class GPT2Block(nn.Module):
                                  m.c_proj.bias, self.ln_2.eps, "tanh", True, True, D_.cfg(self, out=m.dropout.p))
         return h, probs
 
+    def forward_step(self, h: Tensor, Lq: int, k_cache: Tensor, v_cache: Tensor, past: int, want_attn: bool):
+        """the block on the Lq new rows per clip at positions past .. past + Lq - 1 (inference: F_.attn_step / F_.mlp_step)"""
+        a, m = self.attn, self.mlp
+        h, probs = F_.attn_step(h, self.ln_1.weight, self.ln_1.bias, a.c_attn.weight, a.c_attn.bias, a.c_proj.weight, a.c_proj.bias,
+                                Lq, a.num_heads, self.ln_1.eps, True, k_cache, v_cache, past, want_attn)
+        h = F_.mlp_step(h, self.ln_2.weight, self.ln_2.bias, m.c_fc.weight, m.c_fc.bias, m.c_proj.weight, m.c_proj.bias, self.ln_2.eps,
+                        "tanh", True)
+        return h, probs
+
 
 class GPT2Model(nn.Module):
     """The slice of HF GPT2Model the reference uses: inputs_embeds + wpe[position_ids] -> drop -> blocks -> ln_f."""
@@ -116,6 +125,30 @@ class GPT2Model(nn.Module):
         h = F_.LayerNormRows.apply(h, self.ln_f.weight, self.ln_f.bias, self.ln_f.eps, 1)
         return h, attns
 
+    def new_cache(self, B: int, cap: int, device) -> "F_.KVCache":
+        return F_.KVCache(len(self.h), B, cap, self.embed_dim, device)
+
+    def forward_step(self, x_rows: Tensor, Lq: int, cache: "F_.KVCache", want_attn: bool = False):
+        """x_rows fp32 [B*Lq, D]: the Lq NEW frames per clip, at positions cache.len .. cache.len + Lq - 1; every layer appends their keys
+        and values to `cache` and attends to what is there.  Inference only (eval mode, no grad).  Returns (last_hidden_state of the new
+        rows, [probs (B, H, Lq, cache.len + Lq) per layer]) and advances cache.len."""
+        assert not torch.is_grad_enabled() and not self.training, "GPT2Model.forward_step is an inference path"
+        past = cache.len
+        if past + Lq > min(cache.cap, self.wpe.weight.shape[0]):
+            raise ValueError(f"GPT2Model.forward_step: positions {past}..{past + Lq - 1} exceed the cache ({cache.cap}) or n_positions")
+        h = torch.empty_like(x_rows)
+        F_.ops.add_rows_periodic(x_rows, self.wpe.weight[past:past + Lq], Lq, h)
+        attns = []
+        for i, blk in enumerate(self.h):
+            h, probs = blk.forward_step(h, Lq, *cache.layer(i), past, want_attn)
+            if want_attn:
+                attns.append(probs)
+        y = torch.empty_like(h)
+        F_.ops.layernorm_fwd(h, self.ln_f.weight, self.ln_f.bias, self.ln_f.eps, y)
+        F_._forget_output()
+        cache.len = past + Lq
+        return y, attns
+
 
 class BaseFuturePredictor(nn.Module):
     """future predictor for single modality (GPT-2 style causal transformer over frames)"""
@@ -139,16 +172,22 @@ class BaseFuturePredictor(nn.Module):
         return F_.Linear.apply(x.reshape(B * T, C), lin.weight, None).view(B, T, -1)
 
     def forward(self, feats: torch.Tensor, output_len: int = 1) -> Tuple[torch.Tensor, Dict]:
-        """feats (B, T, C) -> (B, T + output_len - 1, C), {gpt2_att_i: (B, layers, heads, L, L)}.
+        """feats (B, T, C) -> (B, T + output_len - 1, C), {gpt2_att_i: (B, layers, heads, T, T) for i = 0, (B, layers, heads, 1, T + i) after}.
 
-        output_len > 1: the reference rolls out with HF's KV cache, feeding the last hidden state back as the
-        next input embedding at the next position (future_prediction.py:395-412).  A causal model's earlier
-        positions do not change when a token is appended, so the roll-out is computed by re-running the
-        extended sequence and keeping its last frame -- the same arithmetic without a cache."""
+        output_len > 1: the reference rolls out with HF's KV cache, feeding the last hidden state back as the next input embedding at the
+        next position (future_prediction.py:395-412).  In evaluation (eval mode, no grad, runtime.kv_cache(); every precision but 'fp16x2',
+        whose one-pass GEMM sites exist on the composite sub-layer calls only) this does the same: the T
+        observed frames run once through GPT2Model.forward_step, which leaves every layer's keys and values in a KVCache, and every
+        further frame is ONE new row per clip attending to the cache (afft_attention_step_fwd).  With grad enabled, in training mode or
+        with AFFT_KV_CACHE=0 the roll-out re-runs the extended sequence for every predicted frame and keeps its last row -- a causal
+        model's earlier positions do not change when a token is appended, so that is the same arithmetic without a cache, and it is the
+        form that has a backward pass."""
         addl_endpoints = {}
         feats = self._map(self.encoder, feats)
         B, T, D = feats.shape
         seq = feats if feats.dtype == torch.float32 else feats.float()
+        if output_len > 1 and rt.kv_cache() and not torch.is_grad_enabled() and not self.training and rt.precision() != "fp16x2":
+            return self._rollout_cached(seq, output_len, addl_endpoints)
         outs: List[Tensor] = []
         for output_id in range(output_len):
             L = seq.shape[1]
@@ -162,6 +201,23 @@ class BaseFuturePredictor(nn.Module):
             if output_id + 1 < output_len:
                 seq = torch.cat([seq, h[:, -1:, :]], dim=1)
         return (outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)), addl_endpoints
+
+    def _rollout_cached(self, seq: Tensor, output_len: int, addl_endpoints: Dict) -> Tuple[torch.Tensor, Dict]:
+        """the roll-out over a KVCache: one forward_step on the T observed frames, then one per further frame on the previous last row"""
+        B, T, D = seq.shape
+        cache = self.gpt_model.new_cache(B, T + output_len - 1, seq.device)
+        outs: List[Tensor] = []
+        new = seq.reshape(B * T, D).contiguous()
+        for output_id in range(output_len):
+            Lq = T if output_id == 0 else 1
+            h, attns = self.gpt_model.forward_step(new, Lq, cache, self.output_attentions)
+            if self.output_attentions:
+                addl_endpoints[f'gpt2_att_{output_id}'] = torch.stack(attns, dim=1)      # (B, layers, H, Lq, Lk)
+            h = h.view(B, Lq, D)
+            outs.append(self._map(self.decoder, h))
+            new = h[:, -1, :].contiguous()
+        return torch.cat(outs, dim=1), addl_endpoints
+
 
 
 # --------------------------------------------------------------------------- cross-modal fusion + prediction

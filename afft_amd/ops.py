@@ -393,6 +393,26 @@ def attention_bias_bwd(dout: Tensor, v: Tensor, probs: Tensor, nseq: int, L_: in
     return dbias
 
 
+def attention_step(q: Tensor, k_new: Tensor, v_new: Tensor, k_cache: Tensor, v_cache: Tensor, nseq: int, Lq: int, Lk: int, H: int, hd: int,
+                   scale: float, out: Tensor, probs: Optional[Tensor]) -> Tensor:
+    """one step of a cached roll-out (afft_attention_step_fwd): causal attention of the Lq new rows per sequence (q / k_new / v_new
+    [nseq * Lq, H * hd] views) against k_cache / v_cache [nseq, cap, H * hd], whose rows [Lk - Lq, Lk) become k_new / v_new in the same
+    launch; probs (optional) fp32 [nseq, H, Lq, Lk]"""
+    assert q.dtype == k_new.dtype == v_new.dtype == k_cache.dtype == v_cache.dtype == out.dtype
+    if k_cache.dim() != 3 or k_cache.shape != v_cache.shape or k_cache.stride() != v_cache.stride() or k_cache.stride(2) != 1:
+        raise ValueError(f"afft_amd: the caches must be two [nseq, cap, H*hd] tensors of one layout with unit column stride, got "
+                         f"{tuple(k_cache.shape)} {k_cache.stride()} and {tuple(v_cache.shape)} {v_cache.stride()}")
+    if k_cache.shape[0] != nseq or k_cache.shape[2] != H * hd:
+        raise ValueError(f"afft_amd: caches of shape {tuple(k_cache.shape)} for nseq = {nseq}, H * hd = {H * hd}")
+    if probs is not None:
+        assert probs.dtype == torch.float32 and probs.is_contiguous() and probs.numel() == nseq * H * Lq * Lk
+    L.check(L.lib().afft_attention_step_fwd(_p(q), _rowmajor(q, "q"), _p(k_new), _rowmajor(k_new, "k_new"), _p(v_new), _rowmajor(v_new, "v_new"),
+                                            _p(k_cache), _p(v_cache), k_cache.stride(1), k_cache.stride(0), _dt(q), nseq, Lq, Lk,
+                                            k_cache.shape[1], H, hd, scale, _p(out), _rowmajor(out, "out"), _p(probs), _stream()),
+            "attention_step")
+    return out
+
+
 def softmax_ce(logits: Tensor, C_: int, *, labels: Optional[Tensor] = None, soft: Optional[Tensor] = None,
                keep: Optional[Tensor] = None, gscale: float = 1.0, row_g: Optional[Tensor] = None,
                loss_sum: Optional[Tensor] = None, dlogits: Optional[Tensor] = None,

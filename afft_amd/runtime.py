@@ -526,6 +526,21 @@ def set_composite(on: bool):
     _COMPOSITE = bool(on)
 
 
+_KV_CACHE = os.environ.get("AFFT_KV_CACHE", "1") != "0"
+
+
+def kv_cache() -> bool:
+    """Roll the future predictor out (output_len > 1, evaluation, no grad) with a key / value cache: the observed frames run once and
+    every further frame is one new row per clip (models/future_prediction.py, BaseFuturePredictor.forward).  AFFT_KV_CACHE=0 re-runs the
+    extended sequence for every predicted frame, as training and every pass with grad enabled do."""
+    return _KV_CACHE
+
+
+def set_kv_cache(on: bool):
+    global _KV_CACHE
+    _KV_CACHE = bool(on)
+
+
 _FUSED_SGD = os.environ.get("AFFT_FUSED_SGD", "1") != "0"
 
 

@@ -324,7 +324,8 @@ int afft_attention_bias_bwd(const void* dout, int64_t lddo, const void* v, int64
                             int32_t nseq, int32_t L, int32_t H, int32_t hd, float drop_p, uint32_t drop_key, float* dbias,
                             int64_t sb, int64_t sh, int64_t si, float* scratch, void* stream);
 
-/* Which attention kernel a call gets (the plan the nine entry points above launch from, csrc/attn_plan.h); launches nothing and needs
+/* Which attention kernel a call gets (the plan the nine entry points above launch from, csrc/attn_plan.h; the tenth, the cached step
+ * below, has a query of its own); launches nothing and needs
  * no device.  direction: 0 forward, 1 backward, 2 bias gradient; dtype: AFFT_F32 / AFFT_BF16; planes != 0: the fp16x2 forward
  * (afft_attention_fwd_split; in_lo != 0: two planes per input); pitch_alignment_ok: rows and pointers take 16-byte loads.
  * Returns family * 10000 + p0 * 10 + p1 -- family 1: generic short kernels, p0 = LM (32 / 64 / 128); 2: MFMA short forward, p0 = NT,
@@ -332,6 +333,27 @@ int afft_attention_bias_bwd(const void* dout, int64_t lddo, const void* v, int64
  * bf16 / MFMA; 8 / 9 / 10: the same three forms of the bias-gradient stage -- or a negative value when no kernel takes the shape
  * (afft_last_error says why).  AFFT_ATTN_GENERIC=1 in the environment keeps bf16 off the MFMA kernels (the fp16x2 forward has no other). */
 int afft_attention_plan_for(int32_t direction, int32_t dtype, int32_t L, int32_t hd, int32_t planes, int32_t in_lo, int32_t pitch_alignment_ok);
+
+/* ------------------------------------------------------------------ one step of a cached roll-out (attention_step.hip)
+ * Causal attention of Lq NEW rows per sequence against a key / value cache, and the append of those rows to the cache, in one launch:
+ * HF GPT-2 with past_key_values, as the reference's roll-out uses it (models/future_prediction.py:395-412).
+ * q / k_new / v_new: the new rows [nseq * Lq, *] with row strides ldq / ldk / ldv, head h at columns h*hd.. (the q | k | v column blocks
+ * of the QKV GEMM output).  k_cache / v_cache: [nseq, cap, H*hd] in the same dtype, row pitch ldc and sequence stride cache_seq (ELEMENTS,
+ * both caches alike), valid in rows [0, Lk - Lq) on entry.  On return rows [Lk - Lq, Lk) of both caches hold k_new / v_new bit for bit
+ * (no other cache row is written); query row i sits at position Lk - Lq + i and attends to keys 0 .. Lk - Lq + i; softmax in fp32 over the
+ * whole row; out: [nseq * Lq, H*hd] in `dtype`; probs (optional): fp32 [nseq, H, Lq, Lk], masked entries exactly 0.  No dropout: an
+ * inference path.  1 <= Lq <= Lk <= cap, Lk <= 512, 1 <= hd <= 1024, dtype AFFT_F32 / AFFT_BF16; anything else is an error and nothing is
+ * launched.  Lq == Lk is the first pass: it fills the cache and agrees with afft_attention_fwd(mask = causal) to rounding.  fp32 arithmetic,
+ * no atomics, sums in a fixed order (bitwise reproducible); 16-byte loads when hd, the pitches and the pointers allow them. */
+int afft_attention_step_fwd(const void* q, int64_t ldq, const void* k_new, int64_t ldk, const void* v_new, int64_t ldv,
+                            void* k_cache, void* v_cache, int64_t ldc, int64_t cache_seq, int32_t dtype, int32_t nseq,
+                            int32_t Lq, int32_t Lk, int32_t cap, int32_t H, int32_t hd, float scale, void* out, int64_t ldo,
+                            float* probs, void* stream);
+/* The plan of such a step (csrc/attn_plan.h plan_attention_step), as afft_attention_plan_for reports the others: launches nothing and
+ * needs no device.  Returns family * 10000 + p0 * 10 -- family 11, p0 = 1: 16-byte loads, 0: element loads -- and, when lds_and_tiles is
+ * not NULL, the dynamic LDS bytes of the launch in lds_and_tiles[0] and the workgroups per (sequence, head) in lds_and_tiles[1]; a negative
+ * value when no kernel takes the shape (afft_last_error says why). */
+int afft_attention_step_plan_for(int32_t dtype, int32_t Lq, int32_t Lk, int32_t hd, int32_t pitch_alignment_ok, int64_t* lds_and_tiles);
 
 /* afft_layernorm_bwd whose incoming residual gradient dx_in is [rows / in_take, d] (row pitch lddx_in) and belongs to rows 0, in_take,
  * 2 in_take, ..: the other rows take no residual gradient (afft_attn_sublayer_t.take; in_take = 1: every row). */
