@@ -235,13 +235,14 @@ int run_attention(const char* who, const AttnCall& c, unsigned which, unsigned l
   if (int rc = check_attention(who, c, which)) return rc;
   if (c.nseq == 0) return 0;
   const AttnTraffic t = attention_traffic(c);
-  AfftKernelScope ktrace(c.dir == kFwd || c.dir == kStep ? AFFT_K_ATTN_FWD : AFFT_K_ATTN_BWD, c.nseq * (c.dir == kStep ? c.Lq : c.L), c.H * c.hd, t.bytes,
+  const bool step = c.dir == kStep || c.dir == kStepBwd;
+  AfftKernelScope ktrace(c.dir == kFwd || c.dir == kStep ? AFFT_K_ATTN_FWD : AFFT_K_ATTN_BWD, c.nseq * (step ? c.Lq : c.L), c.H * c.hd, t.bytes,
                          t.flops, stream);
   if (int rc = check_attention(who, c, late)) return rc;
   const AttnPlan p = plan_attention(c);
   AFFT_CHECK(!p.refusal[0], "%s", p.refusal);
   if (p.family == kGenericShort) return launch_attention_generic(c, p, stream);
-  if (p.family == kStepVec) return launch_attention_step(c, p, stream);
+  if (p.family == kStepVec || p.family == kStepBwdVec) return launch_attention_step(c, p, stream);
   return p.family <= kSlicedBwd ? launch_attention_mfma(c, p, stream) : launch_attention_long(c, p, stream);
 }
 

@@ -1,7 +1,7 @@
 // The dispatch plan of attention: what an entry point was asked (AttnCall), whether the arguments are acceptable (check_attention),
 // which kernel instantiation runs it with which launch geometry (plan_attention), and what the kernel trace records (attention_traffic).
 // Pure host arithmetic over shapes, pitches and pointer alignments -- no HIP runtime call, no global state but the one cached read of
-// AFFT_ATTN_GENERIC (compiles with the plain host compiler) -- and the ONE place that decides: the ten entry points (attention.hip,
+// AFFT_ATTN_GENERIC (compiles with the plain host compiler) -- and the ONE place that decides: the twelve entry points (attention.hip,
 // attention_long.hip, attention_step.hip) check, plan, open the trace scope and hand the plan to the launcher of the family's file, which only maps it to
 // a template instantiation; afft_attention_plan_for reports it.
 #pragma once
@@ -25,7 +25,7 @@ constexpr int QT = 32;                 //   rows of a tile
 constexpr int KB = 64;                 //   rows of the other operand staged at a time (MFMA form)
 constexpr int STEP_QT = 4;             // the cached step (attention_step.hip): query rows of a workgroup, one per wave in its softmax
 
-enum AttnDir { kFwd = 0, kBwd = 1, kBiasBwd = 2, kStep = 3 };
+enum AttnDir { kFwd = 0, kBwd = 1, kBiasBwd = 2, kStep = 3, kStepBwd = 4 };
 
 // what an entry point was asked to do; fields an entry point does not have stay zero
 struct AttnCall {
@@ -55,6 +55,10 @@ struct AttnCall {
   void *k_cache, *v_cache;
   int64_t ldc, cache_seq;
   int Lq, cap;
+  // its backward (kStepBwd): the caches hold all L keys; dq / dk / dv are the gradients of the Lq new rows; the fp32 gradient caches
+  // [nseq, cap, H * hd] (row pitch ldg, sequence stride grad_seq) collect what later steps owe earlier keys
+  float *gk_cache, *gv_cache;
+  int64_t ldg, grad_seq;
 };
 
 inline AttnCall attn_fwd_call(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, int dtype, int nseq, int L,
@@ -78,10 +82,21 @@ inline AttnCall attn_bwd_call(const void* dout, int64_t lddo, const void* q, int
 
 inline AttnCall attn_step_call(const void* q, int64_t ldq, const void* k_new, int64_t ldk, const void* v_new, int64_t ldv, void* k_cache,
                                void* v_cache, int64_t ldc, int64_t cache_seq, int dtype, int nseq, int Lq, int Lk, int cap, int H, int hd,
-                               float scale, void* out, int64_t ldo, float* probs) {
-  AttnCall c = attn_fwd_call(q, ldq, k_new, ldk, v_new, ldv, dtype, nseq, Lk, H, hd, scale, 0.f, 0u, out, ldo, probs);
+                               float scale, void* out, int64_t ldo, float* probs, float drop_p = 0.f, uint32_t drop_key = 0u) {
+  AttnCall c = attn_fwd_call(q, ldq, k_new, ldk, v_new, ldv, dtype, nseq, Lk, H, hd, scale, drop_p, drop_key, out, ldo, probs);
   c.dir = kStep;
   c.k_cache = k_cache; c.v_cache = v_cache; c.ldc = ldc; c.cache_seq = cache_seq; c.Lq = Lq; c.cap = cap;
+  return c;
+}
+inline AttnCall attn_step_bwd_call(const void* dout, int64_t lddo, const void* q, int64_t ldq, const void* k_cache, const void* v_cache,
+                                   int64_t ldc, int64_t cache_seq, int dtype, const float* probs, int nseq, int Lq, int Lk, int cap, int H,
+                                   int hd, float scale, float drop_p, uint32_t drop_key, void* dq, int64_t lddq, void* dk_new, int64_t lddk,
+                                   void* dv_new, int64_t lddv, float* gk_cache, float* gv_cache, int64_t ldg, int64_t grad_seq) {
+  AttnCall c = attn_bwd_call(dout, lddo, q, ldq, nullptr, 0, nullptr, 0, dtype, probs, nseq, Lk, H, hd, scale, drop_p, drop_key, dq, lddq,
+                             dk_new, lddk, dv_new, lddv);
+  c.dir = kStepBwd;
+  c.k_cache = const_cast<void*>(k_cache); c.v_cache = const_cast<void*>(v_cache); c.ldc = ldc; c.cache_seq = cache_seq; c.Lq = Lq; c.cap = cap;
+  c.gk_cache = gk_cache; c.gv_cache = gv_cache; c.ldg = ldg; c.grad_seq = grad_seq;
   return c;
 }
 
@@ -118,6 +133,7 @@ enum : unsigned {
 inline int check_attention(const char* who, const AttnCall& c, unsigned which) {
   const bool ptrs = c.dir == kFwd ? c.q && c.k && c.v && c.out
                     : c.dir == kStep ? c.q && c.k && c.v && c.out && c.k_cache && c.v_cache
+                    : c.dir == kStepBwd ? c.dout && c.q && c.k_cache && c.v_cache && c.probs && c.dq && c.dk && c.dv && c.gk_cache && c.gv_cache
                     : c.dir == kBwd ? c.dout && c.q && c.k && c.v && c.probs && c.dq && c.dk && c.dv
                                     : c.dout && c.v && c.probs && c.dbias;
   AFFT_ATTN_CHECK((!(which & kChkPtrs) || ptrs) && (!(which & kChkBias) || c.bias) && (!(which & kChkRowTerm) || c.row_term),
@@ -144,9 +160,17 @@ inline int check_attention(const char* who, const AttnCall& c, unsigned which) {
     AFFT_ATTN_CHECK(c.Lq >= 1 && c.Lq <= c.L, "%s: %d new rows against %d keys (1 <= Lq <= Lk)", who, c.Lq, c.L);
     AFFT_ATTN_CHECK(c.L <= c.cap, "%s: %d keys do not fit a cache of %d rows", who, c.L, c.cap);
     const int64_t w = (int64_t)c.H * c.hd;
-    AFFT_ATTN_CHECK(c.ldq >= w && c.ldk >= w && c.ldv >= w && c.ldo >= w && c.ldc >= w, "%s: a row pitch is below H * hd = %lld", who, (long long)w);
+    const bool pitches = c.dir == kStep ? c.ldq >= w && c.ldk >= w && c.ldv >= w && c.ldo >= w && c.ldc >= w
+                                        : c.lddo >= w && c.ldq >= w && c.ldc >= w && c.lddq >= w && c.lddk >= w && c.lddv >= w && c.ldg >= w;
+    AFFT_ATTN_CHECK(pitches, "%s: a row pitch is below H * hd = %lld", who, (long long)w);
     AFFT_ATTN_CHECK(c.cache_seq >= (int64_t)(c.cap - 1) * c.ldc + w, "%s: cache sequence stride %lld does not hold %d rows of pitch %lld", who,
                     (long long)c.cache_seq, c.cap, (long long)c.ldc);
+    if (c.dir == kStepBwd) {
+      AFFT_ATTN_CHECK(c.grad_seq >= (int64_t)(c.cap - 1) * c.ldg + w, "%s: gradient cache sequence stride %lld does not hold %d rows of pitch %lld",
+                      who, (long long)c.grad_seq, c.cap, (long long)c.ldg);
+      AFFT_ATTN_CHECK(((((uintptr_t)c.gk_cache) | ((uintptr_t)c.gv_cache) | ((uintptr_t)c.probs)) & 3) == 0,
+                      "%s: the gradient caches and probs must be 4-byte aligned", who);
+    }
   }
   if (which & kChkBiasArgs) {
     const bool grad = c.dir == kBiasBwd;
@@ -172,6 +196,11 @@ inline AttnTraffic attention_traffic(const AttnCall& c) {
     const int64_t row = es * c.nseq * c.H * c.hd, past = c.L - c.Lq;
     return {row * (6 * c.Lq + 2 * past) + (c.probs ? (int64_t)c.nseq * c.H * c.Lq * c.L * 4 : 0), 4 * (int64_t)c.nseq * c.H * c.Lq * c.L * c.hd};
   }
+  if (c.dir == kStepBwd) {   // dout, q read, the L keys and values read, dq / dk_new / dv_new written; the fp32 gradient caches: the past read
+    const int64_t row = (int64_t)c.nseq * c.H * c.hd, past = c.L - c.Lq;      // and written, the new rows read; probs read
+    return {es * row * (5 * c.Lq + 2 * c.L) + 4 * row * (4 * past + 2 * c.Lq) + (int64_t)c.nseq * c.H * c.Lq * c.L * 4,
+            8 * (int64_t)c.nseq * c.H * c.Lq * c.L * c.hd};
+  }
   if (c.dir == kBiasBwd) return {2 * es * rw + (bias_grad_reduces(c) ? 3 : 2) * pb, product};
   // backward: the four products (the long form makes dP twice, once per pass: 10 L^2 hd are executed)
   if (c.dir == kBwd) return {7 * es * rw + pb, 4 * product};
@@ -188,7 +217,8 @@ enum AttnFamily {
   kSlicedBwd = 4,           //                    attn_bwd_sliced_kernel<NT = p0>
   kLongF32 = 5, kLongBf16 = 6, kLongMfma = 7,      // attention_long.hip long_fwd_kernel / long_bwd_q_kernel + long_bwd_kv_kernel
   kBiasF32 = 8, kBiasBf16 = 9, kBiasMfma = 10,     //                    bias_bwd_ds_kernel (+ bias_bwd_reduce_kernel)
-  kStepVec = 11,            // attention_step.hip attn_step_kernel<T, V = p0>: p0 = 1, 16-byte loads; 0, element loads
+  kStepVec = 11,            // attention_step.hip attn_step_kernel<T, V = p0, DROP = p1>: p0 = 1, 16-byte loads; 0, element loads
+  kStepBwdVec = 12,         //                    attn_step_bwd_kernel<T, V = p0>
 };
 
 struct AttnPlan {
@@ -257,7 +287,8 @@ inline bool plan_short_mfma(const AttnCall& c, AttnPlan& p) {
 }
 
 // the cached step: one workgroup per (sequence, head, tile of STEP_QT new rows); LDS = the tile's fp32 scores [rows][Lp] and the P V
-// partial sums of waves 1..3, [3][rows][hd rounded up to 8]
+// partial sums of waves 1..3, [3][rows][hd rounded up to 8].  Its backward: one workgroup per (sequence, head) that walks the tiles with
+// the same carve (dP, then dS; the dS K partial sums) plus the Lq row terms the key pass reads
 inline AttnPlan plan_attention_step(const AttnCall& c) {
   AttnPlan p = {};
   const bool f32 = c.dtype == AFFT_F32;
@@ -266,19 +297,30 @@ inline AttnPlan plan_attention_step(const AttnCall& c) {
     return p;
   }
   const int vec = f32 ? 4 : 8;      // elements of a 16-byte load
-  const bool pitches = c.ldq % vec == 0 && c.ldk % vec == 0 && c.ldv % vec == 0 && c.ldc % vec == 0 && c.cache_seq % vec == 0 && c.ldo % vec == 0;
-  p.family = kStepVec;
-  p.p0 = c.hd % vec == 0 && pitches && al16(c.q) && al16(c.k) && al16(c.v) && al16(c.k_cache) && al16(c.v_cache) && al16(c.out);
   const int rows = c.Lq < STEP_QT ? c.Lq : STEP_QT;
   p.Lp = (c.L + 3) / 4 * 4;
   p.ntiles = (c.Lq + STEP_QT - 1) / STEP_QT;
   p.lds = sizeof(float) * rows * ((size_t)p.Lp + 3 * (size_t)((c.hd + 7) / 8 * 8));
+  if (c.dir == kStepBwd) {      // (fp32 gradient-cache rows start at a column that is a multiple of vec >= 4: float4 accesses need ldg % 4 only)
+    const bool pitches = c.lddo % vec == 0 && c.ldq % vec == 0 && c.ldc % vec == 0 && c.cache_seq % vec == 0 && c.lddq % vec == 0 &&
+                         c.lddk % vec == 0 && c.lddv % vec == 0 && c.ldg % 4 == 0 && c.grad_seq % 4 == 0;
+    p.family = kStepBwdVec;
+    p.p0 = c.hd % vec == 0 && pitches && al16(c.dout) && al16(c.q) && al16(c.k_cache) && al16(c.v_cache) && al16(c.dq) && al16(c.dk) &&
+           al16(c.dv) && al16(c.gk_cache) && al16(c.gv_cache);
+    p.lds += sizeof(float) * (size_t)c.Lq;
+    p.grid = (unsigned)((int64_t)c.nseq * c.H);
+    return p;
+  }
+  const bool pitches = c.ldq % vec == 0 && c.ldk % vec == 0 && c.ldv % vec == 0 && c.ldc % vec == 0 && c.cache_seq % vec == 0 && c.ldo % vec == 0;
+  p.family = kStepVec;
+  p.p0 = c.hd % vec == 0 && pitches && al16(c.q) && al16(c.k) && al16(c.v) && al16(c.k_cache) && al16(c.v_cache) && al16(c.out);
+  p.p1 = c.drop_p > 0.f;
   p.grid = (unsigned)((int64_t)c.nseq * c.H * p.ntiles);
   return p;
 }
 
 inline AttnPlan plan_attention(const AttnCall& c) {
-  if (c.dir == kStep) return plan_attention_step(c);
+  if (c.dir == kStep || c.dir == kStepBwd) return plan_attention_step(c);
   AttnPlan p = {};
   const bool f32 = c.dtype == AFFT_F32, bf16 = c.dtype == AFFT_BF16;
   if (c.L < 1 || c.L > LHI || (!c.planes && (c.hd < 1 || c.hd > 1024 || (!f32 && !bf16)))) {

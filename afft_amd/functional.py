@@ -1217,15 +1217,21 @@ class MLPSublayer(torch.autograd.Function):
 class KVCache:
     """Keys and values of every layer of a causal model for `B` sequences of up to `cap` positions: per layer two [B, cap, D] buffers
     (one allocation from torch's allocator) in the storage dtype the current precision gives its call-by-call attention core (bf16 in
-    'bf16', else fp32), and `len`, the positions filled so far -- advanced by the model once all its layers have appended."""
-    __slots__ = ("kv", "cap", "len")
+    'bf16', else fp32), and `len`, the positions filled so far -- advanced by the model once all its layers have appended.
+    grad=True (the training roll-out only): a gradient twin `gkv`, fp32 and zero-filled, of the same shape -- what later steps of the
+    roll-out owe every cached key and value (afft_attention_step_bwd's write rule)."""
+    __slots__ = ("kv", "gkv", "cap", "len")
 
-    def __init__(self, n_layer: int, B: int, cap: int, D: int, device):
+    def __init__(self, n_layer: int, B: int, cap: int, D: int, device, grad: bool = False):
         self.kv = torch.empty(n_layer, 2, B, cap, D, dtype=rt.act_dtype(), device=device)
+        self.gkv = torch.zeros(n_layer, 2, B, cap, D, dtype=torch.float32, device=device) if grad else None
         self.cap, self.len = cap, 0
 
     def layer(self, i: int) -> Tuple[Tensor, Tensor]:
         return self.kv[i, 0], self.kv[i, 1]
+
+    def grad_layer(self, i: int) -> Tuple[Tensor, Tensor]:
+        return self.gkv[i, 0], self.gkv[i, 1]
 
 
 def attn_step(x: Tensor, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, Lq: int, H: int, eps: float, conv1d: bool, k_cache: Tensor,
@@ -1252,6 +1258,73 @@ def mlp_step(x: Tensor, ln_w, ln_b, w1, b1, w2, b2, eps: float, gelu: str, conv1
     h = Act(R, hidden, x.device)
     _lin_fwd(xn, w1, conv1d, h.live, bias=b1, act=_GELU[gelu][0])
     return _cbc_out(x, h, w2, conv1d, b2, True, None, w2.shape[1] if conv1d else w2.shape[0])
+
+
+# --------------------------------------------------------------------------- cached roll-out with a backward pass
+_ATTN_STEP_NARGS = 18      # AttnStepSublayer.forward
+
+
+class AttnStepSublayer(torch.autograd.Function):
+    """AttnSublayer (pre-LN, causal) on the Lq NEW rows per sequence of x fp32 [nseq * Lq, d], at positions past .. past + Lq - 1: its
+    call-by-call sequence with the attention core replaced by the cached step (afft_attention_step_fwd / _fwd_drop, afft_attention_step_bwd),
+    so gradient sink, first-touch rules, hand-over, side stream and fused-optimizer bookkeeping are AttnSublayer's.
+    Returns (y fp32 [nseq * Lq, d], probs fp32 [nseq, H, Lq, past + Lq]).
+
+    The key / value caches and their fp32 gradient twins are shared, mutable state OUTSIDE autograd: the forward appends this step's keys
+    and values, the backward adds what this step owes earlier rows to the gradient caches and reads what later steps owe its own rows.
+    That is sound because of how a roll-out is wired: step i's input is step i - 1's last hidden row, so every backward node of step i
+    runs before any backward node of step i - 1 -- the gradient-cache rows of step i - 1 are complete when that step reads them -- and
+    a later step's forward writes cache rows at or beyond this step's Lk only, which this step's backward never reads."""
+
+    @staticmethod
+    def forward(ctx, x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, Lq, H, eps, conv1d, drop, k_cache, v_cache, gk_cache, gv_cache, past,
+                probs_out=None):
+        R, d = x.shape
+        nseq, hd, Lk = R // Lq, d // H, past + Lq
+        dev = x.device
+        ctx.set_materialize_grads(False)      # probs takes no gradient (AttnSublayer.forward)
+        xn, mean, rstd = _cbc_ln_in(ctx, x, ln_w, ln_b, eps, True)
+        qkv = Act(R, 3 * d, dev)
+        _lin_fwd(xn, w_qkv, conv1d, qkv.live, bias=b_qkv)
+        ao = Act(R, d, dev)
+        probs = probs_out if probs_out is not None else torch.empty(nseq, H, Lq, Lk, dtype=torch.float32, device=dev)
+        scale = float(hd) ** -0.5
+        ops.attention_step(qkv.cols(0, d), qkv.cols(d, 2 * d), qkv.cols(2 * d, 3 * d), k_cache, v_cache, nseq, Lq, Lk, H, hd, scale, ao.live,
+                           probs, drop=_attn_drop(drop))
+        y = _cbc_out(x, ao, w_proj, conv1d, b_proj, True, drop, d)
+        ctx.save_for_backward(x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, mean, rstd, probs)
+        ctx.acts = (xn, qkv, ao)
+        ctx.caches = (k_cache, v_cache, gk_cache, gv_cache)
+        ctx.cfg = (Lq, Lk, H, scale, conv1d, drop)
+        ctx.mark_non_differentiable(probs)
+        return y, probs
+
+    @staticmethod
+    @_in_backward_precision
+    def backward(ctx, dy, _dprobs):
+        if dy is None:
+            _drop_shadow()
+            flush_ready()
+            return _pad((), _ATTN_STEP_NARGS)
+        x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, mean, rstd, probs = ctx.saved_tensors
+        xn, qkv, ao = ctx.acts
+        k_cache, v_cache, gk_cache, gv_cache = ctx.caches
+        Lq, Lk, H, scale, conv1d, drop = ctx.cfg
+        R, d = x.shape
+        nseq, hd = R // Lq, d // H
+        dev = x.device
+        dy, dya, g_wp, g_bp = _cbc_bwd_open(dy, drop, b_proj, ao, w_proj, conv1d)
+        dao = Act(R, d, dev)
+        _lin_dgrad(dya, w_proj, conv1d, dao.live)
+        dqkv = Act(R, 3 * d, dev)
+        ops.attention_step_bwd(dao.live, qkv.cols(0, d), k_cache, v_cache, probs, nseq, Lq, Lk, H, hd, scale, dqkv.cols(0, d),
+                               dqkv.cols(d, 2 * d), dqkv.cols(2 * d, 3 * d), gk_cache, gv_cache, drop=_attn_drop(drop))
+        ctx.caches = None
+        with _Side(dev):
+            g_wq = _wgrad(dqkv, xn, w_qkv, conv1d)
+            g_bq = _bgrad(dqkv.live, b_qkv)
+        dx, g_lw, g_lb = _cbc_bwd_close(ctx, dqkv, w_qkv, conv1d, x, ln_w, ln_b, mean, rstd, dy, True)
+        return _pad((dx, g_lw, g_lb, g_wq, g_bq, g_wp, g_bp), _ATTN_STEP_NARGS)
 
 
 # --------------------------------------------------------------------------- pre-LN cross-attention sub-layer

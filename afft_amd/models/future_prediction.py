@@ -93,6 +93,17 @@ class GPT2Block(nn.Module):
         return h, probs
 
 
+    def forward_step_train(self, h: Tensor, Lq: int, caches, past: int, probs_out=None):
+        """forward_step with a backward pass and dropout (F_.AttnStepSublayer, F_.MLPSublayer); caches: (k, v, grad k, grad v) of the layer"""
+        a, m = self.attn, self.mlp
+        h, probs = F_.AttnStepSublayer.apply(h, self.ln_1.weight, self.ln_1.bias, a.c_attn.weight, a.c_attn.bias, a.c_proj.weight,
+                                             a.c_proj.bias, Lq, a.num_heads, self.ln_1.eps, True,
+                                             D_.cfg(self, attn=a.attn_dropout.p, out=a.resid_dropout.p), *caches, past, probs_out)
+        h = F_.MLPSublayer.apply(h, self.ln_2.weight, self.ln_2.bias, m.c_fc.weight, m.c_fc.bias, m.c_proj.weight,
+                                 m.c_proj.bias, self.ln_2.eps, "tanh", True, True, D_.cfg(self, out=m.dropout.p))
+        return h, probs
+
+
 class GPT2Model(nn.Module):
     """The slice of HF GPT2Model the reference uses: inputs_embeds + wpe[position_ids] -> drop -> blocks -> ln_f."""
 
@@ -125,8 +136,8 @@ class GPT2Model(nn.Module):
         h = F_.LayerNormRows.apply(h, self.ln_f.weight, self.ln_f.bias, self.ln_f.eps, 1)
         return h, attns
 
-    def new_cache(self, B: int, cap: int, device) -> "F_.KVCache":
-        return F_.KVCache(len(self.h), B, cap, self.embed_dim, device)
+    def new_cache(self, B: int, cap: int, device, grad: bool = False) -> "F_.KVCache":
+        return F_.KVCache(len(self.h), B, cap, self.embed_dim, device, grad=grad)
 
     def forward_step(self, x_rows: Tensor, Lq: int, cache: "F_.KVCache", want_attn: bool = False):
         """x_rows fp32 [B*Lq, D]: the Lq NEW frames per clip, at positions cache.len .. cache.len + Lq - 1; every layer appends their keys
@@ -148,6 +159,28 @@ class GPT2Model(nn.Module):
         F_._forget_output()
         cache.len = past + Lq
         return y, attns
+
+
+    def forward_step_train(self, x_rows: Tensor, Lq: int, cache: "F_.KVCache", want_attn: bool = False):
+        """forward_step as a node of the autograd graph (training mode and / or grad enabled): the same rows, positions and cache
+        traffic through the Functions forward_rows uses -- AddRowTable at positions cache.len .. cache.len + Lq - 1, the embedding
+        dropout, AttnStepSublayer / MLPSublayer per block, LayerNormRows.  `cache` was made with grad=True."""
+        past = cache.len
+        if cache.gkv is None:
+            raise ValueError("GPT2Model.forward_step_train needs a cache with a gradient twin (new_cache(..., grad=True))")
+        if past + Lq > min(cache.cap, self.wpe.weight.shape[0]):
+            raise ValueError(f"GPT2Model.forward_step_train: positions {past}..{past + Lq - 1} exceed the cache ({cache.cap}) or n_positions")
+        h = F_.AddRowTable.apply(x_rows, self.wpe.weight, Lq, past)
+        if self.training and self.drop.p > 0:
+            h = F_.ElementDropout.apply(h, D_.elementwise(self.drop.p))
+        attns = []
+        for i, blk in enumerate(self.h):
+            h, probs = blk.forward_step_train(h, Lq, cache.layer(i) + cache.grad_layer(i), past)
+            if want_attn:
+                attns.append(probs)
+        h = F_.LayerNormRows.apply(h, self.ln_f.weight, self.ln_f.bias, self.ln_f.eps, 1)
+        cache.len = past + Lq
+        return h, attns
 
 
 class BaseFuturePredictor(nn.Module):
@@ -180,14 +213,18 @@ class BaseFuturePredictor(nn.Module):
         observed frames run once through GPT2Model.forward_step, which leaves every layer's keys and values in a KVCache, and every
         further frame is ONE new row per clip attending to the cache (afft_attention_step_fwd).  With grad enabled, in training mode or
         with AFFT_KV_CACHE=0 the roll-out re-runs the extended sequence for every predicted frame and keeps its last row -- a causal
-        model's earlier positions do not change when a token is appended, so that is the same arithmetic without a cache, and it is the
-        form that has a backward pass."""
+        model's earlier positions do not change when a token is appended, so that is the same arithmetic without a cache.  With
+        runtime.kv_cache_train() (AFFT_KV_CACHE_TRAIN=1, off by default) those passes go over the cache too, as the reference trains
+        through HF's: GPT2Model.forward_step_train, whose attention step has a backward pass."""
         addl_endpoints = {}
         feats = self._map(self.encoder, feats)
         B, T, D = feats.shape
         seq = feats if feats.dtype == torch.float32 else feats.float()
         if output_len > 1 and rt.kv_cache() and not torch.is_grad_enabled() and not self.training and rt.precision() != "fp16x2":
             return self._rollout_cached(seq, output_len, addl_endpoints)
+        if (output_len > 1 and rt.kv_cache() and rt.kv_cache_train() and (torch.is_grad_enabled() or self.training)
+                and rt.precision() in ("bf16", "fp32", "bf16x3")):
+            return self._rollout_cached_train(seq, output_len, addl_endpoints)
         outs: List[Tensor] = []
         for output_id in range(output_len):
             L = seq.shape[1]
@@ -211,6 +248,23 @@ class BaseFuturePredictor(nn.Module):
         for output_id in range(output_len):
             Lq = T if output_id == 0 else 1
             h, attns = self.gpt_model.forward_step(new, Lq, cache, self.output_attentions)
+            if self.output_attentions:
+                addl_endpoints[f'gpt2_att_{output_id}'] = torch.stack(attns, dim=1)      # (B, layers, H, Lq, Lk)
+            h = h.view(B, Lq, D)
+            outs.append(self._map(self.decoder, h))
+            new = h[:, -1, :].contiguous()
+        return torch.cat(outs, dim=1), addl_endpoints
+
+    def _rollout_cached_train(self, seq: Tensor, output_len: int, addl_endpoints: Dict) -> Tuple[torch.Tensor, Dict]:
+        """_rollout_cached inside the autograd graph: the fed-back row stays a node of it, so the loss on frame T + i reaches the
+        parameters through every earlier step, and through the cache (F_.AttnStepSublayer)"""
+        B, T, D = seq.shape
+        cache = self.gpt_model.new_cache(B, T + output_len - 1, seq.device, grad=True)
+        outs: List[Tensor] = []
+        new = seq.reshape(B * T, D).contiguous()
+        for output_id in range(output_len):
+            Lq = T if output_id == 0 else 1
+            h, attns = self.gpt_model.forward_step_train(new, Lq, cache, self.output_attentions)
             if self.output_attentions:
                 addl_endpoints[f'gpt2_att_{output_id}'] = torch.stack(attns, dim=1)      # (B, layers, H, Lq, Lk)
             h = h.view(B, Lq, D)

@@ -3,7 +3,7 @@ streams only; every computation below runs in the hand-written HIP kernels of li
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Tuple
 
 import torch
 
@@ -393,24 +393,54 @@ def attention_bias_bwd(dout: Tensor, v: Tensor, probs: Tensor, nseq: int, L_: in
     return dbias
 
 
+def _cache_pair(k_cache: Tensor, v_cache: Tensor, nseq: int, width: int, what: str):
+    if k_cache.dim() != 3 or k_cache.shape != v_cache.shape or k_cache.stride() != v_cache.stride() or k_cache.stride(2) != 1:
+        raise ValueError(f"afft_amd: the {what} must be two [nseq, cap, H*hd] tensors of one layout with unit column stride, got "
+                         f"{tuple(k_cache.shape)} {k_cache.stride()} and {tuple(v_cache.shape)} {v_cache.stride()}")
+    if k_cache.shape[0] != nseq or k_cache.shape[2] != width:
+        raise ValueError(f"afft_amd: {what} of shape {tuple(k_cache.shape)} for nseq = {nseq}, H * hd = {width}")
+
+
 def attention_step(q: Tensor, k_new: Tensor, v_new: Tensor, k_cache: Tensor, v_cache: Tensor, nseq: int, Lq: int, Lk: int, H: int, hd: int,
-                   scale: float, out: Tensor, probs: Optional[Tensor]) -> Tensor:
+                   scale: float, out: Tensor, probs: Optional[Tensor], drop: Optional[Tuple[float, int]] = None) -> Tensor:
     """one step of a cached roll-out (afft_attention_step_fwd): causal attention of the Lq new rows per sequence (q / k_new / v_new
     [nseq * Lq, H * hd] views) against k_cache / v_cache [nseq, cap, H * hd], whose rows [Lk - Lq, Lk) become k_new / v_new in the same
-    launch; probs (optional) fp32 [nseq, H, Lq, Lk]"""
+    launch; probs (optional) fp32 [nseq, H, Lq, Lk], pre-dropout.  drop = (p, key) with p > 0: attention-probability dropout
+    (afft_attention_step_fwd_drop); anything else is the entry point without dropout"""
     assert q.dtype == k_new.dtype == v_new.dtype == k_cache.dtype == v_cache.dtype == out.dtype
-    if k_cache.dim() != 3 or k_cache.shape != v_cache.shape or k_cache.stride() != v_cache.stride() or k_cache.stride(2) != 1:
-        raise ValueError(f"afft_amd: the caches must be two [nseq, cap, H*hd] tensors of one layout with unit column stride, got "
-                         f"{tuple(k_cache.shape)} {k_cache.stride()} and {tuple(v_cache.shape)} {v_cache.stride()}")
-    if k_cache.shape[0] != nseq or k_cache.shape[2] != H * hd:
-        raise ValueError(f"afft_amd: caches of shape {tuple(k_cache.shape)} for nseq = {nseq}, H * hd = {H * hd}")
+    _cache_pair(k_cache, v_cache, nseq, H * hd, "caches")
     if probs is not None:
         assert probs.dtype == torch.float32 and probs.is_contiguous() and probs.numel() == nseq * H * Lq * Lk
+    if drop is not None and drop[0] > 0:
+        L.check(L.lib().afft_attention_step_fwd_drop(_p(q), _rowmajor(q, "q"), _p(k_new), _rowmajor(k_new, "k_new"), _p(v_new),
+                                                     _rowmajor(v_new, "v_new"), _p(k_cache), _p(v_cache), k_cache.stride(1), k_cache.stride(0),
+                                                     _dt(q), nseq, Lq, Lk, k_cache.shape[1], H, hd, scale, float(drop[0]), int(drop[1]),
+                                                     _p(out), _rowmajor(out, "out"), _p(probs), _stream()), "attention_step_drop")
+        return out
     L.check(L.lib().afft_attention_step_fwd(_p(q), _rowmajor(q, "q"), _p(k_new), _rowmajor(k_new, "k_new"), _p(v_new), _rowmajor(v_new, "v_new"),
                                             _p(k_cache), _p(v_cache), k_cache.stride(1), k_cache.stride(0), _dt(q), nseq, Lq, Lk,
                                             k_cache.shape[1], H, hd, scale, _p(out), _rowmajor(out, "out"), _p(probs), _stream()),
             "attention_step")
     return out
+
+
+def attention_step_bwd(dout: Tensor, q: Tensor, k_cache: Tensor, v_cache: Tensor, probs: Tensor, nseq: int, Lq: int, Lk: int, H: int,
+                       hd: int, scale: float, dq: Tensor, dk_new: Tensor, dv_new: Tensor, gk_cache: Tensor, gv_cache: Tensor,
+                       drop: Optional[Tuple[float, int]] = None):
+    """the backward of attention_step (afft_attention_step_bwd): dq / dk_new / dv_new [nseq * Lq, H * hd] views from dout, q, the caches as
+    the forward left them (rows [0, Lk) valid) and its probs; gk_cache / gv_cache fp32 [nseq, cap, H * hd] collect what this step owes
+    the keys and values before its own (rows < Lk - Lq: +=) and hold what later steps owe its new rows (read into dk_new / dv_new)"""
+    assert dout.dtype == q.dtype == k_cache.dtype == v_cache.dtype == dq.dtype == dk_new.dtype == dv_new.dtype
+    _cache_pair(k_cache, v_cache, nseq, H * hd, "caches")
+    _cache_pair(gk_cache, gv_cache, nseq, H * hd, "gradient caches")
+    assert gk_cache.dtype == gv_cache.dtype == torch.float32 and gk_cache.shape[1] == k_cache.shape[1]
+    assert probs.dtype == torch.float32 and probs.is_contiguous() and probs.numel() == nseq * H * Lq * Lk
+    p, key = drop if drop is not None and drop[0] > 0 else (0.0, 0)
+    L.check(L.lib().afft_attention_step_bwd(_p(dout), _rowmajor(dout, "dout"), _p(q), _rowmajor(q, "q"), _p(k_cache), _p(v_cache),
+                                            k_cache.stride(1), k_cache.stride(0), _dt(q), _p(probs), nseq, Lq, Lk, k_cache.shape[1], H, hd,
+                                            scale, float(p), int(key), _p(dq), _rowmajor(dq, "dq"), _p(dk_new), _rowmajor(dk_new, "dk_new"),
+                                            _p(dv_new), _rowmajor(dv_new, "dv_new"), _p(gk_cache), _p(gv_cache), gk_cache.stride(1),
+                                            gk_cache.stride(0), _stream()), "attention_step_bwd")
 
 
 def softmax_ce(logits: Tensor, C_: int, *, labels: Optional[Tensor] = None, soft: Optional[Tensor] = None,

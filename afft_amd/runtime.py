@@ -541,6 +541,22 @@ def set_kv_cache(on: bool):
     _KV_CACHE = bool(on)
 
 
+_KV_CACHE_TRAIN = os.environ.get("AFFT_KV_CACHE_TRAIN", "0") == "1"
+
+
+def kv_cache_train() -> bool:
+    """Train THROUGH the key / value cache, as the reference trains through HF's: with grad enabled or in training mode the roll-out
+    (output_len > 1, kv_cache() on, precision 'bf16', 'fp32' or 'bf16x3') runs T + output_len - 1 predictor rows per clip instead of
+    re-running the extended sequence for every predicted frame (functional.AttnStepSublayer, afft_attention_step_bwd).
+    AFFT_KV_CACHE_TRAIN=1; off by default: the recompute stays the training form until this one is made the default."""
+    return _KV_CACHE_TRAIN
+
+
+def set_kv_cache_train(on: bool):
+    global _KV_CACHE_TRAIN
+    _KV_CACHE_TRAIN = bool(on)
+
+
 _FUSED_SGD = os.environ.get("AFFT_FUSED_SGD", "1") != "0"
 
 

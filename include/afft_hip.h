@@ -324,8 +324,8 @@ int afft_attention_bias_bwd(const void* dout, int64_t lddo, const void* v, int64
                             int32_t nseq, int32_t L, int32_t H, int32_t hd, float drop_p, uint32_t drop_key, float* dbias,
                             int64_t sb, int64_t sh, int64_t si, float* scratch, void* stream);
 
-/* Which attention kernel a call gets (the plan the nine entry points above launch from, csrc/attn_plan.h; the tenth, the cached step
- * below, has a query of its own); launches nothing and needs
+/* Which attention kernel a call gets (the plan the nine entry points above launch from, csrc/attn_plan.h; the cached step
+ * below has a query of its own); launches nothing and needs
  * no device.  direction: 0 forward, 1 backward, 2 bias gradient; dtype: AFFT_F32 / AFFT_BF16; planes != 0: the fp16x2 forward
  * (afft_attention_fwd_split; in_lo != 0: two planes per input); pitch_alignment_ok: rows and pointers take 16-byte loads.
  * Returns family * 10000 + p0 * 10 + p1 -- family 1: generic short kernels, p0 = LM (32 / 64 / 128); 2: MFMA short forward, p0 = NT,
@@ -341,14 +341,43 @@ int afft_attention_plan_for(int32_t direction, int32_t dtype, int32_t L, int32_t
  * of the QKV GEMM output).  k_cache / v_cache: [nseq, cap, H*hd] in the same dtype, row pitch ldc and sequence stride cache_seq (ELEMENTS,
  * both caches alike), valid in rows [0, Lk - Lq) on entry.  On return rows [Lk - Lq, Lk) of both caches hold k_new / v_new bit for bit
  * (no other cache row is written); query row i sits at position Lk - Lq + i and attends to keys 0 .. Lk - Lq + i; softmax in fp32 over the
- * whole row; out: [nseq * Lq, H*hd] in `dtype`; probs (optional): fp32 [nseq, H, Lq, Lk], masked entries exactly 0.  No dropout: an
- * inference path.  1 <= Lq <= Lk <= cap, Lk <= 512, 1 <= hd <= 1024, dtype AFFT_F32 / AFFT_BF16; anything else is an error and nothing is
+ * whole row; out: [nseq * Lq, H*hd] in `dtype`; probs (optional): fp32 [nseq, H, Lq, Lk], masked entries exactly 0.  No dropout (the
+ * inference path; afft_attention_step_fwd_drop below is the training form).  1 <= Lq <= Lk <= cap, Lk <= 512, 1 <= hd <= 1024, dtype AFFT_F32 / AFFT_BF16; anything else is an error and nothing is
  * launched.  Lq == Lk is the first pass: it fills the cache and agrees with afft_attention_fwd(mask = causal) to rounding.  fp32 arithmetic,
  * no atomics, sums in a fixed order (bitwise reproducible); 16-byte loads when hd, the pitches and the pointers allow them. */
 int afft_attention_step_fwd(const void* q, int64_t ldq, const void* k_new, int64_t ldk, const void* v_new, int64_t ldv,
                             void* k_cache, void* v_cache, int64_t ldc, int64_t cache_seq, int32_t dtype, int32_t nseq,
                             int32_t Lq, int32_t Lk, int32_t cap, int32_t H, int32_t hd, float scale, void* out, int64_t ldo,
                             float* probs, void* stream);
+/* The same step with attention-probability dropout, for training through the cache: afft_attention_step_fwd plus drop_p / drop_key, by the
+ * convention of afft_attention_fwd -- probs receives the PRE-dropout probabilities, the product uses P' = P o M with M = 1 / (1 - drop_p)
+ * for a kept element and 0 for a dropped one; an element is kept or dropped by its index in probs[nseq, H, Lq, Lk] and drop_key (xor the
+ * device salt of afft_set_dropout_salt), so the backward regenerates the mask.  0 <= drop_p < 1; drop_p = 0 runs the very kernel of
+ * afft_attention_step_fwd (the same bits). */
+int afft_attention_step_fwd_drop(const void* q, int64_t ldq, const void* k_new, int64_t ldk, const void* v_new, int64_t ldv,
+                                 void* k_cache, void* v_cache, int64_t ldc, int64_t cache_seq, int32_t dtype, int32_t nseq,
+                                 int32_t Lq, int32_t Lk, int32_t cap, int32_t H, int32_t hd, float scale, float drop_p,
+                                 uint32_t drop_key, void* out, int64_t ldo, float* probs, void* stream);
+/* The backward of that step, written so that a roll-out can be trained THROUGH the cache.  dout, q: [nseq * Lq, *] in `dtype`, own row
+ * pitches; k_cache / v_cache: as the forward left them, rows [0, Lk) valid (read only); probs: the forward's fp32 [nseq, H, Lq, Lk];
+ * scale, drop_p, drop_key: the forward's.  With past = Lk - Lq and query row i seeing keys 0 .. past + i:
+ *   dP' = dO V^T, dP = dP' o M, r_i = sum_j P_ij dP_ij, dS = P o (dP - r), dq = scale dS K, cK = scale dS^T Q, cV = P'^T dO.
+ * dq, dk_new, dv_new: [nseq * Lq, *] in `dtype`, own row pitches (the three column blocks of one dqkv buffer, for instance).
+ * gk_cache / gv_cache: fp32 [nseq, cap, H*hd], row pitch ldg and sequence stride grad_seq (ELEMENTS, both alike), 4-byte aligned: the
+ * gradients that LATER steps of the roll-out owe each cached key and value.  Write rule: rows j < past take gk_cache[j] += cK[j],
+ * gv_cache[j] += cV[j]; rows past <= j < Lk are read and not written: dk_new[j - past] = gk_cache[j] + cK[j] cast to `dtype`, dv_new
+ * alike -- by the time a step's backward runs, every later step has left its share in those rows.  Rows >= Lk of the gradient caches
+ * and the key / value caches are neither read nor written beyond that.  The caller zero-fills the gradient caches once per roll-out and
+ * runs the steps' backwards last step first.
+ * 1 <= Lq <= Lk <= cap, Lk <= 512, 1 <= hd <= 1024, AFFT_F32 / AFFT_BF16; anything else is an error and nothing is launched.  One
+ * workgroup per (sequence, head) owns its hd columns of every row: no atomics, sums in a fixed order (bitwise reproducible), fp32
+ * arithmetic; two passes (per query tile r_i and dq; per key dP again, then cK and cV); 16-byte accesses when hd, the pitches and the
+ * pointers allow them. */
+int afft_attention_step_bwd(const void* dout, int64_t lddo, const void* q, int64_t ldq, const void* k_cache, const void* v_cache,
+                            int64_t ldc, int64_t cache_seq, int32_t dtype, const float* probs, int32_t nseq, int32_t Lq,
+                            int32_t Lk, int32_t cap, int32_t H, int32_t hd, float scale, float drop_p, uint32_t drop_key,
+                            void* dq, int64_t lddq, void* dk_new, int64_t lddk, void* dv_new, int64_t lddv, float* gk_cache,
+                            float* gv_cache, int64_t ldg, int64_t grad_seq, void* stream);
 /* The plan of such a step (csrc/attn_plan.h plan_attention_step), as afft_attention_plan_for reports the others: launches nothing and
  * needs no device.  Returns family * 10000 + p0 * 10 -- family 11, p0 = 1: 16-byte loads, 0: element loads -- and, when lds_and_tiles is
  * not NULL, the dynamic LDS bytes of the launch in lds_and_tiles[0] and the workgroups per (sequence, head) in lds_and_tiles[1]; a negative

@@ -1,0 +1,251 @@
+"""GPU: the roll-out of the future predictor TRAINED through the key / value cache (runtime.kv_cache_train, BaseFuturePredictor.
+_rollout_cached_train, GPT2Model.forward_step_train, functional.AttnStepSublayer, afft_attention_step_bwd) at model level: outputs and the
+gradient of every parameter of the tiny roll-out configuration (t2_roll, fp_output_len = 3) against the recompute, against the oracle under
+torch autograd and against the reference's golden, within the bars tests/test_model_gpu.py applies to the recompute (fp32 1e-3; bf16 2e-2
+on outputs, 2.5e-2 on gradients); once at the real head size; and one training step with dropout through parallel.Trainer."""
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from cases import oracle_cfg  # noqa: E402
+from helpers import case_tensors, flatten_outputs, load_golden, max_rel, rel_l2, surrogate  # noqa: E402
+
+TOL = {"fp32": 1e-3, "bf16": 2e-2}      # tests/test_model_gpu.py TOL
+GTOL = {"fp32": 1e-3, "bf16": 2.5e-2}   # ... and its gradient bars (GTOL_BF16)
+NAME = "t2_roll"
+_REF = {}
+
+
+def _reference():
+    """the golden, the case's tensors, and the oracle's outputs and gradients of the surrogate loss: made once, shared, never modified"""
+    if not _REF:
+        from oracle import afft_oracle as O
+        z, _ = load_golden(NAME)
+        c, state, data, tgt, sub = case_tensors(NAME)
+        P = {k: (v.clone().requires_grad_(True) if v.is_floating_point() else v.clone()) for k, v in state.items()}
+        oout = O.base_model_forward(P, data, oracle_cfg(c))
+        surrogate(oout).backward()
+        _REF.update(z=z, c=c, state=state, data=data, tgt=tgt, sub=sub,
+                    out={k: v.detach() for k, v in flatten_outputs(oout).items() if torch.is_tensor(v)},
+                    grad={k: v.grad.detach() for k, v in P.items() if v.requires_grad and v.grad is not None})
+    return _REF
+
+
+class _count_steps:
+    """how many times ops.attention_step and ops.attention_step_bwd ran inside the block"""
+
+    def __enter__(self):
+        from afft_amd import ops
+        self.ops, self.real, self.fwd, self.bwd = ops, (ops.attention_step, ops.attention_step_bwd), 0, 0
+
+        def fwd(*a, **k):
+            self.fwd += 1
+            return self.real[0](*a, **k)
+
+        def bwd(*a, **k):
+            self.bwd += 1
+            return self.real[1](*a, **k)
+        ops.attention_step, ops.attention_step_bwd = fwd, bwd
+        return self
+
+    def __exit__(self, *exc):
+        self.ops.attention_step, self.ops.attention_step_bwd = self.real
+
+
+@pytest.fixture()
+def switch():
+    import afft_amd
+    from afft_amd import runtime as rt
+    saved = rt.kv_cache(), rt.kv_cache_train()
+    yield rt
+    rt.set_kv_cache(saved[0])
+    rt.set_kv_cache_train(saved[1])
+    rt.set_grad_mode("sink")
+    afft_amd.set_precision("bf16")
+
+
+def _model(precision):
+    import afft_amd
+    from afft_amd import runtime as rt
+    from afft_amd.config import make_model_cfg
+    from afft_amd.models.base_model import BaseModel
+    r = _reference()
+    c = r["c"]
+    afft_amd.set_precision(precision)
+    rt.set_grad_mode("sink")
+    cfg = make_model_cfg(c["modal_dims"], c["d"], c["D"], fuser=c["fuser"], depth=c["depth"], num_heads=c["num_heads"],
+                         fp_layers=c["fp_layers"], fp_heads=c["fp_heads"], fp_output_len=c["fp_output_len"], T=c["T"])
+    model = BaseModel(cfg, num_classes={"action": c["num_classes"]}, class_mappings={})
+    model.load_state_dict(r["state"], strict=True)
+    return model.cuda()
+
+
+def _forward_backward(model):
+    """one forward with grad enabled and the backward of the surrogate loss: (outputs, gradients, step calls forward, backward)"""
+    from afft_amd import runtime as rt
+    r = _reference()
+    dev = torch.device("cuda:0")
+    rt.SINK.begin_step()
+    for p in model.parameters():
+        p.grad = None
+    with _count_steps() as n:
+        out, _ = model({m: d.to(dev) for m, d in r["data"].items()}, mixup_fn=None, target={"action": r["tgt"].to(dev)},
+                       target_subclips={"action": r["sub"].to(dev)}, target_subclips_ignore_index=None)
+        surrogate(out).backward()
+        rt.SINK.finish_step(list(model.parameters()))
+    torch.cuda.synchronize()
+    flat = {k: v.detach().float().cpu() for k, v in flatten_outputs(out).items() if torch.is_tensor(v)}
+    grads = {k: p.grad.detach().float().cpu().clone() for k, p in model.named_parameters() if p.grad is not None}
+    return flat, grads, n.fwd, n.bwd
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_t2_roll_cached_train_against_recompute_oracle_and_golden(precision, switch):
+    """Drop rates 0 (evaluation mode), grad enabled.  fp32: cached-train against recompute is bounded by 10 x the recompute's own worst
+    distance from the oracle (outputs and gradients each; both paths are fp32-grade evaluations of one function that add the same terms
+    in another order), as tests/test_rollout_cache_gpu.py bounds the inference path; bf16: the mode's bars."""
+    r = _reference()
+    c, z = r["c"], r["z"]
+    tol, gtol = TOL[precision], GTOL[precision]
+    model = _model(precision).eval()
+    runs = {}
+    for on in (False, True):
+        switch.set_kv_cache_train(on)
+        runs[on] = _forward_backward(model)
+        steps = c["fp_layers"] * c["fp_output_len"] if on else 0
+        assert runs[on][2] == steps and runs[on][3] == steps                # the path under test is the one that ran
+    names = [k for k, _ in model.named_parameters()]
+    worst = {}
+    for on in (False, True):
+        flat, grads = runs[on][:2]
+        assert sorted(grads) == sorted(names)                               # every parameter takes a gradient
+        w_out = w_grad = 0.0
+        for k, ref in r["out"].items():                                     # against the oracle under torch autograd
+            if k.startswith("attentions"):
+                continue
+            e = rel_l2(flat[k], ref.float())
+            w_out = max(w_out, e)
+            assert e < tol, (on, k, e)
+        for k, ref in r["grad"].items():
+            e = rel_l2(grads[k], ref.float())
+            w_grad = max(w_grad, e)
+            assert e < gtol, (on, k, e)
+        checked = 0
+        for k in z.files:                                                   # against the golden, where it holds them
+            if k.startswith("out:") and not k.startswith("out:attentions"):
+                ref = torch.from_numpy(z[k])
+                e, em = rel_l2(flat[k[4:]], ref), max_rel(flat[k[4:]], ref)
+                assert e < tol and em < tol * 3, (on, k, e, em)
+                checked += 1
+            elif k.startswith("grad:"):
+                e = rel_l2(grads[k[5:]], torch.from_numpy(z[k]))
+                assert e < gtol, (on, k, e)
+                checked += 1
+        assert checked >= 11
+        for nm, gn in zip([str(s) for s in z["gradnames"]], z["gradnorm"]):
+            assert abs(float(grads[nm].norm()) - gn) < gtol * max(gn, 1e-3) * 2, (on, nm, float(grads[nm].norm()), gn)
+        worst[on] = (w_out, w_grad)
+    d_out = max(rel_l2(runs[True][0][k], runs[False][0][k]) for k in r["out"] if not k.startswith("attentions"))
+    d_grad = max(rel_l2(runs[True][1][k], runs[False][1][k]) for k in names)
+    print(f"[{NAME}/{precision}] vs oracle: recompute out {worst[False][0]:.2e} grad {worst[False][1]:.2e}, cached-train out {worst[True][0]:.2e} "
+          f"grad {worst[True][1]:.2e}; cached-train vs recompute: out {d_out:.2e} grad {d_grad:.2e}")
+    b_out, b_grad = (10 * worst[False][0], 10 * worst[False][1]) if precision == "fp32" else (tol, gtol)
+    assert d_out < b_out and d_grad < b_grad, (d_out, b_out, d_grad, b_grad)
+
+
+def _predictor(D, H, layers, seed, **drop):
+    from afft_amd.models.future_prediction import BaseFuturePredictor
+    torch.manual_seed(seed)
+    drop = drop or dict(embd_pdrop=0.0, resid_pdrop=0.0, attn_pdrop=0.0)
+    return BaseFuturePredictor(D, inter_dim=D, n_layer=layers, n_head=H, output_attentions=True, **drop)
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_real_head_size_cached_train_against_recompute(precision, switch):
+    """D = 2048, H = 4 (head dimension 512), 1 layer, B = 2, T = 16, output_len = 3, loss = sum(out * w) with fixed random w: outputs, the
+    input gradient and every parameter's gradient, cached-train against recompute and both against the float64 oracle under autograd.
+    fp32: cached-train against recompute at most 10 x the recompute's own worst distance from the oracle; bf16: the mode's bars."""
+    import afft_amd
+    from afft_amd import runtime as rt
+    from oracle import afft_oracle as O
+    D, H, B, T, n_out = 2048, 4, 2, 16, 3
+    afft_amd.set_precision(precision)
+    rt.set_grad_mode("sink")
+    pred = _predictor(D, H, 1, seed=5).eval()
+    g = torch.Generator().manual_seed(6)
+    feats = torch.randn(B, T, D, generator=g)
+    w = torch.randn(B, T + n_out - 1, D, generator=g)
+    P = {k: v.double().requires_grad_(True) for k, v in pred.state_dict().items()}
+    xo = feats.double().requires_grad_(True)
+    o_ref, a_ref = O.future_predictor(P, "", xo, 1, H, n_out, True)
+    (o_ref * w.double()).sum().backward()
+    pred = pred.cuda()
+    names = [k for k, _ in pred.named_parameters()]
+    runs = {}
+    for on in (False, True):
+        switch.set_kv_cache_train(on)
+        rt.SINK.begin_step()
+        for p in pred.parameters():
+            p.grad = None
+        x = feats.cuda().requires_grad_(True)
+        with _count_steps() as n:
+            out, att = pred(x, n_out)
+            (out * w.cuda()).sum().backward()
+            rt.SINK.finish_step(list(pred.parameters()))
+        torch.cuda.synchronize()
+        assert n.fwd == n.bwd == (n_out if on else 0)
+        runs[on] = (out.detach().float().cpu(), x.grad.float().cpu(), {k: p.grad.float().cpu().clone() for k, p in pred.named_parameters()},
+                    {k: v.float().cpu() for k, v in att.items()})
+    tol, gtol = TOL[precision], GTOL[precision]
+    worst = {}
+    for on in (False, True):
+        out, dx, grads, att = runs[on]
+        e_out = rel_l2(out, o_ref.detach().float())
+        e_g = max([rel_l2(dx, xo.grad.float())] + [rel_l2(grads[k], P[k].grad.float()) for k in names])
+        assert e_out < tol and e_g < gtol, (on, e_out, e_g)
+        for k in a_ref:
+            assert att[k].shape == a_ref[k].shape and rel_l2(att[k], a_ref[k].detach().float()) < tol, (on, k)
+        worst[on] = (e_out, e_g)
+    d_out = rel_l2(runs[True][0], runs[False][0])
+    d_g = max([rel_l2(runs[True][1], runs[False][1])] + [rel_l2(runs[True][2][k], runs[False][2][k]) for k in names])
+    print(f"[real head size/{precision}] vs oracle: recompute out {worst[False][0]:.2e} grad {worst[False][1]:.2e}, cached-train out "
+          f"{worst[True][0]:.2e} grad {worst[True][1]:.2e}; cached-train vs recompute: out {d_out:.2e} grad {d_g:.2e}")
+    b_out, b_g = (10 * worst[False][0], 10 * worst[False][1]) if precision == "fp32" else (tol, gtol)
+    assert d_out < b_out and d_g < b_g, (d_out, b_out, d_g, b_g)
+
+
+def test_training_step_with_dropout_through_the_trainer(switch):
+    """training mode with the reference's drop rates, sink mode, the fused optimizer on: two steps through parallel.Trainer (the fused
+    set is learned on the first and audited on the second) -- finite loss, the audit passes, every predictor parameter changes"""
+    from afft_amd import dropout as D_
+    from afft_amd.parallel import Trainer
+    r = _reference()
+    c = r["c"]
+    dev = torch.device("cuda:0")
+    switch.set_kv_cache_train(True)
+    switch.set_fused_sgd(True)
+    D_.manual_seed(5)
+    model = _model("bf16").train()
+    drops = [m.p for m in model.future_predictor.modules() if isinstance(m, torch.nn.Dropout)]
+    assert drops and min(drops) > 0                                         # the reference's rates: dropout is live in every step
+    before = {k: p.detach().clone() for k, p in model.named_parameters() if "future_predictor" in k}
+    tr = Trainer(model, {"cls_action": 1.0, "past_cls_action": 1.0, "past_reg": 1.0}, lr=1e-2, momentum=0.9, weight_decay=1e-4,
+                 bucket_elems=1 << 15)
+    def squares(out, target, target_subclips, **kw):      # tests/helpers.py surrogate, per row: the reference's loss is undefined at fp_output_len > 1
+        rows = lambda t: t.pow(2).mean(-1).reshape(-1)   # noqa: E731
+        return {"cls_action": rows(out["logits/action"]["all-fused"]), "past_cls_action": rows(out["past_logits/action"]["all-fused"]),
+                "past_reg": rows(out["past_futures"]["all-fused"])}, None
+    tr.loss_fn = squares
+    feats = {m: d.to(dev) for m, d in r["data"].items()}
+    with _count_steps() as n:
+        for _ in range(2):
+            loss, _ = tr.step(feats, {"action": r["tgt"].to(dev)}, {"action": r["sub"].to(dev)})
+    torch.cuda.synchronize()
+    assert n.fwd == n.bwd == 2 * c["fp_layers"] * c["fp_output_len"]
+    assert torch.isfinite(torch.as_tensor(float(loss)))
+    assert tr._fused, "no weight took the fused path"
+    after = dict(model.named_parameters())
+    assert len(before) >= 12 * c["fp_layers"] + 3
+    for k, p0 in before.items():
+        assert torch.isfinite(after[k]).all() and not torch.equal(after[k].detach(), p0), k
