@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("AFFT_LIB") or os.path.join(_HERE, "lib", "libafft_hip
 globals().update({k[len("AFFT_"):]: v for k, v in _cabi.consts.items()})      # AFFT_X -> X: F32 / BF16 / F16, ACT_*, MASK_*, K_*, SGD_*, ...
 
 _NAMES = {"afft_dropout_t": "Dropout", "afft_sgd_fused_t": "SgdFused", "afft_gemm_t": "GemmDesc", "afft_attn_sublayer_t": "AttnSublayer",
-          "afft_mlp_sublayer_t": "MLPSublayer", "afft_cross_attn_sublayer_t": "CrossAttnSublayer",
+          "afft_mlp_sublayer_t": "MLPSublayer", "afft_cross_attn_sublayer_t": "CrossAttnSublayer", "afft_attn_step_sublayer_t": "AttnStepSublayer",
           "afft_gemm_trace_rec_t": "GemmTraceRec", "afft_kernel_trace_rec_t": "KernelTraceRec"}      # C struct -> its public name here
 for _c, _py in _NAMES.items():
     _cabi.structs[_c].__name__ = _cabi.structs[_c].__qualname__ = _py

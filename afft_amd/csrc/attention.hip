@@ -242,7 +242,7 @@ int run_attention(const char* who, const AttnCall& c, unsigned which, unsigned l
   const AttnPlan p = plan_attention(c);
   AFFT_CHECK(!p.refusal[0], "%s", p.refusal);
   if (p.family == kGenericShort) return launch_attention_generic(c, p, stream);
-  if (p.family == kStepVec || p.family == kStepBwdVec) return launch_attention_step(c, p, stream);
+  if (p.family == kStepVec || p.family == kStepBwdVec || p.family == kStepSplit) return launch_attention_step(c, p, stream);
   return p.family <= kSlicedBwd ? launch_attention_mfma(c, p, stream) : launch_attention_long(c, p, stream);
 }
 

@@ -11,6 +11,10 @@
 // DROP (afft_attention_step_fwd_drop with p > 0): attention-probability dropout by attention.hip's convention -- probs receives the
 // PRE-dropout probabilities, the product uses P' = P o M, M = 1 / (1 - p) for a kept element and 0 for a dropped one, decided by
 // drop_keep on the element's index in probs[nseq, H, Lq, Lk].  DROP = false is the kernel as it was, bit for bit.
+// Storage (the kernel's first template parameter): Dense<float> / Dense<bf16_t> -- every operand in one dtype, the append a copy of bits;
+// Planes (afft_attention_step_fwd_split, the "fp16x2" forward) -- q / k_new / v_new as fp16 hi planes with an optional lo plane in_lo
+// elements behind (value float(hi) + float(lo)), fp32 caches that take that value, out as fp16 hi (+ lo, out_lo elements behind:
+// hi = fp16(x), lo = fp16(x - hi)).  The arithmetic between load and store is the same code.
 // The backward (attn_step_bwd_kernel) is at the end of the file.
 #include "common.h"
 #include "attn_plan.h"
@@ -32,6 +36,7 @@ struct StepArgs {
   unsigned dthresh, dkey;      // make_drop's: threshold (0: off), key, 1 / (1 - p), the device salt
   float dinv;
   const unsigned* salt;
+  int64_t in_lo, out_lo;       // Planes: distance (elements) to the lo planes of q / k_new / v_new and of out; 0: none
 };
 
 template <typename T> struct StepElem;      // N: elements of one 16-byte access
@@ -70,9 +75,98 @@ __device__ __forceinline__ void copy_cols(T* dst, const T* src, int c, int hd) {
   }
 }
 
-template <typename T, bool V, bool DROP>
+// fp32 rows (the backward's gradient caches, the caches of Planes): x = p[c .. c + N) (V: N / 4 16-byte accesses)
+template <int N, bool V>
+__device__ __forceinline__ void ldf_cols(const float* p, int c, int hd, float (&x)[N]) {
+#pragma unroll
+  for (int e = 0; e < N; e += 4) {
+    if constexpr (V) {
+      const float4 f = *(const float4*)(p + c + e);
+      x[e] = f.x; x[e + 1] = f.y; x[e + 2] = f.z; x[e + 3] = f.w;
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) x[e + u] = c + e + u < hd ? p[c + e + u] : 0.f;
+    }
+  }
+}
+template <int N, bool V>
+__device__ __forceinline__ void stf_cols(float* p, int c, int hd, const float (&x)[N]) {
+#pragma unroll
+  for (int e = 0; e < N; e += 4) {
+    if constexpr (V) {
+      *(float4*)(p + c + e) = make_float4(x[e], x[e + 1], x[e + 2], x[e + 3]);
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (c + e + u < hd) p[c + e + u] = x[e + u];
+    }
+  }
+}
+
+
+// ---- storage of a step's rows (see the head of the file): element types, the elements N a lane takes per access, a key / value row
+// (from the cache below `past`, else from the new rows), loads to fp32, the append, the store of out
+template <typename T> struct Dense {
+  using In = T; using Cache = T; using Out = T;
+  static constexpr int N = StepElem<T>::N;
+  using Row = const T*;
+  static __device__ __forceinline__ Row row(const T* ch, int64_t ldc, const T* nh, int64_t ldn, int j, int past) {
+    return j < past ? ch + (int64_t)j * ldc : nh + (int64_t)(j - past) * ldn;
+  }
+  template <bool V> static __device__ __forceinline__ void ld_new(const T* p, int c, int hd, int64_t, float (&x)[N]) { ld_cols<T, V>(p, c, hd, x); }
+  template <bool V> static __device__ __forceinline__ void ld_row(Row r, int c, int hd, int64_t, float (&x)[N]) { ld_cols<T, V>(r, c, hd, x); }
+  template <bool V> static __device__ __forceinline__ void append(T* dst, const T* src, int c, int hd, int64_t) { copy_cols<T, V>(dst, src, c, hd); }
+  template <bool V> static __device__ __forceinline__ void st(T* p, int c, int hd, int64_t, const float (&x)[N]) { st_cols<T, V>(p, c, hd, x); }
+};
+struct Planes {
+  using In = bf16_t; using Cache = float; using Out = bf16_t;      // (fp16 bits in 16-bit words, as common.h carries them)
+  static constexpr int N = 8;
+  struct Row { const float* c; const bf16_t* n; };                  // one of the two
+  static __device__ __forceinline__ Row row(const float* ch, int64_t ldc, const bf16_t* nh, int64_t ldn, int j, int past) {
+    return j < past ? Row{ch + (int64_t)j * ldc, nullptr} : Row{nullptr, nh + (int64_t)(j - past) * ldn};
+  }
+  template <bool V> static __device__ __forceinline__ void ld_new(const bf16_t* p, int c, int hd, int64_t lo, float (&x)[N]) {
+    if constexpr (V) {
+      load8(p, c, AFFT_F16, x);
+      if (lo) {
+        float l[N];
+        load8(p, c + lo, AFFT_F16, l);
+#pragma unroll
+        for (int e = 0; e < N; ++e) x[e] += l[e];
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < N; ++e) x[e] = c + e < hd ? (lo ? h2f(p[c + e]) + h2f(p[c + e + lo]) : h2f(p[c + e])) : 0.f;
+    }
+  }
+  template <bool V> static __device__ __forceinline__ void ld_row(Row r, int c, int hd, int64_t lo, float (&x)[N]) {
+    if (r.c) ldf_cols<N, V>(r.c, c, hd, x); else ld_new<V>(r.n, c, hd, lo, x);
+  }
+  template <bool V> static __device__ __forceinline__ void append(float* dst, const bf16_t* src, int c, int hd, int64_t lo) {
+    float x[N];
+    ld_new<V>(src, c, hd, lo, x);
+    stf_cols<N, V>(dst, c, hd, x);
+  }
+  template <bool V> static __device__ __forceinline__ void st(bf16_t* p, int c, int hd, int64_t lo, const float (&x)[N]) {
+    if constexpr (V) {
+      if (lo) store_split<N>(p, c, lo, x); else store8(p, c, AFFT_F16, x);
+    } else {
+#pragma unroll
+      for (int e = 0; e < N; ++e)
+        if (c + e < hd) {
+          const bf16_t h = f2h(x[e]);
+          p[c + e] = h;
+          if (lo) p[c + e + lo] = f2h(x[e] - h2f(h));
+        }
+    }
+  }
+};
+
+template <typename IO, bool V, bool DROP>
 __global__ __launch_bounds__(256) void attn_step_kernel(const StepArgs a) {
-  constexpr int N = StepElem<T>::N, NT = 1024 / (64 * N);      // a lane owns columns (lane + 64 t) N .. + N, t < NT: hd <= 1024
+  using TI = typename IO::In;
+  using TC = typename IO::Cache;
+  constexpr int N = IO::N, NT = 1024 / (64 * N);      // a lane owns columns (lane + 64 t) N .. + N, t < NT: hd <= 1024
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const int tile = blockIdx.x % a.ntiles, sh = blockIdx.x / a.ntiles, h = sh % a.H, seq = sh / a.H;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -83,18 +177,18 @@ __global__ __launch_bounds__(256) void attn_step_kernel(const StepArgs a) {
   float* part = sc + rows * LkP;                                  // [3][rows][hdP] P V partial sums of waves 1..3
 
   const int64_t new0 = (int64_t)seq * Lq, hcol = (int64_t)h * hd;
-  const T* qh = (const T*)a.q + new0 * a.ldq + hcol;
-  const T* knh = (const T*)a.kn + new0 * a.ldk + hcol;
-  const T* vnh = (const T*)a.vn + new0 * a.ldv + hcol;
-  T* kch = (T*)a.kc + seq * a.cseq + hcol;
-  T* vch = (T*)a.vc + seq * a.cseq + hcol;
+  const TI* qh = (const TI*)a.q + new0 * a.ldq + hcol;
+  const TI* knh = (const TI*)a.kn + new0 * a.ldk + hcol;
+  const TI* vnh = (const TI*)a.vn + new0 * a.ldv + hcol;
+  TC* kch = (TC*)a.kc + seq * a.cseq + hcol;
+  TC* vch = (TC*)a.vc + seq * a.cseq + hcol;
 
   // the append: rows past + i of both caches become rows i of k_new / v_new (i < Lq, so past + i < Lk <= cap)
   const int nv = (hd + N - 1) / N;
   for (int idx = tid; idx < nr * nv; idx += 256) {
     const int i = i0 + idx / nv, c = (idx % nv) * N;
-    copy_cols<T, V>(kch + (int64_t)(past + i) * a.ldc, knh + (int64_t)i * a.ldk, c, hd);
-    copy_cols<T, V>(vch + (int64_t)(past + i) * a.ldc, vnh + (int64_t)i * a.ldv, c, hd);
+    IO::template append<V>(kch + (int64_t)(past + i) * a.ldc, knh + (int64_t)i * a.ldk, c, hd, a.in_lo);
+    IO::template append<V>(vch + (int64_t)(past + i) * a.ldc, vnh + (int64_t)i * a.ldv, c, hd, a.in_lo);
   }
 
   // scores: a wave takes (row, 4 keys) at a time -- the row in registers, the 4 x NT loads of the keys independent of each other
@@ -107,7 +201,7 @@ __global__ __launch_bounds__(256) void attn_step_kernel(const StepArgs a) {
     for (int t = 0; t < NT; ++t) {
       const int c = (lane + 64 * t) * N;
       if (c < hd) {
-        ld_cols<T, V>(qh + (int64_t)i * a.ldq, c, hd, qv[t]);
+        IO::template ld_new<V>(qh + (int64_t)i * a.ldq, c, hd, a.in_lo, qv[t]);
       } else {
 #pragma unroll
         for (int e = 0; e < N; ++e) qv[t][e] = 0.f;
@@ -118,13 +212,13 @@ __global__ __launch_bounds__(256) void attn_step_kernel(const StepArgs a) {
     for (int u = 0; u < 4; ++u) {
       const int j = j0 + u;
       if (j <= last) {
-        const T* kr = j < past ? kch + (int64_t)j * a.ldc : knh + (int64_t)(j - past) * a.ldk;
+        const typename IO::Row kr = IO::row(kch, a.ldc, knh, a.ldk, j, past);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
           const int c = (lane + 64 * t) * N;
           if (c < hd) {
             float kx[N];
-            ld_cols<T, V>(kr, c, hd, kx);
+            IO::template ld_row<V>(kr, c, hd, a.in_lo, kx);
 #pragma unroll
             for (int e = 0; e < N; ++e) acc[u] += qv[t][e] * kx[e];
           }
@@ -185,7 +279,7 @@ __global__ __launch_bounds__(256) void attn_step_kernel(const StepArgs a) {
   const int jend = past + i0 + nr;      // the keys the tile's last row sees
 #pragma unroll 2
   for (int j = wave; j < jend; j += 4) {
-    const T* vr = j < past ? vch + (int64_t)j * a.ldc : vnh + (int64_t)(j - past) * a.ldv;
+    const typename IO::Row vr = IO::row(vch, a.ldc, vnh, a.ldv, j, past);
     float pj[STEP_QT];
 #pragma unroll
     for (int r = 0; r < STEP_QT; ++r) pj[r] = r < nr ? sc[r * LkP + j] : 0.f;
@@ -194,7 +288,7 @@ __global__ __launch_bounds__(256) void attn_step_kernel(const StepArgs a) {
       const int c = (lane + 64 * t) * N;
       if (c < hd) {
         float vx[N];
-        ld_cols<T, V>(vr, c, hd, vx);
+        IO::template ld_row<V>(vr, c, hd, a.in_lo, vx);
 #pragma unroll
         for (int r = 0; r < STEP_QT; ++r)
 #pragma unroll
@@ -228,15 +322,15 @@ __global__ __launch_bounds__(256) void attn_step_kernel(const StepArgs a) {
 #pragma unroll
             for (int e = 0; e < N; ++e) acc[r][t][e] += src[e];
           }
-          st_cols<T, V>((T*)a.out + (new0 + i0 + r) * a.ldo + hcol, c, hd, acc[r][t]);
+          IO::template st<V>((typename IO::Out*)a.out + (new0 + i0 + r) * a.ldo + hcol, c, hd, a.out_lo, acc[r][t]);
         }
       }
   }
 }
 
-template <typename T, bool V, bool DROP>
+template <typename IO, bool V, bool DROP>
 int launch_step(const StepArgs& a, const AttnPlan& p, hipStream_t stream) {
-  auto kern = attn_step_kernel<T, V, DROP>;
+  auto kern = attn_step_kernel<IO, V, DROP>;
   static std::atomic<uint64_t> attr{0};
   if (p.lds > 48 * 1024)
     if (int rc = afft_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), p.lds, &attr)) return rc;
@@ -266,34 +360,6 @@ struct StepBwdArgs {
   float dinv;
   const unsigned* salt;
 };
-
-// fp32 rows of the gradient caches: x = p[c .. c + N) (V: N / 4 16-byte accesses)
-template <int N, bool V>
-__device__ __forceinline__ void ldf_cols(const float* p, int c, int hd, float (&x)[N]) {
-#pragma unroll
-  for (int e = 0; e < N; e += 4) {
-    if constexpr (V) {
-      const float4 f = *(const float4*)(p + c + e);
-      x[e] = f.x; x[e + 1] = f.y; x[e + 2] = f.z; x[e + 3] = f.w;
-    } else {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) x[e + u] = c + e + u < hd ? p[c + e + u] : 0.f;
-    }
-  }
-}
-template <int N, bool V>
-__device__ __forceinline__ void stf_cols(float* p, int c, int hd, const float (&x)[N]) {
-#pragma unroll
-  for (int e = 0; e < N; e += 4) {
-    if constexpr (V) {
-      *(float4*)(p + c + e) = make_float4(x[e], x[e + 1], x[e + 2], x[e + 3]);
-    } else {
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (c + e + u < hd) p[c + e + u] = x[e + u];
-    }
-  }
-}
 
 template <typename T, bool V>
 __global__ __launch_bounds__(256) void attn_step_bwd_kernel(const StepBwdArgs a) {
@@ -523,7 +589,7 @@ int launch_step_bwd(const StepBwdArgs& a, const AttnPlan& p, hipStream_t stream)
 
 template <typename T, bool V>
 int launch_step_fwd(const StepArgs& a, const AttnPlan& p, hipStream_t stream) {
-  return p.p1 ? launch_step<T, V, true>(a, p, stream) : launch_step<T, V, false>(a, p, stream);
+  return p.p1 ? launch_step<Dense<T>, V, true>(a, p, stream) : launch_step<Dense<T>, V, false>(a, p, stream);
 }
 
 }  // namespace
@@ -541,8 +607,9 @@ int launch_attention_step(const AttnCall& c, const AttnPlan& p, hipStream_t stre
              : (p.p0 ? launch_step_bwd<bf16_t, true>(a, p, stream) : launch_step_bwd<bf16_t, false>(a, p, stream));
   } else {
     const StepArgs a = {c.q, c.k, c.v, c.ldq, c.ldk, c.ldv, c.k_cache, c.v_cache, c.ldc, c.cache_seq, c.out, c.ldo, c.probs,
-                        c.Lq, c.L, c.H, c.hd, p.ntiles, p.Lp, c.scale, dp.thresh, dp.key, dp.inv_keep, dp.salt};
-    rc = f32 ? (p.p0 ? launch_step_fwd<float, true>(a, p, stream) : launch_step_fwd<float, false>(a, p, stream))
+                        c.Lq, c.L, c.H, c.hd, p.ntiles, p.Lp, c.scale, dp.thresh, dp.key, dp.inv_keep, dp.salt, c.in_lo, c.out_lo};
+    rc = p.family == kStepSplit ? (p.p0 ? launch_step<Planes, true, false>(a, p, stream) : launch_step<Planes, false, false>(a, p, stream))
+       : f32 ? (p.p0 ? launch_step_fwd<float, true>(a, p, stream) : launch_step_fwd<float, false>(a, p, stream))
              : (p.p0 ? launch_step_fwd<bf16_t, true>(a, p, stream) : launch_step_fwd<bf16_t, false>(a, p, stream));
   }
   if (rc) return rc;
@@ -588,4 +655,28 @@ extern "C" int afft_attention_step_bwd(const void* dout, int64_t lddo, const voi
   const AttnCall c = attn_step_bwd_call(dout, lddo, q, ldq, k_cache, v_cache, ldc, cache_seq, dtype, probs, nseq, Lq, Lk, cap, H, hd, scale,
                                         drop_p, drop_key, dq, lddq, dk_new, lddk, dv_new, lddv, gk_cache, gv_cache, ldg, grad_seq);
   return run_attention("attention_step_bwd", c, kChkPtrs | kLenAll | kChkDrop | kChkBatch | kChkHd | kChkDtype | kChkStep, 0, (hipStream_t)stream_);
+}
+
+// the plan of the fp16x2 step as afft_attention_step_plan_for describes a problem; in_lo / out_lo: are there lo planes (their offset does
+// not change the kernel, only whether 16-byte accesses reach them, which pitch_alignment_ok states)
+extern "C" int afft_attention_step_split_plan_for(int32_t Lq, int32_t Lk, int32_t hd, int32_t in_lo, int32_t out_lo, int32_t pitch_alignment_ok,
+                                                  int64_t* lds_and_tiles) {
+  const int64_t ld = (hd + 7) / 8 * 8 + (pitch_alignment_ok ? 0 : 1);
+  void* x = reinterpret_cast<void*>(uintptr_t{4096});      // never dereferenced
+  const int64_t plane = ld * (Lq > 0 ? Lq : 1);
+  const AttnCall c = attn_step_split_call(x, ld, x, ld, x, ld, in_lo ? plane : 0, (float*)x, (float*)x, ld, ld * (Lk > 0 ? Lk : 1), 1, Lq, Lk, Lk, 1,
+                                          hd, 1.f, x, ld, out_lo ? plane : 0, nullptr);
+  const AttnPlan p = plan_attention(c);
+  if (!p.family) { afft_set_error("%s", p.refusal); return -1; }
+  if (lds_and_tiles) { lds_and_tiles[0] = (int64_t)p.lds; lds_and_tiles[1] = p.ntiles; }
+  return p.family * 10000 + p.p0 * 10 + p.p1;
+}
+
+extern "C" int afft_attention_step_fwd_split(const void* q, int64_t ldq, const void* k_new, int64_t ldk, const void* v_new, int64_t ldv,
+                                             int64_t in_lo, float* k_cache, float* v_cache, int64_t ldc, int64_t cache_seq, int32_t nseq,
+                                             int32_t Lq, int32_t Lk, int32_t cap, int32_t H, int32_t hd, float scale, void* out_hi,
+                                             int64_t ldo, int64_t out_lo, float* probs, void* stream_) {
+  const AttnCall c = attn_step_split_call(q, ldq, k_new, ldk, v_new, ldv, in_lo, k_cache, v_cache, ldc, cache_seq, nseq, Lq, Lk, cap, H, hd, scale,
+                                          out_hi, ldo, out_lo, probs);
+  return run_attention("attention_step_split", c, kChkPtrs | kLenAll | kChkBatch | kChkHd | kChkStep | kChkStepPlanes, 0, (hipStream_t)stream_);
 }

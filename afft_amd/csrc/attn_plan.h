@@ -1,7 +1,7 @@
 // The dispatch plan of attention: what an entry point was asked (AttnCall), whether the arguments are acceptable (check_attention),
 // which kernel instantiation runs it with which launch geometry (plan_attention), and what the kernel trace records (attention_traffic).
 // Pure host arithmetic over shapes, pitches and pointer alignments -- no HIP runtime call, no global state but the one cached read of
-// AFFT_ATTN_GENERIC (compiles with the plain host compiler) -- and the ONE place that decides: the twelve entry points (attention.hip,
+// AFFT_ATTN_GENERIC (compiles with the plain host compiler) -- and the ONE place that decides: the thirteen entry points (attention.hip,
 // attention_long.hip, attention_step.hip) check, plan, open the trace scope and hand the plan to the launcher of the family's file, which only maps it to
 // a template instantiation; afft_attention_plan_for reports it.
 #pragma once
@@ -42,7 +42,7 @@ struct AttnCall {
   uint32_t drop_key;
   const float* bias;                   // additive fp32 bias or null: element (seq, h, i, j) at bias[seq*sb + h*sh + i*si + j]
   int64_t sb, sh, si;
-  int planes;                          // fp16x2 forward (afft_attention_fwd_split): q / k / v / out are hi planes
+  int planes;                          // fp16x2 forward (afft_attention_fwd_split, afft_attention_step_fwd_split): q / k / v / out are hi planes
   int64_t in_lo, out_lo;
   void* out_b;
   int64_t ldob;
@@ -88,6 +88,15 @@ inline AttnCall attn_step_call(const void* q, int64_t ldq, const void* k_new, in
   c.k_cache = k_cache; c.v_cache = v_cache; c.ldc = ldc; c.cache_seq = cache_seq; c.Lq = Lq; c.cap = cap;
   return c;
 }
+// the step of the "fp16x2" forward (afft_attention_step_fwd_split): q / k_new / v_new / out are fp16 hi planes, the caches fp32
+inline AttnCall attn_step_split_call(const void* q, int64_t ldq, const void* k_new, int64_t ldk, const void* v_new, int64_t ldv, int64_t in_lo,
+                                     float* k_cache, float* v_cache, int64_t ldc, int64_t cache_seq, int nseq, int Lq, int Lk, int cap, int H,
+                                     int hd, float scale, void* out_hi, int64_t ldo, int64_t out_lo, float* probs) {
+  AttnCall c = attn_step_call(q, ldq, k_new, ldk, v_new, ldv, k_cache, v_cache, ldc, cache_seq, AFFT_F16, nseq, Lq, Lk, cap, H, hd, scale, out_hi,
+                              ldo, probs);
+  c.planes = 1; c.in_lo = in_lo; c.out_lo = out_lo;
+  return c;
+}
 inline AttnCall attn_step_bwd_call(const void* dout, int64_t lddo, const void* q, int64_t ldq, const void* k_cache, const void* v_cache,
                                    int64_t ldc, int64_t cache_seq, int dtype, const float* probs, int nseq, int Lq, int Lk, int cap, int H,
                                    int hd, float scale, float drop_p, uint32_t drop_key, void* dq, int64_t lddq, void* dk_new, int64_t lddk,
@@ -120,6 +129,7 @@ enum : unsigned {
   kChkScratch = 1u << 11,   // a bias gradient that sums needs scratch
   kLenShort = 1u << 12, kLenSplit = 1u << 13, kLenLong = 1u << 14, kLenAll = 1u << 15,      // the entry point's length band
   kChkStep = 1u << 16,      // the cached step: new rows, keys and capacity in order, pitches that hold a row and a sequence's rows
+  kChkStepPlanes = 1u << 17,   // its fp16x2 form: lo planes behind their hi planes, alignment of the element types
 };
 
 #define AFFT_ATTN_CHECK(cond, ...) \
@@ -172,6 +182,20 @@ inline int check_attention(const char* who, const AttnCall& c, unsigned which) {
                       "%s: the gradient caches and probs must be 4-byte aligned", who);
     }
   }
+  if (which & kChkStepPlanes) {      // a lo plane starts behind the last element of its hi plane: an offset inside the hi plane would make
+    // two lanes write one address (out) or read a value as its own correction (in); 0 = no lo plane
+    const int64_t w = (int64_t)c.H * c.hd, rows = (int64_t)c.nseq * c.Lq;
+    const int64_t ldin = c.ldq > c.ldk ? (c.ldq > c.ldv ? c.ldq : c.ldv) : (c.ldk > c.ldv ? c.ldk : c.ldv);
+    AFFT_ATTN_CHECK(c.in_lo == 0 || (rows > 0 && c.in_lo >= (rows - 1) * ldin + w),
+                    "%s: in_lo %lld lies inside the hi plane (0: no lo plane, else at least (nseq * Lq - 1) * pitch + H * hd = %lld)", who,
+                    (long long)c.in_lo, (long long)((rows - 1) * ldin + w));
+    AFFT_ATTN_CHECK(c.out_lo == 0 || (rows > 0 && c.out_lo >= (rows - 1) * c.ldo + w),
+                    "%s: out_lo %lld lies inside the hi plane (0: no lo plane, else at least (nseq * Lq - 1) * pitch + H * hd = %lld)", who,
+                    (long long)c.out_lo, (long long)((rows - 1) * c.ldo + w));
+    AFFT_ATTN_CHECK(((((uintptr_t)c.q) | ((uintptr_t)c.k) | ((uintptr_t)c.v) | ((uintptr_t)c.out)) & 1) == 0 &&
+                    ((((uintptr_t)c.k_cache) | ((uintptr_t)c.v_cache) | ((uintptr_t)c.probs)) & 3) == 0,
+                    "%s: fp16 planes must be 2-byte aligned, the fp32 caches and probs 4-byte aligned", who);
+  }
   if (which & kChkBiasArgs) {
     const bool grad = c.dir == kBiasBwd;
     const int64_t sb = grad ? c.dsb : c.sb, sh = grad ? c.dsh : c.sh, si = grad ? c.dsi : c.si;
@@ -192,6 +216,11 @@ struct AttnTraffic { int64_t bytes, flops; };
 inline AttnTraffic attention_traffic(const AttnCall& c) {
   const int64_t es = c.dtype == AFFT_F32 ? 4 : 2, rw = (int64_t)c.nseq * c.L * c.H * c.hd, pb = (int64_t)c.nseq * c.H * c.L * c.L * 4;
   const int64_t product = 2 * (int64_t)c.nseq * c.H * c.L * c.L * c.hd;      // one L x L x hd product
+  if (c.dir == kStep && c.planes) {      // the same with fp16 planes in and out (2 bytes each, those that are there) and fp32 caches
+    const int64_t row = (int64_t)c.nseq * c.H * c.hd, past = c.L - c.Lq;
+    return {row * (c.Lq * (3 * (c.in_lo ? 4 : 2) + 8 + (c.out_lo ? 4 : 2)) + 8 * past) + (c.probs ? (int64_t)c.nseq * c.H * c.Lq * c.L * 4 : 0),
+            4 * (int64_t)c.nseq * c.H * c.Lq * c.L * c.hd};
+  }
   if (c.dir == kStep) {      // q, k_new, v_new read, both appended, the past read, out and probs written
     const int64_t row = es * c.nseq * c.H * c.hd, past = c.L - c.Lq;
     return {row * (6 * c.Lq + 2 * past) + (c.probs ? (int64_t)c.nseq * c.H * c.Lq * c.L * 4 : 0), 4 * (int64_t)c.nseq * c.H * c.Lq * c.L * c.hd};
@@ -219,6 +248,7 @@ enum AttnFamily {
   kBiasF32 = 8, kBiasBf16 = 9, kBiasMfma = 10,     //                    bias_bwd_ds_kernel (+ bias_bwd_reduce_kernel)
   kStepVec = 11,            // attention_step.hip attn_step_kernel<T, V = p0, DROP = p1>: p0 = 1, 16-byte loads; 0, element loads
   kStepBwdVec = 12,         //                    attn_step_bwd_kernel<T, V = p0>
+  kStepSplit = 13,          //                    attn_step_kernel<Planes, V = p0, false>: fp16 planes in and out, fp32 caches; p0 as family 11
 };
 
 struct AttnPlan {
@@ -292,7 +322,8 @@ inline bool plan_short_mfma(const AttnCall& c, AttnPlan& p) {
 inline AttnPlan plan_attention_step(const AttnCall& c) {
   AttnPlan p = {};
   const bool f32 = c.dtype == AFFT_F32;
-  if (c.Lq < 1 || c.Lq > c.L || c.L > LHI || c.hd < 1 || c.hd > 1024 || (!f32 && c.dtype != AFFT_BF16)) {
+  const bool planes = c.planes && c.dir == kStep;      // afft_attention_step_fwd_split
+  if (c.Lq < 1 || c.Lq > c.L || c.L > LHI || c.hd < 1 || c.hd > 1024 || (!planes && !f32 && c.dtype != AFFT_BF16) || (c.planes && !planes)) {
     snprintf(p.refusal, sizeof p.refusal, "attention_step: no kernel for Lq = %d, Lk = %d, head dimension %d, dtype %d", c.Lq, c.L, c.hd, c.dtype);
     return p;
   }
@@ -309,6 +340,14 @@ inline AttnPlan plan_attention_step(const AttnCall& c) {
            al16(c.dv) && al16(c.gk_cache) && al16(c.gv_cache);
     p.lds += sizeof(float) * (size_t)c.Lq;
     p.grid = (unsigned)((int64_t)c.nseq * c.H);
+    return p;
+  }
+  if (planes) {      // 8 elements a lane: one 16-byte load of an fp16 plane, two of an fp32 cache row (head columns start at a multiple of hd)
+    const bool pitches = c.ldq % 8 == 0 && c.ldk % 8 == 0 && c.ldv % 8 == 0 && c.ldo % 8 == 0 && c.in_lo % 8 == 0 && c.out_lo % 8 == 0 &&
+                         c.ldc % 4 == 0 && c.cache_seq % 4 == 0;
+    p.family = kStepSplit;
+    p.p0 = c.hd % 8 == 0 && pitches && al16(c.q) && al16(c.k) && al16(c.v) && al16(c.k_cache) && al16(c.v_cache) && al16(c.out);
+    p.grid = (unsigned)((int64_t)c.nseq * c.H * p.ntiles);
     return p;
   }
   const bool pitches = c.ldq % vec == 0 && c.ldk % vec == 0 && c.ldv % vec == 0 && c.ldc % vec == 0 && c.cache_seq % vec == 0 && c.ldo % vec == 0;

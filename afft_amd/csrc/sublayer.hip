@@ -176,6 +176,40 @@ extern "C" int afft_attn_sublayer_fwd(const afft_attn_sublayer_t* s, void* strea
   return afft_gemm(&g, st);
 }
 
+// the attention half of one cached step, "fp16x2" form: the f16x2 branch above with the attention core replaced by the step kernel
+extern "C" int afft_attn_step_sublayer_fwd(const afft_attn_step_sublayer_t* s, void* stream_) {
+  hipStream_t st = (hipStream_t)stream_;
+  AFFT_CHECK(s && s->x && s->w_qkv && s->w_proj && s->xn && s->qkv && s->ao && s->k_cache && s->v_cache && s->y, "attn_step_sublayer_fwd: null pointer");
+  AFFT_CHECK(s->rows > 0 && s->Lq > 0 && s->rows % s->Lq == 0 && s->H > 0 && s->d > 0 && s->d % 64 == 0 && s->d % s->H == 0,
+             "attn_step_sublayer_fwd: bad geometry (rows %d, Lq %d, d %d, H %d)", s->rows, s->Lq, s->d, s->H);
+  AFFT_CHECK((s->f16x2 & 3) == 1, "attn_step_sublayer_fwd: f16x2 must be 1 | AFFT_F16X2_ONE_PASS_* (fp16 lo planes; no e4m3 form)");
+  const int R = s->rows, d = s->d, pr = pad64(R);
+  const int64_t lo1 = (int64_t)pr * d, lo3 = (int64_t)pr * 3 * d;
+  const bool one1 = s->f16x2 & AFFT_F16X2_ONE_PASS_1, one2 = s->f16x2 & AFFT_F16X2_ONE_PASS_2, one_attn = s->f16x2 & AFFT_F16X2_ONE_PASS_ATTN;
+  const Ws ws = main_ws(s);
+  bf16_t *xn = (bf16_t*)s->xn, *qkv = (bf16_t*)s->qkv, *ao = (bf16_t*)s->ao;
+  TRY(zero_row_tail(xn, R, d, st));
+  if (!one1) TRY(zero_row_tail(xn + lo1, R, d, st));
+  TRY(zero_row_tail(qkv, R, 3 * d, st));
+  if (!one_attn) TRY(zero_row_tail(qkv + lo3, R, 3 * d, st));
+  TRY(zero_row_tail(ao, R, d, st));
+  if (!one2) TRY(zero_row_tail(ao + lo1, R, d, st));
+  TRY(afft_layernorm_fwd_split(s->x, d, s->ln_w, s->ln_b, s->eps, R, d, xn, d, one1 ? 0 : lo1, nullptr, 0, nullptr, nullptr, nullptr, st));
+  afft_gemm_t g = lin_fwd(xn, d, R, d, s->w_qkv, s->ldw_qkv, 3 * d, s->conv1d, ws);
+  if (one1) as_f16_one(g); else as_f16x2(g, lo1);
+  g.bias = s->b_qkv;
+  g.out = qkv; g.ldo = 3 * d; g.out_dtype = AFFT_F16; g.out_lo = one_attn ? 0 : lo3;
+  TRY(afft_gemm(&g, st));
+  TRY(afft_attention_step_fwd_split(qkv, 3 * d, qkv + d, 3 * d, qkv + 2 * d, 3 * d, one_attn ? 0 : lo3, s->k_cache, s->v_cache, s->ldc, s->cache_seq,
+                                    R / s->Lq, s->Lq, s->Lk, s->cap, s->H, d / s->H, s->scale, ao, d, one2 ? 0 : lo1, s->probs, st));
+  g = lin_fwd(ao, d, R, d, s->w_proj, s->ldw_proj, d, s->conv1d, ws);
+  if (one2) as_f16_one(g); else as_f16x2(g, lo1);
+  g.bias = s->b_proj;
+  g.residual = s->x; g.ldres = d;
+  g.out = s->y; g.ldo = d; g.out_dtype = AFFT_F32;
+  return afft_gemm(&g, st);
+}
+
 extern "C" int afft_attn_sublayer_bwd(const afft_attn_sublayer_t* s, void* stream_, void* aux_) {
   hipStream_t st = (hipStream_t)stream_, aux = aux_ ? (hipStream_t)aux_ : st;
   AFFT_CHECK(s && s->x && s->dy && s->dya && s->dao && s->dqkv && s->dxn && s->dx && s->ln_partial && s->xn && s->qkv && s->ao &&

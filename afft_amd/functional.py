@@ -1260,6 +1260,53 @@ def mlp_step(x: Tensor, ln_w, ln_b, w1, b1, w2, b2, eps: float, gelu: str, conv1
     return _cbc_out(x, h, w2, conv1d, b2, True, None, w2.shape[1] if conv1d else w2.shape[0])
 
 
+def _step_composite_ok(x: Tensor, *widths: int) -> bool:
+    """the 'fp16x2' step goes through the composite calls where the sub-layer Functions would (_composite_ok without the precision, which
+    the caller has looked at); otherwise through the call-by-call step above, whose GEMMs then run every site in two passes"""
+    return rt.composite() and x.is_contiguous() and all(w % 64 == 0 for w in widths)      # (one row per call: any stride(0) is dense)
+
+
+def attn_step_f16x2(x: Tensor, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, Lq: int, H: int, eps: float, conv1d: bool, k_cache: Tensor,
+                    v_cache: Tensor, past: int, want_probs: bool) -> Tuple[Tensor, Optional[Tensor]]:
+    """attn_step in the 'fp16x2' precision: ONE composite call (ops.attn_step_sublayer_f16x2 -> afft_attn_step_sublayer_fwd) with the
+    one-pass flags the sub-layer Functions give the same sites (runtime.one_pass_flags; Conv1D weights: never the fp8 lo pass), the FP16
+    weight images, and fp16 scratch with room for a lo plane only where one is written: xn | qkv | ao in one allocation"""
+    R, d = x.shape
+    if not (conv1d and _step_composite_ok(x, d)):
+        return attn_step(x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, Lq, H, eps, conv1d, k_cache, v_cache, past, want_probs)
+    nseq, hd, Lk, pr = R // Lq, d // H, past + Lq, rt.pad64(R)
+    flags = 1 | rt.one_pass_flags(True, d, "qkv", "proj", "attn")
+    n_xn = pr * d * (1 if flags & L_.F16X2_ONE_PASS_1 else 2)
+    n_qkv = pr * 3 * d * (1 if flags & L_.F16X2_ONE_PASS_ATTN else 2)
+    n_ao = pr * d * (1 if flags & L_.F16X2_ONE_PASS_2 else 2)
+    planes = torch.empty(n_xn + n_qkv + n_ao, dtype=torch.float16, device=x.device)
+    probs = torch.empty(nseq, H, Lq, Lk, dtype=torch.float32, device=x.device) if want_probs else None
+    y = torch.empty(R, d, dtype=torch.float32, device=x.device)
+    ops.attn_step_sublayer_f16x2(x, ln_w, ln_b, rt.weight_f16(w_qkv), b_qkv, rt.weight_f16(w_proj), b_proj, flags, Lq, Lk, H, eps,
+                                 float(hd) ** -0.5, planes[:n_xn], planes[n_xn:n_xn + n_qkv], planes[n_xn + n_qkv:], k_cache, v_cache, probs, y)
+    _note_output(y, None, b_proj)
+    return y, probs
+
+
+def mlp_step_f16x2(x: Tensor, ln_w, ln_b, w1, b1, w2, b2, eps: float, gelu: str, conv1d: bool) -> Tensor:
+    """mlp_step in the 'fp16x2' precision: the composite MLP forward (afft_mlp_sublayer_fwd) with nothing saved"""
+    R, d = x.shape
+    hidden = w1.shape[1] if conv1d else w1.shape[0]
+    if not (conv1d and w2.shape[1] == d and _step_composite_ok(x, d, hidden)):
+        return mlp_step(x, ln_w, ln_b, w1, b1, w2, b2, eps, gelu, conv1d)
+    pr = rt.pad64(R)
+    flags = 1 | rt.one_pass_flags(True, d, "fc1", "fc2")
+    n_xn = pr * d * (1 if flags & L_.F16X2_ONE_PASS_1 else 2)
+    n_h = pr * hidden * (1 if flags & L_.F16X2_ONE_PASS_2 else 2)
+    planes = torch.empty(n_xn + n_h, dtype=torch.float16, device=x.device)
+    stats = torch.empty(2, R, dtype=torch.float32, device=x.device)
+    y = torch.empty(R, d, dtype=torch.float32, device=x.device)
+    ops.mlp_step_sublayer_f16x2(x, ln_w, ln_b, rt.weight_f16(w1), b1, rt.weight_f16(w2), b2, flags, _GELU[gelu][0], eps, planes[:n_xn],
+                                planes[n_xn:], stats, y)
+    _note_output(y, None, b2)
+    return y
+
+
 # --------------------------------------------------------------------------- cached roll-out with a backward pass
 _ATTN_STEP_NARGS = 18      # AttnStepSublayer.forward
 

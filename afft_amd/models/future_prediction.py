@@ -84,8 +84,15 @@ class GPT2Block(nn.Module):
         return h, probs
 
     def forward_step(self, h: Tensor, Lq: int, k_cache: Tensor, v_cache: Tensor, past: int, want_attn: bool):
-        """the block on the Lq new rows per clip at positions past .. past + Lq - 1 (inference: F_.attn_step / F_.mlp_step)"""
+        """the block on the Lq new rows per clip at positions past .. past + Lq - 1 (inference: F_.attn_step / F_.mlp_step; in the
+        'fp16x2' precision their composite forms F_.attn_step_f16x2 / F_.mlp_step_f16x2)"""
         a, m = self.attn, self.mlp
+        if rt.precision() == "fp16x2":
+            h, probs = F_.attn_step_f16x2(h, self.ln_1.weight, self.ln_1.bias, a.c_attn.weight, a.c_attn.bias, a.c_proj.weight, a.c_proj.bias,
+                                          Lq, a.num_heads, self.ln_1.eps, True, k_cache, v_cache, past, want_attn)
+            h = F_.mlp_step_f16x2(h, self.ln_2.weight, self.ln_2.bias, m.c_fc.weight, m.c_fc.bias, m.c_proj.weight, m.c_proj.bias,
+                                  self.ln_2.eps, "tanh", True)
+            return h, probs
         h, probs = F_.attn_step(h, self.ln_1.weight, self.ln_1.bias, a.c_attn.weight, a.c_attn.bias, a.c_proj.weight, a.c_proj.bias,
                                 Lq, a.num_heads, self.ln_1.eps, True, k_cache, v_cache, past, want_attn)
         h = F_.mlp_step(h, self.ln_2.weight, self.ln_2.bias, m.c_fc.weight, m.c_fc.bias, m.c_proj.weight, m.c_proj.bias, self.ln_2.eps,
@@ -208,8 +215,9 @@ class BaseFuturePredictor(nn.Module):
         """feats (B, T, C) -> (B, T + output_len - 1, C), {gpt2_att_i: (B, layers, heads, T, T) for i = 0, (B, layers, heads, 1, T + i) after}.
 
         output_len > 1: the reference rolls out with HF's KV cache, feeding the last hidden state back as the next input embedding at the
-        next position (future_prediction.py:395-412).  In evaluation (eval mode, no grad, runtime.kv_cache(); every precision but 'fp16x2',
-        whose one-pass GEMM sites exist on the composite sub-layer calls only) this does the same: the T
+        next position (future_prediction.py:395-412).  In evaluation (eval mode, no grad, runtime.kv_cache(); the 'fp16x2' precision
+        only with runtime.kv_cache_fp16x2(), off by default: its step is a composite call of its own, which knows that precision's
+        one-pass GEMM sites) this does the same: the T
         observed frames run once through GPT2Model.forward_step, which leaves every layer's keys and values in a KVCache, and every
         further frame is ONE new row per clip attending to the cache (afft_attention_step_fwd).  With grad enabled, in training mode or
         with AFFT_KV_CACHE=0 the roll-out re-runs the extended sequence for every predicted frame and keeps its last row -- a causal
@@ -220,7 +228,8 @@ class BaseFuturePredictor(nn.Module):
         feats = self._map(self.encoder, feats)
         B, T, D = feats.shape
         seq = feats if feats.dtype == torch.float32 else feats.float()
-        if output_len > 1 and rt.kv_cache() and not torch.is_grad_enabled() and not self.training and rt.precision() != "fp16x2":
+        if output_len > 1 and rt.kv_cache() and not torch.is_grad_enabled() and not self.training and (
+                rt.precision() != "fp16x2" or rt.kv_cache_fp16x2()):
             return self._rollout_cached(seq, output_len, addl_endpoints)
         if (output_len > 1 and rt.kv_cache() and rt.kv_cache_train() and (torch.is_grad_enabled() or self.training)
                 and rt.precision() in ("bf16", "fp32", "bf16x3")):

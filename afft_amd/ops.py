@@ -424,6 +424,98 @@ def attention_step(q: Tensor, k_new: Tensor, v_new: Tensor, k_cache: Tensor, v_c
     return out
 
 
+def attention_step_split(q: Tensor, k_new: Tensor, v_new: Tensor, in_lo: int, k_cache: Tensor, v_cache: Tensor, nseq: int, Lq: int, Lk: int,
+                         H: int, hd: int, scale: float, out_hi: Tensor, out_lo: int, probs: Optional[Tensor]) -> Tensor:
+    """attention_step in the operand form of the 'fp16x2' forward (afft_attention_step_fwd_split): q / k_new / v_new / out_hi are fp16 hi
+    planes [nseq * Lq, H * hd] (views with a row pitch), their lo planes in_lo / out_lo elements behind (0: none); the caches are fp32 and
+    take float(hi) + float(lo) of the new keys and values"""
+    assert q.dtype == k_new.dtype == v_new.dtype == out_hi.dtype == torch.float16 and k_cache.dtype == v_cache.dtype == torch.float32
+    assert q.shape == k_new.shape == v_new.shape == out_hi.shape == (nseq * Lq, H * hd) and in_lo >= 0 and out_lo >= 0
+    _cache_pair(k_cache, v_cache, nseq, H * hd, "caches")
+    if probs is not None:
+        assert probs.dtype == torch.float32 and probs.is_contiguous() and probs.numel() == nseq * H * Lq * Lk
+    L.check(L.lib().afft_attention_step_fwd_split(_p(q), _rowmajor(q, "q"), _p(k_new), _rowmajor(k_new, "k_new"), _p(v_new),
+                                                  _rowmajor(v_new, "v_new"), int(in_lo), _p(k_cache), _p(v_cache), k_cache.stride(1),
+                                                  k_cache.stride(0), nseq, Lq, Lk, k_cache.shape[1], H, hd, scale, _p(out_hi),
+                                                  _rowmajor(out_hi, "out_hi"), int(out_lo), _p(probs), _stream()), "attention_step_split")
+    return out_hi
+
+
+def _planes(buf: Tensor, rows: int, width: int, lo: bool, what: str):
+    """an fp16 scratch buffer of a composite 'fp16x2' call: room for the hi plane [pad64(rows), width] and, with `lo`, the lo plane behind it"""
+    need = (rows + 63) // 64 * 64 * width * (2 if lo else 1)
+    if buf.dtype != torch.float16 or not buf.is_contiguous() or buf.numel() < need:
+        raise ValueError(f"afft_amd: {what} must be a contiguous float16 buffer of at least {need} elements, got {buf.dtype} {tuple(buf.shape)}")
+
+
+def _image(w: Tensor, k: int, n: int, what: str):
+    if w.dtype != torch.float16 or w.dim() != 2 or w.stride(1) != 1 or w.shape[0] < k or w.shape[1] < n:
+        raise ValueError(f"afft_amd: {what} must be the FP16 image of a Conv1D weight [{k}, {n}] (runtime.weight_f16), got {w.dtype} {tuple(w.shape)}")
+
+
+def attn_step_sublayer_f16x2(x: Tensor, ln_w: Optional[Tensor], ln_b: Optional[Tensor], w_qkv: Tensor, b_qkv: Optional[Tensor], w_proj: Tensor,
+                             b_proj: Optional[Tensor], flags: int, Lq: int, Lk: int, H: int, eps: float, scale: float, xn: Tensor, qkv: Tensor,
+                             ao: Tensor, k_cache: Tensor, v_cache: Tensor, probs: Optional[Tensor], y: Tensor) -> Tensor:
+    """the attention half of one cached step in the 'fp16x2' form, ONE call (afft_attn_step_sublayer_fwd): y = x + proj(step(qkv(LN(x)))) on
+    the nseq * Lq new rows of x fp32 [rows, d].  w_qkv / w_proj: FP16 images of the Conv1D weights; flags: 1 | F16X2_ONE_PASS_*; xn / qkv /
+    ao: fp16 scratch, hi plane [pad64(rows), width] and -- unless the flag of its consumer is set -- the lo plane behind it"""
+    rows, d = x.shape
+    assert x.dtype == y.dtype == torch.float32 and x.is_contiguous() and y.is_contiguous() and y.shape == x.shape
+    if rows % Lq or d % 64 or d % H:
+        raise ValueError(f"afft_amd: attn_step_sublayer_f16x2 needs rows % Lq == 0, d % 64 == 0 and d % H == 0 (rows {rows}, Lq {Lq}, d {d}, H {H})")
+    nseq = rows // Lq
+    _image(w_qkv, d, 3 * d, "w_qkv")
+    _image(w_proj, d, d, "w_proj")
+    _planes(xn, rows, d, not flags & L.F16X2_ONE_PASS_1, "xn")
+    _planes(qkv, rows, 3 * d, not flags & L.F16X2_ONE_PASS_ATTN, "qkv")
+    _planes(ao, rows, d, not flags & L.F16X2_ONE_PASS_2, "ao")
+    assert k_cache.dtype == v_cache.dtype == torch.float32
+    _cache_pair(k_cache, v_cache, nseq, d, "caches")
+    for t, n in ((ln_w, d), (ln_b, d), (b_qkv, 3 * d), (b_proj, d)):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n)
+    if probs is not None:
+        assert probs.dtype == torch.float32 and probs.is_contiguous() and probs.numel() == nseq * H * Lq * Lk
+    s = L.AttnStepSublayer()
+    s.rows, s.d, s.Lq, s.Lk, s.cap, s.H, s.conv1d, s.f16x2, s.eps, s.scale = rows, d, Lq, Lk, k_cache.shape[1], H, 1, int(flags), eps, scale
+    s.x, s.ln_w, s.ln_b = _p(x), _p(ln_w), _p(ln_b)
+    s.w_qkv, s.ldw_qkv, s.b_qkv = _p(w_qkv), w_qkv.stride(0), _p(b_qkv)
+    s.w_proj, s.ldw_proj, s.b_proj = _p(w_proj), w_proj.stride(0), _p(b_proj)
+    s.xn, s.qkv, s.ao = _p(xn), _p(qkv), _p(ao)
+    s.k_cache, s.v_cache, s.ldc, s.cache_seq = _p(k_cache), _p(v_cache), k_cache.stride(1), k_cache.stride(0)
+    s.probs, s.y = _p(probs), _p(y)
+    ws = gemm_workspace(x.device)
+    s.gemm_ws, s.gemm_ws_bytes = ws.data_ptr(), ws.numel()
+    L.check(L.lib().afft_attn_step_sublayer_fwd(C.byref(s), _stream()), "attn_step_sublayer_fwd")
+    return y
+
+
+def mlp_step_sublayer_f16x2(x: Tensor, ln_w: Optional[Tensor], ln_b: Optional[Tensor], w1: Tensor, b1: Optional[Tensor], w2: Tensor,
+                            b2: Optional[Tensor], flags: int, gelu: int, eps: float, xn: Tensor, h: Tensor, stats: Tensor, y: Tensor) -> Tensor:
+    """the MLP half of a cached step in the 'fp16x2' form: afft_mlp_sublayer_fwd with nothing saved (u, xn_b, h_b NULL), Conv1D FP16 images
+    w1 [d, hidden] / w2 [hidden, d]; xn / h: fp16 scratch as in attn_step_sublayer_f16x2 (lo planes unless F16X2_ONE_PASS_1 / _2);
+    stats: fp32 [2, rows] (mean, rstd: the entry point wants them)"""
+    rows, d = x.shape
+    hidden = w1.shape[1]
+    assert x.dtype == y.dtype == torch.float32 and x.is_contiguous() and y.is_contiguous() and y.shape == x.shape
+    if d % 64 or hidden % 64:
+        raise ValueError(f"afft_amd: mlp_step_sublayer_f16x2 needs d % 64 == 0 and hidden % 64 == 0 (d {d}, hidden {hidden})")
+    _image(w1, d, hidden, "w1")
+    _image(w2, hidden, d, "w2")
+    _planes(xn, rows, d, not flags & L.F16X2_ONE_PASS_1, "xn")
+    _planes(h, rows, hidden, not flags & L.F16X2_ONE_PASS_2, "h")
+    assert stats.dtype == torch.float32 and stats.is_contiguous() and stats.shape == (2, rows)
+    s = L.MLPSublayer()
+    s.rows, s.d, s.hidden, s.conv1d, s.gelu, s.eps, s.f16x2 = rows, d, hidden, 1, gelu, eps, int(flags)
+    s.x, s.ln_w, s.ln_b = _p(x), _p(ln_w), _p(ln_b)
+    s.w1, s.ldw1, s.b1, s.w2, s.ldw2, s.b2 = _p(w1), w1.stride(0), _p(b1), _p(w2), w2.stride(0), _p(b2)
+    s.xn, s.h = _p(xn), _p(h)
+    s.mean, s.rstd, s.y = _p(stats[0]), _p(stats[1]), _p(y)
+    ws = gemm_workspace(x.device)
+    s.gemm_ws, s.gemm_ws_bytes = ws.data_ptr(), ws.numel()
+    L.check(L.lib().afft_mlp_sublayer_fwd(C.byref(s), _stream()), "mlp_sublayer_fwd")
+    return y
+
+
 def attention_step_bwd(dout: Tensor, q: Tensor, k_cache: Tensor, v_cache: Tensor, probs: Tensor, nseq: int, Lq: int, Lk: int, H: int,
                        hd: int, scale: float, dq: Tensor, dk_new: Tensor, dv_new: Tensor, gk_cache: Tensor, gv_cache: Tensor,
                        drop: Optional[Tuple[float, int]] = None):

@@ -557,6 +557,22 @@ def set_kv_cache_train(on: bool):
     _KV_CACHE_TRAIN = bool(on)
 
 
+_KV_CACHE_FP16X2 = os.environ.get("AFFT_KV_CACHE_FP16X2", "0") == "1"
+
+
+def kv_cache_fp16x2() -> bool:
+    """Let the 'fp16x2' precision take the cached roll-out too (evaluation, no grad, output_len > 1, kv_cache() on): its step is one
+    composite call per attention half (afft_attn_step_sublayer_fwd, which knows the one-pass sites of that precision) around
+    afft_attention_step_fwd_split, fp32 caches.  AFFT_KV_CACHE_FP16X2=1; off by default: 'fp16x2' then recomputes, bit for
+    bit as before.  Training through the cache (kv_cache_train) stays closed to this precision."""
+    return _KV_CACHE_FP16X2
+
+
+def set_kv_cache_fp16x2(on: bool):
+    global _KV_CACHE_FP16X2
+    _KV_CACHE_FP16X2 = bool(on)
+
+
 _FUSED_SGD = os.environ.get("AFFT_FUSED_SGD", "1") != "0"
 
 

@@ -384,6 +384,29 @@ int afft_attention_step_bwd(const void* dout, int64_t lddo, const void* q, int64
  * value when no kernel takes the shape (afft_last_error says why). */
 int afft_attention_step_plan_for(int32_t dtype, int32_t Lq, int32_t Lk, int32_t hd, int32_t pitch_alignment_ok, int64_t* lds_and_tiles);
 
+/* The forward step in the operand form of the "fp16x2" precision: the same contract, range, append rule, mask, probs and summation order
+ * as afft_attention_step_fwd (fp32 arithmetic, no atomics, no scratch), with other storage.
+ *   q / k_new / v_new: fp16 HI planes [nseq * Lq, *] with row pitches ldq / ldk / ldv; in_lo != 0: each has a lo plane in_lo ELEMENTS
+ *     behind it (same pitch) and the value used is float(hi) + float(lo) -- what afft_gemm writes with out_dtype = AFFT_F16, out_lo = in_lo;
+ *     in_lo == 0: the hi planes alone (AFFT_F16X2_ONE_PASS_ATTN).
+ *   k_cache / v_cache: fp32 [nseq, cap, H*hd] (ldc, cache_seq in elements).  Rows [Lk - Lq, Lk) receive that fp32 value, nothing else is
+ *     written; new keys and values are read from k_new / v_new, never back from the cache.
+ *   out_hi: fp16 [nseq * Lq, H*hd], row pitch ldo: hi = fp16(x); out_lo != 0: lo = fp16(x - float(hi)) out_lo elements behind it (the
+ *     split of afft_layernorm_fwd_split / afft_attention_fwd_split: the A operand of the projection GEMM); out_lo == 0: hi only.
+ * Lo offsets: 0, or at least (nseq * Lq - 1) * pitch + H*hd (for in_lo the largest of ldq, ldk, ldv): a lo plane starts behind the last
+ * element of its hi plane.  A smaller non-zero offset -- one that overlaps the hi plane -- and a negative one are errors; that the planes
+ * of DIFFERENT operands do not overlap is the caller's business.  Pointers: planes 2-byte, caches and probs 4-byte aligned.
+ * 16-byte accesses when hd, ldq, ldk, ldv, ldo, in_lo, out_lo are multiples of 8, ldc and cache_seq of 4, and the pointers are 16-byte
+ * aligned; element accesses otherwise.  Every refusal is a host error before any launch. */
+int afft_attention_step_fwd_split(const void* q, int64_t ldq, const void* k_new, int64_t ldk, const void* v_new, int64_t ldv,
+                                  int64_t in_lo, float* k_cache, float* v_cache, int64_t ldc, int64_t cache_seq, int32_t nseq,
+                                  int32_t Lq, int32_t Lk, int32_t cap, int32_t H, int32_t hd, float scale, void* out_hi,
+                                  int64_t ldo, int64_t out_lo, float* probs, void* stream);
+/* Its plan, as afft_attention_step_plan_for reports the other forms: family 13, p0 = 1: 16-byte accesses, 0: element accesses; in_lo /
+ * out_lo != 0: the problem has those lo planes (at offsets pitch_alignment_ok describes).  No device needed. */
+int afft_attention_step_split_plan_for(int32_t Lq, int32_t Lk, int32_t hd, int32_t in_lo, int32_t out_lo, int32_t pitch_alignment_ok,
+                                       int64_t* lds_and_tiles);
+
 /* afft_layernorm_bwd whose incoming residual gradient dx_in is [rows / in_take, d] (row pitch lddx_in) and belongs to rows 0, in_take,
  * 2 in_take, ..: the other rows take no residual gradient (afft_attn_sublayer_t.take; in_take = 1: every row). */
 int afft_layernorm_bwd_take(const void* dy, int64_t lddy, int32_t dy_dtype, const float* x, int64_t ldx, const float* w, const float* mean,
@@ -748,6 +771,32 @@ typedef struct {       /* y = x + drop(proj(attention(q = w_q LN_q(x), k = w_k L
 } afft_cross_attn_sublayer_t;
 int afft_cross_attn_sublayer_fwd(const afft_cross_attn_sublayer_t* s, void* stream);
 int afft_cross_attn_sublayer_bwd(const afft_cross_attn_sublayer_t* s, void* stream, void* aux_stream);
+
+/* The attention half of ONE CACHED STEP of a roll-out in the "fp16x2" form (inference: nothing saved, no dropout, no side stream):
+ *   y = x + proj(step(qkv(LN(x))))  on the rows = nseq * Lq NEW rows, against the layer's key / value caches
+ * = afft_layernorm_fwd_split -> afft_gemm (QKV, bias, fp16 plane output) -> afft_attention_step_fwd_split -> afft_gemm (projection, bias,
+ * residual x, fp32 y), the launches and arguments of the f16x2 branch of afft_attn_sublayer_fwd with the attention core replaced.
+ * The other precisions keep their call-by-call step (afft_amd/functional.py attn_step). */
+typedef struct {
+  int32_t rows, d, Lq, Lk, cap, H;       /* rows = nseq * Lq new rows at positions Lk - Lq .. Lk - 1; d % 64 == 0                      */
+  int32_t conv1d;
+  int32_t f16x2;                         /* 1 | AFFT_F16X2_ONE_PASS_1 / _2 / _ATTN, as afft_attn_sublayer_t.f16x2 (2, the e4m3 lo planes, */
+                                         /* is refused: the step serves Conv1D weights)                                                  */
+  float eps, scale;
+  const float* x;                        /* [rows, d] fp32, dense                                                                       */
+  const float* ln_w; const float* ln_b;
+  const void* w_qkv; int64_t ldw_qkv; const float* b_qkv;      /* FP16 images                                                           */
+  const void* w_proj; int64_t ldw_proj; const float* b_proj;
+  void* xn; void* qkv; void* ao;         /* fp16 scratch, rows_pad = rows up to 64: hi plane [rows_pad, width], then -- where the flags   */
+                                         /* leave one: xn without ONE_PASS_1, qkv without ONE_PASS_ATTN, ao without ONE_PASS_2 -- the lo    */
+                                         /* plane rows_pad * width elements behind it; rows rows .. rows_pad - 1 of every plane are zeroed */
+  float* k_cache; float* v_cache;        /* fp32 [nseq, cap, d]                                                                         */
+  int64_t ldc, cache_seq;
+  float* probs;                          /* fp32 [nseq, H, Lq, Lk] or NULL                                                              */
+  float* y;                              /* [rows, d] fp32                                                                              */
+  void* gemm_ws; int64_t gemm_ws_bytes;  /* afft_gemm_t.workspace of `stream`                                                           */
+} afft_attn_step_sublayer_t;
+int afft_attn_step_sublayer_fwd(const afft_attn_step_sublayer_t* s, void* stream);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,9 @@ mode) over output_len = 2, 4, 8.
 
 Defaults are the cfg2 widths of bench.py: B = 64 clips, T = 16 frames, D = 2048, 6 layers, 4 heads, precision bf16.  --tree imports
 afft_amd from another checkout (a build of the parent commit, to compare against); --cache sets runtime.set_kv_cache where the tree has
-it, --cache-train sets runtime.set_kv_cache_train where the tree has it (0, or a tree without it: the recompute).  Every pass is bracketed by a device event pair and followed by a synchronise; every output_len is warmed up before its timed
+it, --cache-train sets runtime.set_kv_cache_train where the tree has it (0, or a tree without it: the recompute).  --precision fp16x2
+--cache-fp16x2 0|1: the evaluation forward in that precision with runtime.set_kv_cache_fp16x2 off (the recompute: the parent's behaviour)
+or on (the cached roll-out through the composite step), where the tree has the switch.  Every pass is bracketed by a device event pair and followed by a synchronise; every output_len is warmed up before its timed
 window; a run reports the median and the 10th / 90th percentile of its window.  Run-to-run spread: repeat the command (alternating the
 trees) and give the files to --table, which prints every run's median and their range per label.
 """
@@ -39,6 +41,9 @@ def run(a):
     has_train = hasattr(rt, "set_kv_cache_train")
     if has_train:
         rt.set_kv_cache_train(bool(a.cache_train))
+    has_f16 = hasattr(rt, "set_kv_cache_fp16x2")
+    if has_f16:
+        rt.set_kv_cache_fp16x2(bool(a.cache_fp16x2))
     pred = BaseFuturePredictor(a.D, inter_dim=a.D, n_layer=a.layers, n_head=a.heads).to(dev)
     pred = pred.train() if a.train else pred.eval()
     feats = torch.randn(a.B, a.T, a.D, device=dev)
@@ -72,7 +77,8 @@ def run(a):
                 ms.append(e0.elapsed_time(e1))
             ms.sort()
             rec = dict(label=a.label, kv_cache=bool(a.cache) if has_switch else None, train=bool(a.train),
-                       kv_cache_train=bool(a.cache_train) if has_train else None, precision=a.precision, B=a.B, T=a.T, D=a.D, layers=a.layers,
+                       kv_cache_train=bool(a.cache_train) if has_train else None,
+                       kv_cache_fp16x2=bool(a.cache_fp16x2) if has_f16 else None, precision=a.precision, B=a.B, T=a.T, D=a.D, layers=a.layers,
                        output_len=n_out, reps=a.reps, median_ms=round(statistics.median(ms), 4), p10_ms=round(ms[len(ms) // 10], 4),
                        p90_ms=round(ms[(len(ms) * 9) // 10], 4), checksum=float(out.detach().float().abs().mean()))
             lines.append(json.dumps(rec))
@@ -110,6 +116,7 @@ def main():
     ap.add_argument("--precision", default="bf16")
     ap.add_argument("--train", action="store_true")
     ap.add_argument("--cache-train", type=int, default=1)
+    ap.add_argument("--cache-fp16x2", type=int, default=0)
     ap.add_argument("--output-len", type=int, nargs="+", default=None)
     ap.add_argument("--B", type=int, default=64)
     ap.add_argument("--T", type=int, default=16)
