@@ -1028,7 +1028,7 @@ def _cross_bwd_c(ctx, dy):
 # The same sequences for what the composite entry points do not take (tensor masks, more than ATTN_SHORT_MAX tokens, post-LN and bare
 # modules, widths off the 64 grid, fp32 / bf16x3, the CPU double of afft_amd.ops).  The helpers below are the halves the three Functions
 # share, as _fwd_call / _bwd_begin / _bwd_finish are for the composite path; the order of steps inside each carries meaning, see there.
-_ATTN_NARGS, _ATTN_BIAS_AT = 18, 17       # AttnSublayer.forward: how many arguments, and which of them is `bias`
+_ATTN_NARGS, _ATTN_BIAS_AT = 20, 17       # AttnSublayer.forward: how many arguments, and which of them is `bias`
 _MLP_NARGS = 12                           # MLPSublayer.forward
 _CROSS_NARGS, _CROSS_BIAS_AT = 22, 21     # CrossAttnSublayer.forward (b_q, b_k, b_v sit right before `bias`)
 
@@ -1098,46 +1098,84 @@ def _cbc_bwd_close(ctx, dz: Act, W_in: Tensor, conv1d: bool, x: Tensor, ln_w, ln
 
 
 # --------------------------------------------------------------------------- pre-LN self-attention sub-layer
-class AttnSublayer(torch.autograd.Function):
-    """y = x + proj(attn(split(qkv(LN(x)))))   -- Block / DecoderBlock self-attention half
-    (models/transformerblock.py:131-133,158-159) and GPT2Block's attention half (HF modeling_gpt2.py).
-    x: fp32 [nseq*L, d].  Returns (y fp32 [nseq*L, d], probs fp32 [nseq, H, L, L])."""
-
-    @staticmethod
-    def forward(ctx, x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, L, H, mask, eps, conv1d, pre_ln=True, scale=None,
-                drop=None, probs_out=None, take=0, bias=None):
-        """probs_out: fp32 [nseq, H, L, L] to write the attention maps into (the caller's slice of ONE buffer for all its blocks:
-        the SA-Fuser returns the stacked maps, models/fusion.py:144 -- no torch.stack copy of every block's maps per forward)
-        take = L: y is [nseq, d], token 0 of every sequence (attn_take_ok says whether this call can do that)
-        bias: the tensor of mask = ('bias', tensor), as an argument of its own so that it can take a gradient"""
-        R, d = x.shape
-        assert take in (0, L) and (not take or attn_take_ok(x, L, H, pre_ln)), "AttnSublayer: take needs the composite path (attn_take_ok)"
-        nseq, hd = R // L, d // H
-        dev = x.device
-        ctx.composite = False
-        if probs_out is not None:
-            assert probs_out.shape == (nseq, H, L, L) and probs_out.dtype == torch.float32 and probs_out.is_contiguous()
-        # probs is returned for the caller's attention maps and takes no gradient: without this autograd hands backward a
-        # freshly ZERO-FILLED tensor of its shape for it on every call (a fill kernel per attention sub-layer and step)
-        ctx.set_materialize_grads(False)
-        if bias is None:
-            bias = mask_bias(mask)
-        if not _mask_is_tensor(mask) and L <= ATTN_SHORT_MAX and _composite_ok(x, pre_ln, d) and _attn_core_ok(L, hd):
-            return _attn_fwd_c(ctx, x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, L, H, mask, eps, conv1d, scale, drop, probs_out, take)
-        xn, mean, rstd = _cbc_ln_in(ctx, x, ln_w, ln_b, eps, pre_ln)
-        qkv = Act(R, 3 * d, dev)
-        _lin_fwd(xn, w_qkv, conv1d, qkv.live, bias=b_qkv)
-        ao = Act(R, d, dev)
-        probs = probs_out if probs_out is not None else torch.empty(nseq, H, L, L, dtype=torch.float32, device=dev)
-        scale = float(scale) if scale else float(hd) ** -0.5
-        _attention_fwd(qkv.cols(0, d), qkv.cols(d, 2 * d), qkv.cols(2 * d, 3 * d), nseq, L, H, hd, scale, mask, ao.live, probs, drop, bias)
-        ctx.attn_bias = bias if len(ctx.needs_input_grad) > _ATTN_BIAS_AT and ctx.needs_input_grad[_ATTN_BIAS_AT] else None
-        y = _cbc_out(x, ao, w_proj, conv1d, b_proj, pre_ln, drop, d)
+def _attn_cbc_fwd(ctx, x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, L, H, eps, conv1d, pre_ln, scale, drop, probs, mask, bias=None, cache=None,
+                  past=0):
+    """The call-by-call attention forward, the ONE place it is written: LN, QKV GEMM, core, output projection.  Returns (y, probs).
+    cache None: the core is the full-sequence one over the L tokens of every sequence (`mask`, `bias`); cache = (k_cache, v_cache[,
+    gk_cache, gv_cache]): the cached step (afft_attention_step_fwd / _fwd_drop) -- the L rows per sequence are NEW ones at positions
+    past .. past + L - 1, they attend causally to the keys and values earlier calls left in the caches and are appended by the same launch.
+    probs: the fp32 buffer to write the maps into, True (allocate it) or None (no maps: the no-grad step only).
+    ctx None: the no-grad use (attn_step) -- no upstream is looked up, nothing is kept, and the step is called without `drop`."""
+    R, d = x.shape
+    nseq, hd = R // L, d // H
+    dev = x.device
+    xn, mean, rstd = _cbc_ln_in(ctx, x, ln_w, ln_b, eps, pre_ln)
+    qkv = Act(R, 3 * d, dev)
+    _lin_fwd(xn, w_qkv, conv1d, qkv.live, bias=b_qkv)
+    ao = Act(R, d, dev)
+    Lk = past + L
+    if probs is True:
+        probs = torch.empty(nseq, H, L, Lk, dtype=torch.float32, device=dev)
+    scale = float(scale) if scale else float(hd) ** -0.5
+    q, k, v = qkv.cols(0, d), qkv.cols(d, 2 * d), qkv.cols(2 * d, 3 * d)
+    if cache is None:
+        _attention_fwd(q, k, v, nseq, L, H, hd, scale, mask, ao.live, probs, drop, bias)
+    elif ctx is None:
+        ops.attention_step(q, k, v, cache[0], cache[1], nseq, L, Lk, H, hd, scale, ao.live, probs)
+    else:
+        ops.attention_step(q, k, v, cache[0], cache[1], nseq, L, Lk, H, hd, scale, ao.live, probs, drop=_attn_drop(drop))
+    y = _cbc_out(x, ao, w_proj, conv1d, b_proj, pre_ln, drop, d)
+    if ctx is not None:
         ctx.save_for_backward(x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, mean, rstd, probs)
         ctx.acts = (xn, qkv, ao)
         ctx.cfg = (L, H, scale, conv1d, pre_ln, drop)
+        ctx.step = (cache, past) if cache is not None else None
         ctx.mark_non_differentiable(probs)
-        return y, probs
+    return y, probs
+
+
+class AttnSublayer(torch.autograd.Function):
+    """y = x + proj(attn(split(qkv(LN(x)))))   -- Block / DecoderBlock self-attention half
+    (models/transformerblock.py:131-133,158-159) and GPT2Block's attention half (HF modeling_gpt2.py).
+    x: fp32 [nseq*L, d].  Returns (y fp32 [nseq*L, d], probs fp32 [nseq, H, L, L]).
+
+    With `cache` it is one step of a cached roll-out inside the autograd graph: the same call-by-call sequence with the cached step as
+    its core (_attn_cbc_fwd; afft_attention_step_bwd in the backward), so gradient sink, first-touch rules, hand-over, side stream and
+    fused-optimizer bookkeeping are the same code; probs is then fp32 [nseq, H, L, past + L].
+    The key / value caches and their fp32 gradient twins are shared, mutable state OUTSIDE autograd: the forward appends this step's keys
+    and values, the backward adds what this step owes earlier rows to the gradient caches and reads what later steps owe its own rows.
+    That is sound because of how a roll-out is wired: step i's input is step i - 1's last hidden row, so every backward node of step i
+    runs before any backward node of step i - 1 -- the gradient-cache rows of step i - 1 are complete when that step reads them -- and
+    a later step's forward writes cache rows at or beyond this step's Lk only, which this step's backward never reads."""
+
+    @staticmethod
+    def forward(ctx, x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, L, H, mask, eps, conv1d, pre_ln=True, scale=None,
+                drop=None, probs_out=None, take=0, bias=None, cache=None, past=0):
+        """probs_out: fp32 [nseq, H, L, L] to write the attention maps into (the caller's slice of ONE buffer for all its blocks:
+        the SA-Fuser returns the stacked maps, models/fusion.py:144 -- no torch.stack copy of every block's maps per forward)
+        take = L: y is [nseq, d], token 0 of every sequence (attn_take_ok says whether this call can do that)
+        bias: the tensor of mask = ('bias', tensor), as an argument of its own so that it can take a gradient
+        cache, past: (k_cache, v_cache, gk_cache, gv_cache) of a layer of a KVCache made with grad=True (KVCache.layer(i)) and the positions
+        it holds; pre-LN and causal, call by call"""
+        R, d = x.shape
+        assert take in (0, L) and (not take or attn_take_ok(x, L, H, pre_ln)), "AttnSublayer: take needs the composite path (attn_take_ok)"
+        nseq, hd = R // L, d // H
+        ctx.composite = False
+        if probs_out is not None:
+            assert probs_out.shape == (nseq, H, L, past + L) and probs_out.dtype == torch.float32
+            assert probs_out.is_contiguous()
+        # probs is returned for the caller's attention maps and takes no gradient: without this autograd hands backward a
+        # freshly ZERO-FILLED tensor of its shape for it on every call (a fill kernel per attention sub-layer and step)
+        ctx.set_materialize_grads(False)
+        if cache is not None:
+            assert mask == "causal" and pre_ln and not take and bias is None, "AttnSublayer: a cached step is pre-LN and causal"
+        elif bias is None:
+            bias = mask_bias(mask)
+        if cache is None and not _mask_is_tensor(mask) and L <= ATTN_SHORT_MAX and _composite_ok(x, pre_ln, d) and _attn_core_ok(L, hd):
+            return _attn_fwd_c(ctx, x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, L, H, mask, eps, conv1d, scale, drop, probs_out, take)
+        ctx.attn_bias = bias if len(ctx.needs_input_grad) > _ATTN_BIAS_AT and ctx.needs_input_grad[_ATTN_BIAS_AT] else None
+        return _attn_cbc_fwd(ctx, x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, L, H, eps, conv1d, pre_ln, scale, drop,
+                             probs_out if probs_out is not None else True, mask, bias, cache, past)
 
     @staticmethod
     @_in_backward_precision
@@ -1149,6 +1187,7 @@ class AttnSublayer(torch.autograd.Function):
         if ctx.composite:
             return _pad(_attn_bwd_c(ctx, dy), _ATTN_NARGS)
         x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, mean, rstd, probs = ctx.saved_tensors
+        # (_b16 is the identity in every precision a cached step trains in: bf16 acts in 'bf16', and no bf16 backward in 'fp32' / 'bf16x3')
         xn, qkv, ao = (_b16(t) for t in ctx.acts)
         L, H, scale, conv1d, pre_ln, drop = ctx.cfg
         R, d = x.shape
@@ -1158,37 +1197,55 @@ class AttnSublayer(torch.autograd.Function):
         dao = Act(R, d, dev)
         _lin_dgrad(dya, w_proj, conv1d, dao.live)
         dqkv = Act(R, 3 * d, dev)
-        _attention_bwd(dao.live, qkv.cols(0, d), qkv.cols(d, 2 * d), qkv.cols(2 * d, 3 * d), probs, nseq, L, H, hd,
-                       scale, dqkv.cols(0, d), dqkv.cols(d, 2 * d), dqkv.cols(2 * d, 3 * d), drop)
-        g_bias = _attention_bias_bwd(ctx.attn_bias, dao.live, qkv.cols(2 * d, 3 * d), probs, nseq, L, H, hd, drop)
+        q, v = qkv.cols(0, d), qkv.cols(2 * d, 3 * d)
+        dq, dk, dv = dqkv.cols(0, d), dqkv.cols(d, 2 * d), dqkv.cols(2 * d, 3 * d)
+        g_bias = None
+        if ctx.step is None:
+            _attention_bwd(dao.live, q, qkv.cols(d, 2 * d), v, probs, nseq, L, H, hd, scale, dq, dk, dv, drop)
+            g_bias = _attention_bias_bwd(ctx.attn_bias, dao.live, v, probs, nseq, L, H, hd, drop)
+        else:
+            (k_cache, v_cache, gk_cache, gv_cache), past = ctx.step
+            ops.attention_step_bwd(dao.live, q, k_cache, v_cache, probs, nseq, L, past + L, H, hd, scale, dq, dk, dv, gk_cache, gv_cache,
+                                   drop=_attn_drop(drop))
+            ctx.step = ()      # (the caches are released; a second backward fails on unpacking this, as one of the full core does on ctx.acts)
         with _Side(dev):
             g_wq = _wgrad(dqkv, xn, w_qkv, conv1d)
             g_bq = _bgrad(dqkv.live, b_qkv)
         dx, g_lw, g_lb = _cbc_bwd_close(ctx, dqkv, w_qkv, conv1d, x, ln_w, ln_b, mean, rstd, dy, pre_ln)
-        return _pad((dx, g_lw, g_lb, g_wq, g_bq, g_wp, g_bp), _ATTN_BIAS_AT) + (g_bias,)
+        return _pad(_pad((dx, g_lw, g_lb, g_wq, g_bq, g_wp, g_bp), _ATTN_BIAS_AT) + (g_bias,), _ATTN_NARGS)
 
 
 # --------------------------------------------------------------------------- pre-LN MLP sub-layer
+def _mlp_cbc_fwd(ctx, x, ln_w, ln_b, w1, b1, w2, b2, eps, gelu, conv1d, pre_ln, drop):
+    """The call-by-call MLP forward: LN, fc1 + activation, fc2.  ctx None: the no-grad use (mlp_step), which keeps nothing -- and so
+    does not have fc1 write its pre-activation, which only the backward reads."""
+    R, d = x.shape
+    dev = x.device
+    hidden = w1.shape[1] if conv1d else w1.shape[0]
+    xn, mean, rstd = _cbc_ln_in(ctx, x, ln_w, ln_b, eps, pre_ln)
+    u = Act(R, hidden, dev) if ctx is not None else None
+    h = Act(R, hidden, dev)
+    _lin_fwd(xn, w1, conv1d, h.live, bias=b1, act=_GELU[gelu][0], pre=u.live if u is not None else None)
+    y = _cbc_out(x, h, w2, conv1d, b2, pre_ln, drop, w2.shape[1] if conv1d else w2.shape[0])
+    if ctx is not None:
+        ctx.save_for_backward(x, ln_w, ln_b, w1, b1, w2, b2, mean, rstd)
+        ctx.acts = (xn, u, h)
+        ctx.cfg = (gelu, conv1d, hidden, pre_ln, drop)
+    return y
+
+
 class MLPSublayer(torch.autograd.Function):
     """y = x + fc2(act(fc1(LN(x))))  -- models/transformerblock.py:84-89,134 (exact-erf GELU) and HF GPT2MLP (gelu_new)."""
 
     @staticmethod
     def forward(ctx, x, ln_w, ln_b, w1, b1, w2, b2, eps, gelu, conv1d, pre_ln=True, drop=None):
-        R, d = x.shape
-        dev = x.device
+        d = x.shape[1]
         hidden = w1.shape[1] if conv1d else w1.shape[0]
         d_out = w2.shape[1] if conv1d else w2.shape[0]
         ctx.composite = False
         if d_out == d and _composite_ok(x, pre_ln, d, hidden):
             return _mlp_fwd_c(ctx, x, ln_w, ln_b, w1, b1, w2, b2, eps, gelu, conv1d, hidden, drop)
-        xn, mean, rstd = _cbc_ln_in(ctx, x, ln_w, ln_b, eps, pre_ln)
-        u, h = Act(R, hidden, dev), Act(R, hidden, dev)
-        _lin_fwd(xn, w1, conv1d, h.live, bias=b1, act=_GELU[gelu][0], pre=u.live)
-        y = _cbc_out(x, h, w2, conv1d, b2, pre_ln, drop, d_out)
-        ctx.save_for_backward(x, ln_w, ln_b, w1, b1, w2, b2, mean, rstd)
-        ctx.acts = (xn, u, h)
-        ctx.cfg = (gelu, conv1d, hidden, pre_ln, drop)
-        return y
+        return _mlp_cbc_fwd(ctx, x, ln_w, ln_b, w1, b1, w2, b2, eps, gelu, conv1d, pre_ln, drop)
 
     @staticmethod
     @_in_backward_precision
@@ -1211,9 +1268,11 @@ class MLPSublayer(torch.autograd.Function):
 
 
 # --------------------------------------------------------------------------- cached roll-out: the two sub-layers on NEW rows only
-# Inference only (no autograd graph, nothing saved, no side stream): the forward halves of the call-by-call sequences above, with the
-# attention core replaced by afft_attention_step_fwd -- the new rows attend to the keys and values the earlier calls left in the cache,
-# and are appended to it by the same launch.
+# ONE path for every roll-out over a key / value cache.  Its attention half is the call-by-call sequence of AttnSublayer with the cached
+# step as the core (_attn_cbc_fwd): the new rows attend to the keys and values the earlier calls left in the cache, and are appended to it
+# by the same launch.  Inside the autograd graph (training through the cache) that is AttnSublayer(cache=...) and MLPSublayer; without
+# one (evaluation: nothing saved, no side stream) attn_step and mlp_step below, which run the same bodies with no ctx -- or, in the
+# 'fp16x2' precision, ONE composite call each, which knows that precision's one-pass GEMM sites.
 class KVCache:
     """Keys and values of every layer of a causal model for `B` sequences of up to `cap` positions: per layer two [B, cap, D] buffers
     (one allocation from torch's allocator) in the storage dtype the current precision gives its call-by-call attention core (bf16 in
@@ -1227,151 +1286,67 @@ class KVCache:
         self.gkv = torch.zeros(n_layer, 2, B, cap, D, dtype=torch.float32, device=device) if grad else None
         self.cap, self.len = cap, 0
 
-    def layer(self, i: int) -> Tuple[Tensor, Tensor]:
-        return self.kv[i, 0], self.kv[i, 1]
+    def layer(self, i: int) -> tuple:
+        """what a step of layer i takes: (k_cache, v_cache), and (gk_cache, gv_cache) behind them with a gradient twin.  Made per step, where
+        the device has work queued, not up front in the constructor, where it waits for the first launch."""
+        if self.gkv is None:
+            return self.kv[i, 0], self.kv[i, 1]
+        return self.kv[i, 0], self.kv[i, 1], self.gkv[i, 0], self.gkv[i, 1]
 
-    def grad_layer(self, i: int) -> Tuple[Tensor, Tensor]:
-        return self.gkv[i, 0], self.gkv[i, 1]
+
+def _step_composite_ok(x: Tensor, conv1d: bool, *widths: int) -> bool:
+    """the 'fp16x2' step (the caller has looked at the precision) goes through the composite calls where the sub-layer Functions would
+    (_composite_ok; Conv1D weights only); otherwise through the call-by-call step, whose GEMMs then run every site in two passes"""
+    return conv1d and rt.composite() and x.is_contiguous() and all(w % 64 == 0 for w in widths)      # (one row per call: any stride(0) is dense)
+
+
+def _f16x2_planes(rows: int, device, *sites):
+    """the fp16 scratch of a composite 'fp16x2' call, ONE allocation carved into a buffer per (width, one-pass flag of its consumer):
+    the hi plane [pad64(rows), width] and, unless that flag is set, the lo plane behind it"""
+    sizes = [rt.pad64(rows) * width * (1 if one_pass else 2) for width, one_pass in sites]
+    return torch.empty(sum(sizes), dtype=torch.float16, device=device).split(sizes)
 
 
 def attn_step(x: Tensor, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, Lq: int, H: int, eps: float, conv1d: bool, k_cache: Tensor,
               v_cache: Tensor, past: int, want_probs: bool) -> Tuple[Tensor, Optional[Tensor]]:
     """AttnSublayer's forward (pre-LN, causal, no dropout) on the Lq new rows per sequence of x fp32 [nseq * Lq, d], which sit at positions
-    past .. past + Lq - 1.  Returns (y, probs fp32 [nseq, H, Lq, past + Lq] or None)."""
+    past .. past + Lq - 1, without an autograd graph.  Returns (y, probs fp32 [nseq, H, Lq, past + Lq] or None).
+    In the 'fp16x2' precision: ONE composite call (ops.attn_step_sublayer_f16x2 -> afft_attn_step_sublayer_fwd) with the one-pass flags
+    the sub-layer Functions give the same sites (runtime.one_pass_flags; Conv1D weights: never the fp8 lo pass), the FP16 weight images,
+    and fp16 scratch with room for a lo plane only where one is written: xn | qkv | ao."""
     R, d = x.shape
+    if rt.precision() != "fp16x2" or not _step_composite_ok(x, conv1d, d):
+        return _attn_cbc_fwd(None, x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, Lq, H, eps, conv1d, True, None, None, want_probs or None,
+                             "causal", None, (k_cache, v_cache), past)
     nseq, hd, Lk = R // Lq, d // H, past + Lq
-    xn, _, _ = _cbc_ln_in(None, x, ln_w, ln_b, eps, True)
-    qkv = Act(R, 3 * d, x.device)
-    _lin_fwd(xn, w_qkv, conv1d, qkv.live, bias=b_qkv)
-    ao = Act(R, d, x.device)
-    probs = torch.empty(nseq, H, Lq, Lk, dtype=torch.float32, device=x.device) if want_probs else None
-    ops.attention_step(qkv.cols(0, d), qkv.cols(d, 2 * d), qkv.cols(2 * d, 3 * d), k_cache, v_cache, nseq, Lq, Lk, H, hd, float(hd) ** -0.5,
-                       ao.live, probs)
-    return _cbc_out(x, ao, w_proj, conv1d, b_proj, True, None, d), probs
-
-
-def mlp_step(x: Tensor, ln_w, ln_b, w1, b1, w2, b2, eps: float, gelu: str, conv1d: bool) -> Tensor:
-    """MLPSublayer's forward (pre-LN, no dropout) without the saved pre-activation"""
-    R, d = x.shape
-    hidden = w1.shape[1] if conv1d else w1.shape[0]
-    xn, _, _ = _cbc_ln_in(None, x, ln_w, ln_b, eps, True)
-    h = Act(R, hidden, x.device)
-    _lin_fwd(xn, w1, conv1d, h.live, bias=b1, act=_GELU[gelu][0])
-    return _cbc_out(x, h, w2, conv1d, b2, True, None, w2.shape[1] if conv1d else w2.shape[0])
-
-
-def _step_composite_ok(x: Tensor, *widths: int) -> bool:
-    """the 'fp16x2' step goes through the composite calls where the sub-layer Functions would (_composite_ok without the precision, which
-    the caller has looked at); otherwise through the call-by-call step above, whose GEMMs then run every site in two passes"""
-    return rt.composite() and x.is_contiguous() and all(w % 64 == 0 for w in widths)      # (one row per call: any stride(0) is dense)
-
-
-def attn_step_f16x2(x: Tensor, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, Lq: int, H: int, eps: float, conv1d: bool, k_cache: Tensor,
-                    v_cache: Tensor, past: int, want_probs: bool) -> Tuple[Tensor, Optional[Tensor]]:
-    """attn_step in the 'fp16x2' precision: ONE composite call (ops.attn_step_sublayer_f16x2 -> afft_attn_step_sublayer_fwd) with the
-    one-pass flags the sub-layer Functions give the same sites (runtime.one_pass_flags; Conv1D weights: never the fp8 lo pass), the FP16
-    weight images, and fp16 scratch with room for a lo plane only where one is written: xn | qkv | ao in one allocation"""
-    R, d = x.shape
-    if not (conv1d and _step_composite_ok(x, d)):
-        return attn_step(x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, Lq, H, eps, conv1d, k_cache, v_cache, past, want_probs)
-    nseq, hd, Lk, pr = R // Lq, d // H, past + Lq, rt.pad64(R)
     flags = 1 | rt.one_pass_flags(True, d, "qkv", "proj", "attn")
-    n_xn = pr * d * (1 if flags & L_.F16X2_ONE_PASS_1 else 2)
-    n_qkv = pr * 3 * d * (1 if flags & L_.F16X2_ONE_PASS_ATTN else 2)
-    n_ao = pr * d * (1 if flags & L_.F16X2_ONE_PASS_2 else 2)
-    planes = torch.empty(n_xn + n_qkv + n_ao, dtype=torch.float16, device=x.device)
+    xn, qkv, ao = _f16x2_planes(R, x.device, (d, flags & L_.F16X2_ONE_PASS_1), (3 * d, flags & L_.F16X2_ONE_PASS_ATTN),
+                                (d, flags & L_.F16X2_ONE_PASS_2))
     probs = torch.empty(nseq, H, Lq, Lk, dtype=torch.float32, device=x.device) if want_probs else None
     y = torch.empty(R, d, dtype=torch.float32, device=x.device)
     ops.attn_step_sublayer_f16x2(x, ln_w, ln_b, rt.weight_f16(w_qkv), b_qkv, rt.weight_f16(w_proj), b_proj, flags, Lq, Lk, H, eps,
-                                 float(hd) ** -0.5, planes[:n_xn], planes[n_xn:n_xn + n_qkv], planes[n_xn + n_qkv:], k_cache, v_cache, probs, y)
+                                 float(hd) ** -0.5, xn, qkv, ao, k_cache, v_cache, probs, y)
     _note_output(y, None, b_proj)
     return y, probs
 
 
-def mlp_step_f16x2(x: Tensor, ln_w, ln_b, w1, b1, w2, b2, eps: float, gelu: str, conv1d: bool) -> Tensor:
-    """mlp_step in the 'fp16x2' precision: the composite MLP forward (afft_mlp_sublayer_fwd) with nothing saved"""
+def mlp_step(x: Tensor, ln_w, ln_b, w1, b1, w2, b2, eps: float, gelu: str, conv1d: bool) -> Tensor:
+    """MLPSublayer's forward (pre-LN, no dropout) without an autograd graph and without the saved pre-activation; in the 'fp16x2'
+    precision the composite MLP forward (afft_mlp_sublayer_fwd) with nothing saved"""
     R, d = x.shape
     hidden = w1.shape[1] if conv1d else w1.shape[0]
-    if not (conv1d and w2.shape[1] == d and _step_composite_ok(x, d, hidden)):
-        return mlp_step(x, ln_w, ln_b, w1, b1, w2, b2, eps, gelu, conv1d)
-    pr = rt.pad64(R)
+    if rt.precision() != "fp16x2" or not (_step_composite_ok(x, conv1d, d, hidden) and w2.shape[1] == d):
+        return _mlp_cbc_fwd(None, x, ln_w, ln_b, w1, b1, w2, b2, eps, gelu, conv1d, True, None)
     flags = 1 | rt.one_pass_flags(True, d, "fc1", "fc2")
-    n_xn = pr * d * (1 if flags & L_.F16X2_ONE_PASS_1 else 2)
-    n_h = pr * hidden * (1 if flags & L_.F16X2_ONE_PASS_2 else 2)
-    planes = torch.empty(n_xn + n_h, dtype=torch.float16, device=x.device)
+    xn, h = _f16x2_planes(R, x.device, (d, flags & L_.F16X2_ONE_PASS_1), (hidden, flags & L_.F16X2_ONE_PASS_2))
     stats = torch.empty(2, R, dtype=torch.float32, device=x.device)
     y = torch.empty(R, d, dtype=torch.float32, device=x.device)
-    ops.mlp_step_sublayer_f16x2(x, ln_w, ln_b, rt.weight_f16(w1), b1, rt.weight_f16(w2), b2, flags, _GELU[gelu][0], eps, planes[:n_xn],
-                                planes[n_xn:], stats, y)
+    ops.mlp_step_sublayer_f16x2(x, ln_w, ln_b, rt.weight_f16(w1), b1, rt.weight_f16(w2), b2, flags, _GELU[gelu][0], eps, xn, h, stats, y)
     _note_output(y, None, b2)
     return y
 
 
-# --------------------------------------------------------------------------- cached roll-out with a backward pass
-_ATTN_STEP_NARGS = 18      # AttnStepSublayer.forward
-
-
-class AttnStepSublayer(torch.autograd.Function):
-    """AttnSublayer (pre-LN, causal) on the Lq NEW rows per sequence of x fp32 [nseq * Lq, d], at positions past .. past + Lq - 1: its
-    call-by-call sequence with the attention core replaced by the cached step (afft_attention_step_fwd / _fwd_drop, afft_attention_step_bwd),
-    so gradient sink, first-touch rules, hand-over, side stream and fused-optimizer bookkeeping are AttnSublayer's.
-    Returns (y fp32 [nseq * Lq, d], probs fp32 [nseq, H, Lq, past + Lq]).
-
-    The key / value caches and their fp32 gradient twins are shared, mutable state OUTSIDE autograd: the forward appends this step's keys
-    and values, the backward adds what this step owes earlier rows to the gradient caches and reads what later steps owe its own rows.
-    That is sound because of how a roll-out is wired: step i's input is step i - 1's last hidden row, so every backward node of step i
-    runs before any backward node of step i - 1 -- the gradient-cache rows of step i - 1 are complete when that step reads them -- and
-    a later step's forward writes cache rows at or beyond this step's Lk only, which this step's backward never reads."""
-
-    @staticmethod
-    def forward(ctx, x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, Lq, H, eps, conv1d, drop, k_cache, v_cache, gk_cache, gv_cache, past,
-                probs_out=None):
-        R, d = x.shape
-        nseq, hd, Lk = R // Lq, d // H, past + Lq
-        dev = x.device
-        ctx.set_materialize_grads(False)      # probs takes no gradient (AttnSublayer.forward)
-        xn, mean, rstd = _cbc_ln_in(ctx, x, ln_w, ln_b, eps, True)
-        qkv = Act(R, 3 * d, dev)
-        _lin_fwd(xn, w_qkv, conv1d, qkv.live, bias=b_qkv)
-        ao = Act(R, d, dev)
-        probs = probs_out if probs_out is not None else torch.empty(nseq, H, Lq, Lk, dtype=torch.float32, device=dev)
-        scale = float(hd) ** -0.5
-        ops.attention_step(qkv.cols(0, d), qkv.cols(d, 2 * d), qkv.cols(2 * d, 3 * d), k_cache, v_cache, nseq, Lq, Lk, H, hd, scale, ao.live,
-                           probs, drop=_attn_drop(drop))
-        y = _cbc_out(x, ao, w_proj, conv1d, b_proj, True, drop, d)
-        ctx.save_for_backward(x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, mean, rstd, probs)
-        ctx.acts = (xn, qkv, ao)
-        ctx.caches = (k_cache, v_cache, gk_cache, gv_cache)
-        ctx.cfg = (Lq, Lk, H, scale, conv1d, drop)
-        ctx.mark_non_differentiable(probs)
-        return y, probs
-
-    @staticmethod
-    @_in_backward_precision
-    def backward(ctx, dy, _dprobs):
-        if dy is None:
-            _drop_shadow()
-            flush_ready()
-            return _pad((), _ATTN_STEP_NARGS)
-        x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, mean, rstd, probs = ctx.saved_tensors
-        xn, qkv, ao = ctx.acts
-        k_cache, v_cache, gk_cache, gv_cache = ctx.caches
-        Lq, Lk, H, scale, conv1d, drop = ctx.cfg
-        R, d = x.shape
-        nseq, hd = R // Lq, d // H
-        dev = x.device
-        dy, dya, g_wp, g_bp = _cbc_bwd_open(dy, drop, b_proj, ao, w_proj, conv1d)
-        dao = Act(R, d, dev)
-        _lin_dgrad(dya, w_proj, conv1d, dao.live)
-        dqkv = Act(R, 3 * d, dev)
-        ops.attention_step_bwd(dao.live, qkv.cols(0, d), k_cache, v_cache, probs, nseq, Lq, Lk, H, hd, scale, dqkv.cols(0, d),
-                               dqkv.cols(d, 2 * d), dqkv.cols(2 * d, 3 * d), gk_cache, gv_cache, drop=_attn_drop(drop))
-        ctx.caches = None
-        with _Side(dev):
-            g_wq = _wgrad(dqkv, xn, w_qkv, conv1d)
-            g_bq = _bgrad(dqkv.live, b_qkv)
-        dx, g_lw, g_lb = _cbc_bwd_close(ctx, dqkv, w_qkv, conv1d, x, ln_w, ln_b, mean, rstd, dy, True)
-        return _pad((dx, g_lw, g_lb, g_wq, g_bq, g_wp, g_bp), _ATTN_STEP_NARGS)
+attn_step_f16x2, mlp_step_f16x2 = attn_step, mlp_step      # the names these forms had while they were functions of their own
 
 
 # --------------------------------------------------------------------------- pre-LN cross-attention sub-layer

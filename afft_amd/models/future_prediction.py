@@ -73,42 +73,34 @@ class GPT2Block(nn.Module):
         self.ln_2 = nn.LayerNorm(n_embd, eps=eps)
         self.mlp = GPT2MLP(n_embd, resid_pdrop)
 
-    def forward_rows(self, h: Tensor, L: int) -> Tuple[Tensor, Tensor]:
-        a, m = self.attn, self.mlp
-        h, probs = F_.AttnSublayer.apply(h, self.ln_1.weight, self.ln_1.bias, a.c_attn.weight, a.c_attn.bias,
-                                         a.c_proj.weight, a.c_proj.bias, L, a.num_heads, "causal", self.ln_1.eps,
-                                         True, True, None,
-                                         D_.cfg(self, attn=a.attn_dropout.p, out=a.resid_dropout.p))
-        h = F_.MLPSublayer.apply(h, self.ln_2.weight, self.ln_2.bias, m.c_fc.weight, m.c_fc.bias, m.c_proj.weight,
-                                 m.c_proj.bias, self.ln_2.eps, "tanh", True, True, D_.cfg(self, out=m.dropout.p))
+    def _halves(self):
+        """(attention half, MLP half), each (eps of its LayerNorm, its module, its parameters in the order every functional form of it takes).
+        Every sub-module is looked up once: nn.Module attribute look-ups are most of what a block costs the host in a decode step."""
+        ln1, a, ln2, m = self.ln_1, self.attn, self.ln_2, self.mlp
+        qkv, proj, fc1, fc2 = a.c_attn, a.c_proj, m.c_fc, m.c_proj
+        return ((ln1.eps, a, (ln1.weight, ln1.bias, qkv.weight, qkv.bias, proj.weight, proj.bias)),
+                (ln2.eps, m, (ln2.weight, ln2.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias)))
+
+    def forward_rows(self, h: Tensor, L: int, step=()) -> Tuple[Tensor, Tensor]:
+        """the block on rows of the autograd graph: L tokens per clip, or (step = (cache, past): KVCache.layer(i) of a cache with a gradient
+        twin and the positions it holds) the L NEW rows per clip of a cached step"""
+        (eps1, a, attn), (eps2, m, mlp) = self._halves()
+        if step:
+            step = (None, 0, None) + step      # (probs_out, take, bias: AttnSublayer's arguments before `cache`)
+        h, probs = F_.AttnSublayer.apply(h, *attn, L, a.num_heads, "causal", eps1, True, True, None,
+                                         D_.cfg(self, attn=a.attn_dropout.p, out=a.resid_dropout.p), *step)
+        h = F_.MLPSublayer.apply(h, *mlp, eps2, "tanh", True, True, D_.cfg(self, out=m.dropout.p))
         return h, probs
 
-    def forward_step(self, h: Tensor, Lq: int, k_cache: Tensor, v_cache: Tensor, past: int, want_attn: bool):
-        """the block on the Lq new rows per clip at positions past .. past + Lq - 1 (inference: F_.attn_step / F_.mlp_step; in the
-        'fp16x2' precision their composite forms F_.attn_step_f16x2 / F_.mlp_step_f16x2)"""
-        a, m = self.attn, self.mlp
-        if rt.precision() == "fp16x2":
-            h, probs = F_.attn_step_f16x2(h, self.ln_1.weight, self.ln_1.bias, a.c_attn.weight, a.c_attn.bias, a.c_proj.weight, a.c_proj.bias,
-                                          Lq, a.num_heads, self.ln_1.eps, True, k_cache, v_cache, past, want_attn)
-            h = F_.mlp_step_f16x2(h, self.ln_2.weight, self.ln_2.bias, m.c_fc.weight, m.c_fc.bias, m.c_proj.weight, m.c_proj.bias,
-                                  self.ln_2.eps, "tanh", True)
-            return h, probs
-        h, probs = F_.attn_step(h, self.ln_1.weight, self.ln_1.bias, a.c_attn.weight, a.c_attn.bias, a.c_proj.weight, a.c_proj.bias,
-                                Lq, a.num_heads, self.ln_1.eps, True, k_cache, v_cache, past, want_attn)
-        h = F_.mlp_step(h, self.ln_2.weight, self.ln_2.bias, m.c_fc.weight, m.c_fc.bias, m.c_proj.weight, m.c_proj.bias, self.ln_2.eps,
-                        "tanh", True)
-        return h, probs
-
-
-    def forward_step_train(self, h: Tensor, Lq: int, caches, past: int, probs_out=None):
-        """forward_step with a backward pass and dropout (F_.AttnStepSublayer, F_.MLPSublayer); caches: (k, v, grad k, grad v) of the layer"""
-        a, m = self.attn, self.mlp
-        h, probs = F_.AttnStepSublayer.apply(h, self.ln_1.weight, self.ln_1.bias, a.c_attn.weight, a.c_attn.bias, a.c_proj.weight,
-                                             a.c_proj.bias, Lq, a.num_heads, self.ln_1.eps, True,
-                                             D_.cfg(self, attn=a.attn_dropout.p, out=a.resid_dropout.p), *caches, past, probs_out)
-        h = F_.MLPSublayer.apply(h, self.ln_2.weight, self.ln_2.bias, m.c_fc.weight, m.c_fc.bias, m.c_proj.weight,
-                                 m.c_proj.bias, self.ln_2.eps, "tanh", True, True, D_.cfg(self, out=m.dropout.p))
-        return h, probs
+    def forward_step(self, h: Tensor, Lq: int, cache, past: int, want_attn: bool, train: bool = False):
+        """the block on the Lq new rows per clip at positions past .. past + Lq - 1; cache = KVCache.layer(i) = (k, v[, grad k, grad v]).
+        Evaluation: F_.attn_step / F_.mlp_step, which pick their form by the precision.  train: forward_rows over the cache -- the
+        same sequence through the Functions, with a backward pass, dropout and the gradient caches (probs always come back)."""
+        if train:
+            return self.forward_rows(h, Lq, (cache, past))
+        (eps1, a, attn), (eps2, _, mlp) = self._halves()
+        h, probs = F_.attn_step(h, *attn, Lq, a.num_heads, eps1, True, cache[0], cache[1], past, want_attn)
+        return F_.mlp_step(h, *mlp, eps2, "tanh", True), probs
 
 
 class GPT2Model(nn.Module):
@@ -151,43 +143,42 @@ class GPT2Model(nn.Module):
         and values to `cache` and attends to what is there.  Inference only (eval mode, no grad).  Returns (last_hidden_state of the new
         rows, [probs (B, H, Lq, cache.len + Lq) per layer]) and advances cache.len."""
         assert not torch.is_grad_enabled() and not self.training, "GPT2Model.forward_step is an inference path"
-        past = cache.len
-        if past + Lq > min(cache.cap, self.wpe.weight.shape[0]):
-            raise ValueError(f"GPT2Model.forward_step: positions {past}..{past + Lq - 1} exceed the cache ({cache.cap}) or n_positions")
-        h = torch.empty_like(x_rows)
-        F_.ops.add_rows_periodic(x_rows, self.wpe.weight[past:past + Lq], Lq, h)
-        attns = []
-        for i, blk in enumerate(self.h):
-            h, probs = blk.forward_step(h, Lq, *cache.layer(i), past, want_attn)
-            if want_attn:
-                attns.append(probs)
-        y = torch.empty_like(h)
-        F_.ops.layernorm_fwd(h, self.ln_f.weight, self.ln_f.bias, self.ln_f.eps, y)
-        F_._forget_output()
-        cache.len = past + Lq
-        return y, attns
-
+        return self._step(x_rows, Lq, cache, want_attn, train=False)
 
     def forward_step_train(self, x_rows: Tensor, Lq: int, cache: "F_.KVCache", want_attn: bool = False):
         """forward_step as a node of the autograd graph (training mode and / or grad enabled): the same rows, positions and cache
-        traffic through the Functions forward_rows uses -- AddRowTable at positions cache.len .. cache.len + Lq - 1, the embedding
-        dropout, AttnStepSublayer / MLPSublayer per block, LayerNormRows.  `cache` was made with grad=True."""
-        past = cache.len
+        traffic through the Functions forward_rows uses.  `cache` was made with grad=True."""
         if cache.gkv is None:
             raise ValueError("GPT2Model.forward_step_train needs a cache with a gradient twin (new_cache(..., grad=True))")
+        return self._step(x_rows, Lq, cache, want_attn, train=True)
+
+    def _step(self, x_rows: Tensor, Lq: int, cache: "F_.KVCache", want_attn: bool, train: bool):
+        """the one step body: positions cache.len .. cache.len + Lq - 1, the blocks over the cache, ln_f, and cache.len moves on.  train: the
+        positions, the embedding dropout and ln_f go through AddRowTable / ElementDropout / LayerNormRows, as in forward_rows; evaluation
+        makes the bare calls -- no statistics out of the LayerNorm, nothing recorded for a backward pass."""
+        past = cache.len
         if past + Lq > min(cache.cap, self.wpe.weight.shape[0]):
-            raise ValueError(f"GPT2Model.forward_step_train: positions {past}..{past + Lq - 1} exceed the cache ({cache.cap}) or n_positions")
-        h = F_.AddRowTable.apply(x_rows, self.wpe.weight, Lq, past)
-        if self.training and self.drop.p > 0:
-            h = F_.ElementDropout.apply(h, D_.elementwise(self.drop.p))
+            raise ValueError(f"GPT2Model: positions {past}..{past + Lq - 1} of a cached step exceed the cache ({cache.cap}) or n_positions")
+        if train:
+            h = F_.AddRowTable.apply(x_rows, self.wpe.weight, Lq, past)
+            if self.training and self.drop.p > 0:
+                h = F_.ElementDropout.apply(h, D_.elementwise(self.drop.p))
+        else:
+            h = torch.empty_like(x_rows)
+            F_.ops.add_rows_periodic(x_rows, self.wpe.weight[past:past + Lq], Lq, h)
         attns = []
         for i, blk in enumerate(self.h):
-            h, probs = blk.forward_step_train(h, Lq, cache.layer(i) + cache.grad_layer(i), past)
+            h, probs = blk.forward_step(h, Lq, cache.layer(i), past, want_attn, train)
             if want_attn:
                 attns.append(probs)
-        h = F_.LayerNormRows.apply(h, self.ln_f.weight, self.ln_f.bias, self.ln_f.eps, 1)
+        if train:
+            y = F_.LayerNormRows.apply(h, self.ln_f.weight, self.ln_f.bias, self.ln_f.eps, 1)
+        else:
+            y = torch.empty_like(h)
+            F_.ops.layernorm_fwd(h, self.ln_f.weight, self.ln_f.bias, self.ln_f.eps, y)
+            F_._forget_output()
         cache.len = past + Lq
-        return h, attns
+        return y, attns
 
 
 class BaseFuturePredictor(nn.Module):
@@ -215,25 +206,19 @@ class BaseFuturePredictor(nn.Module):
         """feats (B, T, C) -> (B, T + output_len - 1, C), {gpt2_att_i: (B, layers, heads, T, T) for i = 0, (B, layers, heads, 1, T + i) after}.
 
         output_len > 1: the reference rolls out with HF's KV cache, feeding the last hidden state back as the next input embedding at the
-        next position (future_prediction.py:395-412).  In evaluation (eval mode, no grad, runtime.kv_cache(); the 'fp16x2' precision
-        only with runtime.kv_cache_fp16x2(), off by default: its step is a composite call of its own, which knows that precision's
-        one-pass GEMM sites) this does the same: the T
-        observed frames run once through GPT2Model.forward_step, which leaves every layer's keys and values in a KVCache, and every
-        further frame is ONE new row per clip attending to the cache (afft_attention_step_fwd).  With grad enabled, in training mode or
-        with AFFT_KV_CACHE=0 the roll-out re-runs the extended sequence for every predicted frame and keeps its last row -- a causal
-        model's earlier positions do not change when a token is appended, so that is the same arithmetic without a cache.  With
-        runtime.kv_cache_train() (AFFT_KV_CACHE_TRAIN=1, off by default) those passes go over the cache too, as the reference trains
-        through HF's: GPT2Model.forward_step_train, whose attention step has a backward pass."""
+        next position (future_prediction.py:395-412).  rollout_path says which of three forms a call takes.  'cached' (_rollout_cached)
+        does the same: the T observed frames run once through GPT2Model.forward_step, which leaves every layer's keys and values in a
+        KVCache, and every further frame is ONE new row per clip attending to the cache (afft_attention_step_fwd).  'recompute' re-runs
+        the extended sequence for every predicted frame and keeps its last row -- a causal model's earlier positions do not change when a
+        token is appended, so that is the same arithmetic without a cache.  'cached_train' is the cached form inside the autograd graph,
+        as the reference trains through HF's: GPT2Model.forward_step_train, whose attention step has a backward pass."""
         addl_endpoints = {}
         feats = self._map(self.encoder, feats)
         B, T, D = feats.shape
         seq = feats if feats.dtype == torch.float32 else feats.float()
-        if output_len > 1 and rt.kv_cache() and not torch.is_grad_enabled() and not self.training and (
-                rt.precision() != "fp16x2" or rt.kv_cache_fp16x2()):
-            return self._rollout_cached(seq, output_len, addl_endpoints)
-        if (output_len > 1 and rt.kv_cache() and rt.kv_cache_train() and (torch.is_grad_enabled() or self.training)
-                and rt.precision() in ("bf16", "fp32", "bf16x3")):
-            return self._rollout_cached_train(seq, output_len, addl_endpoints)
+        path = rollout_path(output_len, torch.is_grad_enabled() or self.training)
+        if path != "recompute":
+            return self._rollout_cached(seq, output_len, addl_endpoints, train=path == "cached_train")
         outs: List[Tensor] = []
         for output_id in range(output_len):
             L = seq.shape[1]
@@ -248,15 +233,18 @@ class BaseFuturePredictor(nn.Module):
                 seq = torch.cat([seq, h[:, -1:, :]], dim=1)
         return (outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)), addl_endpoints
 
-    def _rollout_cached(self, seq: Tensor, output_len: int, addl_endpoints: Dict) -> Tuple[torch.Tensor, Dict]:
-        """the roll-out over a KVCache: one forward_step on the T observed frames, then one per further frame on the previous last row"""
+    def _rollout_cached(self, seq: Tensor, output_len: int, addl_endpoints: Dict, train: bool) -> Tuple[torch.Tensor, Dict]:
+        """the roll-out over a KVCache: one step on the T observed frames, then one per further frame on the previous last row.  train: inside
+        the autograd graph -- the fed-back row stays a node of it, so the loss on frame T + i reaches the parameters through every earlier
+        step, and through the cache's gradient twin (F_.AttnSublayer with `cache`)"""
         B, T, D = seq.shape
-        cache = self.gpt_model.new_cache(B, T + output_len - 1, seq.device)
+        cache = self.gpt_model.new_cache(B, T + output_len - 1, seq.device, grad=train)
+        step = self.gpt_model.forward_step_train if train else self.gpt_model.forward_step
         outs: List[Tensor] = []
         new = seq.reshape(B * T, D).contiguous()
         for output_id in range(output_len):
             Lq = T if output_id == 0 else 1
-            h, attns = self.gpt_model.forward_step(new, Lq, cache, self.output_attentions)
+            h, attns = step(new, Lq, cache, self.output_attentions)
             if self.output_attentions:
                 addl_endpoints[f'gpt2_att_{output_id}'] = torch.stack(attns, dim=1)      # (B, layers, H, Lq, Lk)
             h = h.view(B, Lq, D)
@@ -264,23 +252,18 @@ class BaseFuturePredictor(nn.Module):
             new = h[:, -1, :].contiguous()
         return torch.cat(outs, dim=1), addl_endpoints
 
-    def _rollout_cached_train(self, seq: Tensor, output_len: int, addl_endpoints: Dict) -> Tuple[torch.Tensor, Dict]:
-        """_rollout_cached inside the autograd graph: the fed-back row stays a node of it, so the loss on frame T + i reaches the
-        parameters through every earlier step, and through the cache (F_.AttnStepSublayer)"""
-        B, T, D = seq.shape
-        cache = self.gpt_model.new_cache(B, T + output_len - 1, seq.device, grad=True)
-        outs: List[Tensor] = []
-        new = seq.reshape(B * T, D).contiguous()
-        for output_id in range(output_len):
-            Lq = T if output_id == 0 else 1
-            h, attns = self.gpt_model.forward_step_train(new, Lq, cache, self.output_attentions)
-            if self.output_attentions:
-                addl_endpoints[f'gpt2_att_{output_id}'] = torch.stack(attns, dim=1)      # (B, layers, H, Lq, Lk)
-            h = h.view(B, Lq, D)
-            outs.append(self._map(self.decoder, h))
-            new = h[:, -1, :].contiguous()
-        return torch.cat(outs, dim=1), addl_endpoints
 
+def rollout_path(output_len: int, grad: bool) -> str:
+    """Which form BaseFuturePredictor.forward takes; grad: autograd is recording or the module is in training mode.
+      'recompute'     nothing to roll out (output_len 1); runtime.kv_cache() off (AFFT_KV_CACHE=0 wins over everything); and whatever
+                      the two lines below leave
+      'cached'        evaluation: every precision -- 'fp16x2' only with runtime.kv_cache_fp16x2() (off by default)
+      'cached_train'  with grad: runtime.kv_cache_train() (off by default) in 'bf16', 'fp32' and 'bf16x3'; 'fp16x2' never trains through it"""
+    if output_len <= 1 or not rt.kv_cache():
+        return "recompute"
+    if grad:
+        return "cached_train" if rt.kv_cache_train() and rt.precision() in ("bf16", "fp32", "bf16x3") else "recompute"
+    return "cached" if rt.precision() != "fp16x2" or rt.kv_cache_fp16x2() else "recompute"
 
 
 # --------------------------------------------------------------------------- cross-modal fusion + prediction

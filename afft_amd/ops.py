@@ -411,16 +411,14 @@ def attention_step(q: Tensor, k_new: Tensor, v_new: Tensor, k_cache: Tensor, v_c
     _cache_pair(k_cache, v_cache, nseq, H * hd, "caches")
     if probs is not None:
         assert probs.dtype == torch.float32 and probs.is_contiguous() and probs.numel() == nseq * H * Lq * Lk
-    if drop is not None and drop[0] > 0:
-        L.check(L.lib().afft_attention_step_fwd_drop(_p(q), _rowmajor(q, "q"), _p(k_new), _rowmajor(k_new, "k_new"), _p(v_new),
-                                                     _rowmajor(v_new, "v_new"), _p(k_cache), _p(v_cache), k_cache.stride(1), k_cache.stride(0),
-                                                     _dt(q), nseq, Lq, Lk, k_cache.shape[1], H, hd, scale, float(drop[0]), int(drop[1]),
-                                                     _p(out), _rowmajor(out, "out"), _p(probs), _stream()), "attention_step_drop")
-        return out
-    L.check(L.lib().afft_attention_step_fwd(_p(q), _rowmajor(q, "q"), _p(k_new), _rowmajor(k_new, "k_new"), _p(v_new), _rowmajor(v_new, "v_new"),
-                                            _p(k_cache), _p(v_cache), k_cache.stride(1), k_cache.stride(0), _dt(q), nseq, Lq, Lk,
-                                            k_cache.shape[1], H, hd, scale, _p(out), _rowmajor(out, "out"), _p(probs), _stream()),
-            "attention_step")
+    args = [_p(q), _rowmajor(q, "q"), _p(k_new), _rowmajor(k_new, "k_new"), _p(v_new), _rowmajor(v_new, "v_new"), _p(k_cache), _p(v_cache),
+            k_cache.stride(1), k_cache.stride(0), _dt(q), nseq, Lq, Lk, k_cache.shape[1], H, hd, scale, _p(out), _rowmajor(out, "out"), _p(probs),
+            _stream()]
+    if drop is not None and drop[0] > 0:      # the _drop entry point takes (p, key) after `scale`
+        args[18:18] = float(drop[0]), int(drop[1])
+        L.check(L.lib().afft_attention_step_fwd_drop(*args), "attention_step_drop")
+    else:
+        L.check(L.lib().afft_attention_step_fwd(*args), "attention_step")
     return out
 
 

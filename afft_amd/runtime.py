@@ -547,7 +547,7 @@ _KV_CACHE_TRAIN = os.environ.get("AFFT_KV_CACHE_TRAIN", "0") == "1"
 def kv_cache_train() -> bool:
     """Train THROUGH the key / value cache, as the reference trains through HF's: with grad enabled or in training mode the roll-out
     (output_len > 1, kv_cache() on, precision 'bf16', 'fp32' or 'bf16x3') runs T + output_len - 1 predictor rows per clip instead of
-    re-running the extended sequence for every predicted frame (functional.AttnStepSublayer, afft_attention_step_bwd).
+    re-running the extended sequence for every predicted frame (functional.AttnSublayer with `cache`, afft_attention_step_bwd).
     AFFT_KV_CACHE_TRAIN=1; off by default: the recompute stays the training form until this one is made the default."""
     return _KV_CACHE_TRAIN
 

@@ -1,7 +1,7 @@
 """Build-container test of the HOST logic of the cached roll-out in the 'fp16x2' precision (runtime.kv_cache_fp16x2, BaseFuturePredictor.forward,
-GPT2Block.forward_step, functional.attn_step_f16x2 / mlp_step_f16x2) on CPU tensors.  The two composite calls of that step
-(ops.attn_step_sublayer_f16x2, ops.mlp_step_sublayer_f16x2) are replaced by the plain-torch doubles below -- restatements of the contracts in
-include/afft_hip.h, modelled on tests/cpu_ops_step.py, which supplies every other double -- and record what they were handed: when the path
+GPT2Block.forward_step, functional.attn_step / mlp_step) on CPU tensors.  The two composite calls of that step
+(ops.attn_step_sublayer_f16x2, ops.mlp_step_sublayer_f16x2) are replaced by the plain-torch doubles of tests/cpu_ops_step_f16x2.py --
+restatements of the contracts in include/afft_hip.h -- which record what they were handed: when the path
 engages, with which rows and lengths, which one-pass flags, and how much plane scratch.  What the kernels compute is tested on the GPU."""
 import contextlib
 import os
@@ -11,74 +11,33 @@ import sys
 import pytest
 import torch
 
-import cpu_ops_step
+import cpu_ops_step_f16x2
+from cpu_ops_step_f16x2 import ONE1, ONE2, ONE_ATTN      # AFFT_F16X2_ONE_PASS_1 / _2 / _ATTN
 
 B, T, D, H, LAYERS = 2, 4, 64, 2, 2
-ONE1, ONE2, ONE_ATTN = 4, 8, 16      # AFFT_F16X2_ONE_PASS_1 / _2 / _ATTN
-
-
-def _operand(t, one_pass):
-    """what a GEMM or the attention core reads of an activation carried as fp16 planes: hi alone, or hi + lo"""
-    hi = t.half().float()
-    return hi if one_pass else hi + (t - hi).half().float()
-
-
-class _Doubles:
-    """the two composite step calls in plain torch, and a record of every call"""
-
-    def __init__(self):
-        self.attn, self.mlp = [], []
-
-    @torch.no_grad()
-    def attn_step_sublayer_f16x2(self, x, ln_w, ln_b, w_qkv, b_qkv, w_proj, b_proj, flags, Lq, Lk, H_, eps, scale, xn, qkv, ao, k_cache, v_cache,
-                                 probs, y):
-        rows, d = x.shape
-        assert flags & 3 == 1 and w_qkv.dtype == w_proj.dtype == xn.dtype == qkv.dtype == ao.dtype == torch.float16
-        assert k_cache.dtype == v_cache.dtype == torch.float32
-        self.attn.append(dict(flags=flags, rows=rows, d=d, Lq=Lq, Lk=Lk, xn=xn.numel(), qkv=qkv.numel(), ao=ao.numel(), probs=probs is not None))
-        v = torch.nn.functional.layer_norm(x, (d,), ln_w, ln_b, eps)
-        q3 = _operand(_operand(v, flags & ONE1) @ w_qkv[:d, :3 * d].float() + b_qkv, flags & ONE_ATTN)
-        out = torch.empty(rows, d)
-        cpu_ops_step.attention_step(q3[:, :d], q3[:, d:2 * d], q3[:, 2 * d:], k_cache, v_cache, rows // Lq, Lq, Lk, H_, d // H_, scale, out, probs)
-        y.copy_(x + _operand(out, flags & ONE2) @ w_proj[:d, :d].float() + b_proj)
-        return y
-
-    @torch.no_grad()
-    def mlp_step_sublayer_f16x2(self, x, ln_w, ln_b, w1, b1, w2, b2, flags, gelu, eps, xn, h, stats, y):
-        from afft_amd import _lib
-        rows, d = x.shape
-        hidden = w1.shape[1]
-        assert flags & 3 == 1 and gelu == _lib.ACT_GELU_TANH and stats.shape == (2, rows)
-        self.mlp.append(dict(flags=flags, rows=rows, d=d, hidden=hidden, xn=xn.numel(), h=h.numel()))
-        v = torch.nn.functional.layer_norm(x, (d,), ln_w, ln_b, eps)
-        u = torch.nn.functional.gelu(_operand(v, flags & ONE1) @ w1[:d, :hidden].float() + b1, approximate="tanh")
-        y.copy_(x + _operand(u, flags & ONE2) @ w2[:hidden, :d].float() + b2)
-        return y
 
 
 @contextlib.contextmanager
 def _installed():
-    """cpu_ops_step's doubles, the two above, and counters on the QKV GEMMs and the call-by-call step"""
+    """cpu_ops_step's doubles, the two composite ones of cpu_ops_step_f16x2, and counters on the QKV GEMMs and the call-by-call step"""
     from afft_amd import ops
-    dbl = _Doubles()
-    with cpu_ops_step.installed():
-        saved = ops.attn_step_sublayer_f16x2, ops.mlp_step_sublayer_f16x2, ops.gemm, ops.attention_step
+    with cpu_ops_step_f16x2.installed() as dbl:
+        saved = ops.gemm, ops.attention_step
         dbl.qkv_rows, dbl.steps = [], 0
 
         def gemm(a, b, out, **kw):
             if out.shape[1] == 3 * D:
                 dbl.qkv_rows.append(out.shape[0])
-            return saved[2](a, b, out, **kw)
+            return saved[0](a, b, out, **kw)
 
         def step(*a, **k):
             dbl.steps += 1
-            return saved[3](*a, **k)
-        ops.attn_step_sublayer_f16x2, ops.mlp_step_sublayer_f16x2, ops.gemm, ops.attention_step = (dbl.attn_step_sublayer_f16x2,
-                                                                                                    dbl.mlp_step_sublayer_f16x2, gemm, step)
+            return saved[1](*a, **k)
+        ops.gemm, ops.attention_step = gemm, step
         try:
             yield dbl
         finally:
-            ops.attn_step_sublayer_f16x2, ops.mlp_step_sublayer_f16x2, ops.gemm, ops.attention_step = saved
+            ops.gemm, ops.attention_step = saved
 
 
 @pytest.fixture()
@@ -190,7 +149,7 @@ def test_env_switch():
         assert r.stdout.strip() == want, (value, r.stdout, r.stderr)
 
 
-# ---------------------------------------------------------------- flag plumbing and plane scratch (functional.attn_step_f16x2 / mlp_step_f16x2)
+# ---------------------------------------------------------------- flag plumbing and plane scratch (functional.attn_step / mlp_step)
 def _step_once(d, rows, Lq, heads=4):
     from afft_amd import functional as F_
     g = torch.Generator().manual_seed(d + rows)
@@ -199,9 +158,9 @@ def _step_once(d, rows, Lq, heads=4):
     past = 2
     caches = torch.zeros(2, rows // Lq, past + Lq, d)
     with _installed() as dbl, torch.no_grad():
-        y, probs = F_.attn_step_f16x2(x, torch.ones(d), torch.zeros(d), r(d, 3 * d), r(3 * d), r(d, d), r(d), Lq, heads, 1e-5, True, caches[0],
-                                      caches[1], past, False)
-        y = F_.mlp_step_f16x2(y, torch.ones(d), torch.zeros(d), r(d, 4 * d), r(4 * d), r(4 * d, d), r(d), 1e-5, "tanh", True)
+        y, probs = F_.attn_step(x, torch.ones(d), torch.zeros(d), r(d, 3 * d), r(3 * d), r(d, d), r(d), Lq, heads, 1e-5, True, caches[0],
+                                caches[1], past, False)
+        y = F_.mlp_step(y, torch.ones(d), torch.zeros(d), r(d, 4 * d), r(4 * d), r(4 * d, d), r(d), 1e-5, "tanh", True)
     assert probs is None and y.shape == (rows, d) and torch.isfinite(y).all()
     assert len(dbl.attn) == len(dbl.mlp) == 1 and dbl.steps == 0
     return dbl.attn[0], dbl.mlp[0]
@@ -251,6 +210,6 @@ def test_widths_off_the_64_grid_take_the_call_by_call_step(rt_state):
     r = lambda *s: 0.02 * torch.randn(*s, generator=g)      # noqa: E731
     caches = torch.zeros(2, rows, 3, d)
     with _installed() as dbl, torch.no_grad():
-        y, _ = F_.attn_step_f16x2(torch.randn(rows, d, generator=g), torch.ones(d), torch.zeros(d), r(d, 3 * d), r(3 * d), r(d, d), r(d), 1, 2, 1e-5,
-                                  True, caches[0], caches[1], 2, False)
+        y, _ = F_.attn_step(torch.randn(rows, d, generator=g), torch.ones(d), torch.zeros(d), r(d, 3 * d), r(3 * d), r(d, d), r(d), 1, 2, 1e-5,
+                            True, caches[0], caches[1], 2, False)
     assert dbl.attn == [] and dbl.steps == 1 and torch.isfinite(y).all()

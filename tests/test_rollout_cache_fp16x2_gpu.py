@@ -1,5 +1,5 @@
-"""GPU: the cached roll-out in the 'fp16x2' precision (runtime.kv_cache_fp16x2: GPT2Block.forward_step -> functional.attn_step_f16x2 /
-mlp_step_f16x2 -> afft_attn_step_sublayer_fwd / afft_mlp_sublayer_fwd) at model level: against the reference's golden of the tiny roll-out
+"""GPU: the cached roll-out in the 'fp16x2' precision (runtime.kv_cache_fp16x2: GPT2Block.forward_step -> functional.attn_step /
+mlp_step -> afft_attn_step_sublayer_fwd / afft_mlp_sublayer_fwd) at model level: against the reference's golden of the tiny roll-out
 configuration (t2_roll, fp_output_len = 3) within the 1e-3 tests/test_model_gpu.py applies to this precision (2e-3 with every one-pass
 site forced on, as its test_fp16x2_one_pass_sites_on_the_small_goldens), switch on against switch off, once at the full predictor width
 with the GEMM trace read as test_fp16x2_forward_full_size reads it, and through evaluate.collect_logits.  The golden holds no temporal

@@ -1,5 +1,5 @@
 """Build-container test of the HOST logic of the roll-out that trains through the key / value cache (runtime.kv_cache_train,
-BaseFuturePredictor._rollout_cached_train, GPT2Model.forward_step_train, functional.AttnStepSublayer, KVCache's gradient twin) on CPU
+BaseFuturePredictor._rollout_cached, GPT2Model.forward_step_train, functional.AttnSublayer with `cache`, KVCache's gradient twin) on CPU
 tensors, with tests/cpu_ops_step_train.py standing in for the C-ABI wrappers: when the path engages, which rows reach the QKV GEMM, and
 that loss, input gradient and every parameter gradient are the recompute's.  What the kernels compute is tested on the GPU."""
 import pytest

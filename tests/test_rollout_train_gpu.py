@@ -1,5 +1,5 @@
 """GPU: the roll-out of the future predictor TRAINED through the key / value cache (runtime.kv_cache_train, BaseFuturePredictor.
-_rollout_cached_train, GPT2Model.forward_step_train, functional.AttnStepSublayer, afft_attention_step_bwd) at model level: outputs and the
+_rollout_cached, GPT2Model.forward_step_train, functional.AttnSublayer with `cache`, afft_attention_step_bwd) at model level: outputs and the
 gradient of every parameter of the tiny roll-out configuration (t2_roll, fp_output_len = 3) against the recompute, against the oracle under
 torch autograd and against the reference's golden, within the bars tests/test_model_gpu.py applies to the recompute (fp32 1e-3; bf16 2e-2
 on outputs, 2.5e-2 on gradients); once at the real head size; and one training step with dropout through parallel.Trainer."""
