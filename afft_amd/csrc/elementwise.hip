@@ -859,9 +859,13 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(int act, const float* __re
       case AFFT_ACT_GELU_TANH: dp = g * dgelu_tanh_f(p); break;
       case AFFT_ACT_RELU: dp = p > 0.f ? g : 0.f; break;
       case AFFT_ACT_SIGMOID_GATE: {
-        const float sg = 1.0f / (1.0f + __expf(-p));
+        // sigmoid(p) and 1 - sigmoid(p) = sigmoid(-p) from e = exp(-|p|) in (0, 1]: nothing overflows, and the small one of the
+        // two keeps its relative accuracy (1 - sg rounds to 0 from p = 17 on, which made dpre exactly 0 there)
+        const float e = __expf(-fabsf(p));
+        const float big = 1.0f / (1.0f + e), small = e * big;
+        const float sg = p >= 0.f ? big : small;
         const float a = aux[(int64_t)r * ldaux + c];
-        dp = g * a * sg * (1.0f - sg);
+        dp = g * a * big * small;
         if (daux) daux[(int64_t)r * ldda + c] = g * sg;
         break;
       }

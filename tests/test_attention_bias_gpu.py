@@ -13,6 +13,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(__file__))
 from helpers import GOLDEN, edge_error, rel_l2  # noqa: E402
+from kernel_doubles import mix32  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -48,15 +49,6 @@ def keep_mask(key, p, nseq, L):
     from afft_amd import dropout as D_
     if D_._salt is not None:
         key ^= int(D_._salt.item()) & 0xFFFFFFFF
-    M = np.uint64(0xFFFFFFFF)
-
-    def mix32(x):
-        x = x ^ (x >> np.uint64(16))
-        x = (x * np.uint64(0x7feb352d)) & M
-        x = x ^ (x >> np.uint64(15))
-        x = (x * np.uint64(0x846ca68b)) & M
-        return x ^ (x >> np.uint64(16))
-
     idx = np.arange(nseq * H * L * L, dtype=np.uint64)
     keep = mix32(mix32(idx) ^ np.uint64(key)) >= np.uint64(int(p * 4294967296.0))
     return torch.from_numpy(keep.reshape(nseq, H, L, L))

@@ -1069,40 +1069,7 @@ def test_sgd_runs_equals_sgd_over_the_same_ranges():
 
 def test_mse_and_elementwise():
     from afft_amd import ops
-    rows, d = 45, 64
-    a, b = rnd(rows, d, seed=1), rnd(rows, d, seed=2)
-    ls = torch.zeros(1, device=dev())
-    da = torch.full((rows, d), 2.0 ** -10, device=dev())
-    db = torch.zeros(rows, d, device=dev())
-    gs = 1.0 / (rows * d)
-    ops.mse(a.to(dev()), b.to(dev()), gs, ls, da, db)
-    torch.cuda.synchronize()
-    assert abs(float(ls) - float(((a - b) ** 2).sum())) < 1e-3
-    assert rel_l2(da.cpu() - 2.0 ** -10, 2 * gs * (a - b)) < 1e-4
-    assert rel_l2(db.cpu(), -2 * gs * (a - b)) < 1e-5
-
-    # cast + transpose with padding
-    W = rnd(70, 24, seed=3)
-    w16 = torch.zeros(70, 64, dtype=torch.bfloat16, device=dev())
-    wt16 = torch.zeros(24, 128, dtype=torch.bfloat16, device=dev())
-    ops.cast(W.to(dev()), w16, wt16, zero_pad=True)
-    torch.cuda.synchronize()
-    assert torch.equal(w16[:, :24].cpu(), W.to(torch.bfloat16)) and float(w16[:, 24:].float().abs().max()) == 0
-    assert torch.equal(wt16[:, :70].cpu(), W.t().to(torch.bfloat16)) and float(wt16[:, 70:].float().abs().max()) == 0
-
-    # token assembly (SA-Fuser, models/fusion.py:338-352)
-    B, T, dd, Mn = 3, 4, 64, 4
-    feats = [rnd(B * T, dd, seed=10 + i) for i in range(Mn)]
-    tok = rnd(T, dd, seed=20)
-    emb = rnd(Mn + 1, dd, seed=21)
-    X = torch.empty(B * T, Mn + 1, dd, device=dev())
-    ops.assemble_tokens([f.to(dev()) for f in feats], tok.to(dev()), dd, emb.to(dev()), B * T, T, dd, X)
-    ref = torch.stack([tok.repeat(B, 1)] + feats, dim=1) + emb
-    assert torch.equal(X.cpu(), ref)
-    X2 = torch.empty(B * T, Mn + 1, dd, device=dev())
-    ops.assemble_tokens([f.to(dev()) for f in feats], tok[:1].contiguous().to(dev()), 0, None, B * T, T, dd, X2)
-    assert torch.equal(X2.cpu(), torch.stack([tok[:1].expand(B * T, dd)] + feats, dim=1))
-
+    # the MSE, cast, token-assembly, group-sum and periodic-table kernels: tests/test_elementwise_gpu.py, one parametrized test each
     # column sums (bias gradients)
     src = rnd(333, 130, seed=30)
     out = torch.full((130,), 2.0, device=dev())
@@ -1110,37 +1077,6 @@ def test_mse_and_elementwise():
     assert rel_l2(out.cpu() - 2.0, bfr(src).sum(0)) < 1e-4
     ops.colsum(src.to(dev()), out, accumulate=False)
     assert rel_l2(out.cpu(), src.sum(0)) < 1e-5
-
-    # token means of the fusers without a modality token, and their backward (a broadcast)
-    xg = rnd(6 * 5, 72, seed=34)
-    yg = torch.empty(6, 72, device=dev())
-    ops.group_sum(xg.to(dev()), 6, 5, 72, 1.0 / 5, yg)
-    assert rel_l2(yg.cpu(), xg.view(6, 5, 72).mean(1)) < 1e-6
-    dxg = torch.empty(6 * 5, 72, device=dev())
-    ops.group_bcast(yg, 6, 5, 72, 0.2, dxg)
-    assert torch.allclose(dxg.cpu().view(6, 5, 72), (yg.cpu() * 0.2)[:, None, :].expand(6, 5, 72))
-
-    # periodic tables
-    x = rnd(B * T, dd, seed=31)
-    tab = rnd(T, dd, seed=32)
-    y = torch.empty(B * T, dd, device=dev())
-    ops.add_rows_periodic(x.to(dev()), tab.to(dev()), T, y)
-    assert torch.equal(y.cpu(), x + tab.repeat(B, 1))
-    acc = torch.ones(T, dd, device=dev())
-    ops.reduce_rows_periodic(x.to(dev()), T, acc)
-    assert rel_l2(acc.cpu() - 1.0, x.view(B, T, dd).sum(0)) < 1e-5
-    # strided source rows (token 0 of every frame), period 1 and period T; ragged row count (rows % period != 0)
-    xs = rnd(B * T, 3 * dd, seed=33)
-    acc1 = torch.zeros(1, dd, device=dev())
-    ops.reduce_rows_periodic(xs.to(dev())[:, :dd], 1, acc1)
-    assert rel_l2(acc1.cpu()[0], xs[:, :dd].sum(0)) < 1e-5
-    accT = torch.zeros(T, dd, device=dev())
-    ops.reduce_rows_periodic(xs.to(dev())[:, :dd], T, accT)
-    assert rel_l2(accT.cpu(), xs[:, :dd].reshape(B, T, dd).sum(0)) < 1e-5
-    accR = torch.zeros(T, dd, device=dev())
-    ops.reduce_rows_periodic(x.to(dev())[:B * T - 3], T, accR)
-    refR = torch.cat([x[:B * T - 3], torch.zeros(3, dd)]).view(B, T, dd).sum(0)
-    assert rel_l2(accR.cpu(), refR) < 1e-5
 
     # gradient clipping by global norm, coefficient kept on the device
     gfl = rnd(5000 + 7, seed=43) * 3.0
