@@ -3,7 +3,12 @@ verb and noun scores by the class-mapping matrices, as one row-softmax kernel an
 that are already on the device (the reference does this in numpy on host copies), followed by the reference's accuracy
 bookkeeping (top-1 / top-5 / mean top-5 recall per verb, noun and action: challenge.py:94-106,161-193, common/utils.py:19-56)
 on ONE host copy of the three score matrices.  Pinned by tests/golden/m0_marginalize.npz, produced by the reference's own
-``marginalize_verb_noun`` on a stub dataset object."""
+``marginalize_verb_noun`` on a stub dataset object.
+
+The second half of the reference's file (challenge.py:243-434) follows below: late fusion of several runs' stored logits and the
+EPIC-KITCHENS-100 ``test.json`` / ``submit.zip``.  Its one hot spot, the 100 best of 3806 action scores per segment, is
+``ops.topk_rows`` (afft_topk_rows, include/afft_hip.h); a combination of complete runs is one ``ops.weighted_sum_fwd`` per space.
+Pinned by tests/golden/s0_submission.npz, produced by the reference's own ``get_struct_outputs_per_dataset``."""
 from __future__ import annotations
 
 from typing import Dict, Tuple
@@ -172,3 +177,230 @@ def get_epic_marginalize_verb_noun(resdir: str, dataset):
             res_action = val
     assert res_action is not None, 'Can not find logits/action in h5.'
     return marginalize_verb_noun(res_action, dataset)
+
+
+# ----------------------------------------------------------------------------- late fusion and the EPIC-KITCHENS-100 submission
+# challenge.py:225-434.  The reference keeps the dataset object in a module global that its __main__ block sets; here every function
+# takes it as the keyword `dataset` and falls back to this attribute.
+dataset = None
+
+
+def _dataset(ds):
+    ds = ds if ds is not None else dataset
+    if ds is None:
+        raise ValueError('a dataset object is needed: pass dataset=..., or set afft_amd.challenge.dataset')
+    return ds
+
+
+def _on_device(x) -> torch.Tensor:
+    """fp32 tensor on the GPU (there is no CPU path); what is there already stays where it is"""
+    x = torch.as_tensor(x)
+    if not x.is_cuda:
+        x = x.cuda()
+    return x if x.dtype == torch.float32 else x.float()
+
+
+def _uids(ds, uid_key):
+    return [str(u) for u in ds.df[uid_key].values]
+
+
+def print_accuracies_epic(metrics: dict, prefix: str = ''):
+    """challenge.py:225-240"""
+    groups = [('Accuracies', ('vtop1', 'vtop5', 'ntop1', 'ntop5', 'atop1', 'atop5')), ('Mean top 5', ('vmt5r', 'nmt5r', 'amt5r')),
+              ('Mean top 5 many shot', ('vmt5r_ms', 'nmt5r_ms', 'amt5r_ms'))]
+    if 'vmt5r_tail' in metrics:      # the tail / unseen numbers come as one group (compute_accuracies_epic)
+        groups += [('Mean top 5 tail', ('vmt5r_tail', 'nmt5r_tail', 'amt5r_tail')),
+                   ('Mean top 5 unseen', ('vmt5r_unseen', 'nmt5r_unseen', 'amt5r_unseen'))]
+    for title, keys in groups:
+        print(f'[{prefix}] {title} verb/noun/action: ' + ' '.join(f'{metrics[k]:.1f}' for k in keys))
+
+
+def top_actions(action_scores, k: int = 100):
+    """(vals fp32 [N, k'], idx int32 [N, k']) as numpy arrays, k' = min(k, C): per row the k' best scores, best first, in the order
+    include/afft_hip.h defines for afft_topk_rows (among equal scores the lower class first, NaN last).  The scores go to the device
+    if they are not there; k' columns per row come back.  (The reference's np.argpartition(row, -100) raises for C < 100.)"""
+    x = _on_device(action_scores)
+    x = x.reshape(-1, x.shape[-1])
+    x = x if x.stride(-1) == 1 else x.contiguous()
+    vals, idx = ops.topk_rows(x, min(int(k), x.shape[1]))
+    return vals.cpu().numpy(), idx.cpu().numpy()
+
+
+def _concat_with_uids(scores, dataset, uid_key):
+    """challenge.py:243-249: [verb, noun, action] matrices -> three {uid: row} dicts; row i belongs to the i-th uid of dataset.df (a
+    matrix with fewer rows covers the first uids only)"""
+    uids = _uids(dataset, uid_key)
+    return [dict(zip(uids, per_space)) for per_space in scores]
+
+
+def _normalize_scores(scores, p):
+    """challenge.py:252-260: every row divided by its p-norm + 0.000001"""
+    return [{uid: row / (np.linalg.norm(row, ord=p, axis=-1) + 0.000001) for uid, row in per_space.items()} for per_space in scores]
+
+
+def contains_list_or_tuple(items) -> bool:
+    return any(isinstance(el, (list, tuple)) for el in items)
+
+
+def read_all_single_models(resdirs, uid_key='narration_id', normalize_before_combine=None, dataset=None):
+    """challenge.py:271-284: per run directory the three {uid: row} dicts of its verb / noun / action scores"""
+    ds = _dataset(dataset)
+    all_scores = []
+    for resdir in resdirs:
+        accuracies, scores = get_epic_marginalize_verb_noun(resdir, ds)
+        scores = _concat_with_uids(scores, ds, uid_key)
+        print_accuracies_epic(accuracies, prefix=resdir)
+        if normalize_before_combine is not None:      # AVT does not normalise
+            scores = _normalize_scores(scores, p=normalize_before_combine)
+        all_scores.append(scores)
+    return all_scores
+
+
+MAX_DEVICE_RUNS = 8      # afft_weighted_sum_fwd adds up to 8 matrices (include/afft_hip.h)
+
+
+def _combine_on_device(per_run, uids, weight):
+    """sum_i weight[i] * run_i for runs that all cover `uids`: one ops.weighted_sum_fwd over the [N, C] matrices"""
+    xs = [_on_device(np.stack([run[u] for u in uids])) for run in per_run]
+    w = torch.tensor([[float(x) for x in weight]], dtype=torch.float32).repeat(len(uids), 1).to(xs[0].device)
+    out = torch.empty_like(xs[0])
+    ops.weighted_sum_fwd(xs, w, out)
+    return dict(zip(uids, out.cpu().numpy()))
+
+
+def _combine_per_uid(per_run, weight):
+    """the reference's union: every uid any run has, summed over the runs that have it (in the order of their first appearance)"""
+    combined = {}
+    for uid in dict.fromkeys(u for run in per_run for u in run):
+        parts = [run[uid] * weight[i] for i, run in enumerate(per_run) if uid in run]
+        combined[uid] = np.sum(np.stack(parts), axis=0)
+    return combined
+
+
+def get_epic_marginalize_late_fuse(resdirs, weights=1.0, mp_best_weights=None, n_best=5, uid_key='narration_id', dataset=None):
+    """challenge.py:287-351: weighted sum of the verb / noun / action scores of several runs.  weights: one float (every run), one
+    weight per run, or a list of such lists (each is combined and scored; the last one's combination is returned).  mp_best_weights
+    (optional list, updated in place) keeps the n_best (amt5r, weights) pairs seen, ascending.  Returns (accuracies, combined,
+    dataset) with combined = three {uid: row} dicts.  When every run covers all rows of dataset.df and there are at most
+    MAX_DEVICE_RUNS of them, a space is combined by one ops.weighted_sum_fwd on the device; otherwise per uid in numpy."""
+    ds = _dataset(dataset)
+    if not isinstance(resdirs, list):
+        resdirs = [resdirs]
+    if isinstance(weights, float):
+        weights = [[weights] * len(resdirs)]
+    elif not isinstance(weights, np.ndarray) and not contains_list_or_tuple(weights):
+        assert len(weights) == len(resdirs)
+        weights = [weights]
+    else:
+        assert all(len(weight) == len(resdirs) for weight in weights)
+    mp_best_weights = [] if mp_best_weights is None else mp_best_weights
+    all_scores = read_all_single_models(resdirs, uid_key=uid_key, dataset=ds)
+    uids = _uids(ds, uid_key)
+    full = len(resdirs) <= MAX_DEVICE_RUNS and all(len(per_space) == len(uids) for run in all_scores for per_space in run)
+    accuracies, combined = None, None
+    for weight in weights:
+        combined = []
+        for space in range(3):      # verb / noun / action
+            per_run = [run[space] for run in all_scores]
+            combined.append(_combine_on_device(per_run, uids, weight) if full else _combine_per_uid(per_run, weight))
+        # the accuracies need matrices again, in the order of the annotations
+        accuracies = compute_accuracies_epic([np.array([per_space[u] for u in uids]) for per_space in combined], ds)
+        print_accuracies_epic(accuracies, prefix=f'combined with {weight}')
+        metric = accuracies['amt5r']
+        if len(mp_best_weights) == 0 or metric > mp_best_weights[0][0]:
+            at = sum(1 for m, _ in mp_best_weights if m <= metric)
+            mp_best_weights.insert(at, (metric, weight))
+            if len(mp_best_weights) > n_best:
+                mp_best_weights.pop(0)
+    return accuracies, combined, ds
+
+
+def struct_outputs_from_scores(scores, dataset, uid_key='narration_id', k=100, uids=None):
+    """The `results` dict of challenge.py:358-377 from scores = [verb, noun, action], arrays or device tensors whose rows follow
+    dataset.df (or `uids`, where given).  Per uid: 'verb' / 'noun' {str(class): score} over every class; 'action' {"verb,noun": score}
+    for the k best actions, inserted best first (top_actions: of the action matrix only k columns per row leave the device).  Every
+    value is a Python float."""
+    uids = _uids(dataset, uid_key) if uids is None else list(uids)
+    to_verb_noun = {action: pair for pair, action in dataset.verb_noun_to_action.items()}
+    verb, noun = (s.detach().cpu().numpy() if isinstance(s, torch.Tensor) else np.asarray(s) for s in scores[:2])
+    vals, idx = top_actions(scores[2], k)
+    assert len(verb) == len(noun) == len(vals) == len(uids), 'one row per uid in each space'
+    names = {}      # class -> "verb,noun", built for the classes that occur
+    results = {}
+    for r, uid in enumerate(uids):
+        action = {}
+        for j, v in zip(idx[r].tolist(), vals[r].tolist()):
+            if j not in names:
+                names[j] = ','.join(str(el) for el in to_verb_noun[j])
+            action[names[j]] = v
+        results[uid] = {'verb': {str(j): v for j, v in enumerate(verb[r].tolist())},
+                        'noun': {str(j): v for j, v in enumerate(noun[r].tolist())},
+                        'action': action}
+    return results
+
+
+def get_struct_outputs_per_dataset(resdirs, weights, uid_key='narration_id', dataset=None):
+    """challenge.py:354-398: the submission structure {'version', 'challenge', 'results'}.  results is keyed in dataset.df order (the
+    uids that have scores), then the rows of dataset.discarded_df that are not yet present, with zero scores for every verb and noun
+    class and for the actions '0,0' .. '0,99'."""
+    _, combined, ds = get_epic_marginalize_late_fuse(resdirs, weights, uid_key=uid_key, dataset=dataset)
+    uids = [u for u in dict.fromkeys(_uids(ds, uid_key)) if u in combined[0]]
+    results = struct_outputs_from_scores([np.stack([per_space[u] for u in uids]) for per_space in combined], ds, uid_key=uid_key,
+                                         uids=uids)
+    if ds.discarded_df is not None:
+        for _, row in ds.discarded_df.iterrows():
+            uid = str(row[uid_key])
+            if uid in results:
+                continue
+            results[uid] = {'verb': {str(j): 0.0 for j in range(len(ds.verb_classes))},
+                            'noun': {str(j): 0.0 for j in range(len(ds.noun_classes))},
+                            'action': {f'0,{j}': 0.0 for j in range(100)}}
+    return {'version': f'{ds.version}', 'challenge': ds.challenge_type, 'results': results}
+
+
+def package_results_for_submission_ek100(resdirs, weights, sls=(1, 4, 3), dataset=None, output_dir=None):
+    """challenge.py:401-414: <output_dir>/test.json and <output_dir>/submit.zip (test.json at its top level); sls = the supervision
+    levels (pretraining, training labels, training data) the challenge asks for.  output_dir defaults to LOGITS_DIR.  Returns the dict."""
+    import json  # noqa: PLC0415
+    import os  # noqa: PLC0415
+    import zipfile  # noqa: PLC0415
+    res = get_struct_outputs_per_dataset(resdirs, weights, uid_key='narration_id', dataset=dataset)
+    res['sls_pt'], res['sls_tl'], res['sls_td'] = sls[0], sls[1], sls[2]
+    output_dir = LOGITS_DIR if output_dir is None else output_dir
+    print(f'Saving outputs to {output_dir}')
+    os.makedirs(output_dir, exist_ok=True)
+    path = os.path.join(output_dir, 'test.json')
+    with open(path, 'w') as fout:
+        json.dump(res, fout, indent=4)      # every value is a Python number already: no numpy encoder
+    with zipfile.ZipFile(os.path.join(output_dir, 'submit.zip'), 'w', zipfile.ZIP_DEFLATED) as z:
+        z.write(path, arcname='test.json')
+    return res
+
+
+def generate_test_json(args, dataset=None):
+    """challenge.py:417-428: args.models = run directories under LOGITS_DIR, args.weights = one weight per model"""
+    import os  # noqa: PLC0415
+    models = args.models if isinstance(args.models, list) else [args.models]
+    weights = args.weights if isinstance(args.weights, list) else [args.weights]
+    return package_results_for_submission_ek100([os.path.join(LOGITS_DIR, m) for m in models], [float(w) for w in weights],
+                                                dataset=dataset)
+
+
+def parse_args(argv=None):
+    import argparse  # noqa: PLC0415
+    parser = argparse.ArgumentParser(description='EPIC-KITCHENS-100 test.json / submit.zip from stored logits')
+    parser.add_argument('--prefix_h5', type=str, default='test', choices=['test', 'val'], help='Prefix of h5 file to be selected')
+    parser.add_argument('--models', type=str, nargs='+', required=True, help='List of models to be selected')
+    parser.add_argument('--weights', type=str, nargs='+', required=True, help='List of weights for selected models')
+    return parser.parse_args(argv)
+
+
+if __name__ == '__main__':
+    from afft_amd import _hydra_compat  # noqa: PLC0415
+    _args = parse_args()
+    PREFIX_H5 = _args.prefix_h5
+    _get_dataset = getattr(_hydra_compat, 'get_dataset', None)
+    if _get_dataset is None:
+        raise SystemExit('afft_amd.challenge: no dataset loader here. Build the dataset object (datasets/epic_kitchens.py of the '
+                         'reference) and call generate_test_json(args, dataset=...) or package_results_for_submission_ek100(...).')
+    generate_test_json(_args, dataset=_get_dataset())

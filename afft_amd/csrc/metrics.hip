@@ -1,5 +1,5 @@
 // Training / evaluation metrics on the device: the rank of the label's score among the scores of its row, and the integer
-// counters of the mean top-k recall.  Semantics: common/runner.py:54-92 (MixUp adjustment of the logits, acc1 / acc5 through
+// counters of the mean top-k recall; the row-wise sorted top-k of the submission path (afft_topk_rows).  Semantics: common/runner.py:54-92 (MixUp adjustment of the logits, acc1 / acc5 through
 // common/utils.py:59-86) and common/metric_tracking.py:22-29 (per-class true positives / counts); tie rule and the handling
 // of labels outside [0, C) are this project's (include/afft_hip.h).
 #include "common.h"
@@ -128,7 +128,66 @@ __global__ __launch_bounds__(256) void recall_accumulate_kernel(const int32_t* _
   if (rank[r] < k) atomicAdd(tps + l, 1);
 }
 
+// Sort key of one score: high word = an unsigned image of the float that orders as the ORDER of include/afft_hip.h says (-0.0 folded
+// onto +0.0 first, NaN -> 0, below the image 0x007fffff of -inf), low word = ~class, so that among equal scores the LOWER class has the
+// LARGER key.  Integer arithmetic only: nothing here depends on the denormal mode.  Key 0 pads the row: below every real key.
+__device__ __forceinline__ uint64_t topk_key(float v, int c) {
+  unsigned u = __float_as_uint(v);
+  if (u == 0x80000000u) u = 0u;
+  const unsigned img = (u & 0x7fffffffu) > 0x7f800000u ? 0u : (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((uint64_t)img << 32) | (uint64_t)(~(unsigned)c);
+}
+
+// One workgroup per row: the row as P = 2^p >= C keys in LDS, a descending bitonic sort over all P, the first k written out.
+// The values are read back from the row itself, so that the sign of a zero and the payload of a NaN survive.
+__global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict__ xs, int64_t ldx, int C, int P, int k, int vec,
+                                                        float* __restrict__ vals, int64_t ldv, int32_t* __restrict__ idx, int64_t ldi) {
+  extern __shared__ uint64_t topk_keys[];
+  const int64_t row = blockIdx.x;
+  const float* x = xs + row * ldx;
+  walk_row(x, C, vec != 0, [&](int c, float v) { topk_keys[c] = topk_key(v, c); });
+  for (int c = C + threadIdx.x; c < P; c += 256) topk_keys[c] = 0;
+  __syncthreads();
+  for (int span = 2; span <= P; span <<= 1) {
+    for (int j = span >> 1; j > 0; j >>= 1) {
+      for (int t = threadIdx.x; t < (P >> 1); t += 256) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));      // the lower element of pair t: bit j clear; i + j < P
+        const uint64_t a = topk_keys[i], b = topk_keys[i + j];
+        if ((i & span) == 0 ? a < b : a > b) { topk_keys[i] = b; topk_keys[i + j] = a; }
+      }
+      __syncthreads();
+    }
+  }
+  for (int j = threadIdx.x; j < k; j += 256) {      // k <= C: the first k keys are real ones, their class lies in [0, C)
+    const int c = (int)~(unsigned)topk_keys[j];
+    idx[row * ldi + j] = c;
+    vals[row * ldv + j] = x[c];
+  }
+}
+
 }  // namespace
+
+extern "C" int afft_topk_rows(const float* x, int64_t ldx, int32_t rows, int32_t C, int32_t k, float* vals, int64_t ldv, int32_t* idx,
+                              int64_t ldi, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  AFFT_CHECK(rows >= 1, "topk_rows: rows >= 1 (got %d)", rows);
+  AFFT_CHECK(k >= 1 && k <= C && C <= AFFT_TOPK_MAX_C, "topk_rows: 1 <= k <= C <= %d (got k = %d, C = %d)", AFFT_TOPK_MAX_C, k, C);
+  AFFT_CHECK(ldx >= C, "topk_rows: ldx %lld < C = %d", (long long)ldx, C);
+  AFFT_CHECK(ldv >= k, "topk_rows: ldv %lld < k = %d", (long long)ldv, k);
+  AFFT_CHECK(ldi >= k, "topk_rows: ldi %lld < k = %d", (long long)ldi, k);
+  AFFT_CHECK(x && vals && idx, "topk_rows: null x / vals / idx");
+  int P = 1;
+  while (P < C) P <<= 1;
+  const size_t lds = (size_t)P * sizeof(uint64_t);
+  static std::atomic<uint64_t> attr_done{0};
+  if (lds > 48 * 1024)      // raised once to what the limit needs: the attribute belongs to the kernel, not to the launch
+    if (int rc = afft_ensure_dynamic_lds(reinterpret_cast<const void*>(topk_rows_kernel), (size_t)AFFT_TOPK_MAX_C * sizeof(uint64_t), &attr_done))
+      return rc;
+  const int vec = ((uintptr_t)x & 15) == 0 && (ldx & 3) == 0;
+  hipLaunchKernelGGL(topk_rows_kernel, dim3(rows), dim3(256), lds, stream, x, ldx, C, P, k, vec, vals, ldv, idx, ldi);
+  AFFT_LAUNCH_CHECK();
+  return 0;
+}
 
 extern "C" int afft_label_rank(const float* logits, int64_t row_stride, int32_t rows, int32_t C, const int64_t* labels,
                                const float* soft, int64_t lds, int32_t k, float acc_scale, int32_t* rank, int64_t* label_out,

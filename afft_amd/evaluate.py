@@ -59,6 +59,16 @@ def collect_logits(model, data_loader: Iterable, device, precision: Optional[str
 
 
 @torch.no_grad()
+def top_predictions(model, data_loader: Iterable, device, k: int = 5, precision: Optional[str] = None):
+    """(key, vals fp32 [N, k'], idx int32 [N, k']) ON THE DEVICE, k' = min(k, classes): the k' best classes of every clip, best first
+    (collect_logits, then ops.topk_rows: among equal logits the lower class first, include/afft_hip.h)."""
+    from . import ops  # noqa: PLC0415
+    key, logits = collect_logits(model, data_loader, device, precision=precision)
+    vals, idx = ops.topk_rows(logits, min(int(k), logits.shape[1]))
+    return key, vals, idx
+
+
+@torch.no_grad()
 def evaluate_scores(model, class_mappings, data_loader: Iterable, device, to_prob: bool = True,
                     precision: Optional[str] = None) -> Dict[str, np.ndarray]:
     """verb / noun / action score matrices of test.py:evaluate -> challenge.marginalize_verb_noun (:196-210), computed on

@@ -903,6 +903,24 @@ def recall_accumulate(rank: Tensor, label: Tensor, k: int, tps: Tensor, nums: Te
     L.check(L.lib().afft_recall_accumulate(_p(rank), _p(label), rows, tps.numel(), k, _p(tps), _p(nums), _stream()), "recall_accumulate")
 
 
+def topk_rows(x: Tensor, k: int, vals: Optional[Tensor] = None, idx: Optional[Tensor] = None):
+    """x fp32 [rows, C] VIEW with unit column stride, C <= TOPK_MAX_C; returns (vals fp32 [rows, k], idx int32 [rows, k]): the k best
+    classes of every row, best first, in the total order of include/afft_hip.h (the lower class first among equal scores, NaN last).
+    vals / idx may be given (wider buffers keep their columns >= k)."""
+    if x.dtype != torch.float32:
+        raise TypeError(f"afft_amd: topk_rows takes fp32 scores, got {x.dtype}")
+    ldx = _rowmajor(x, "x")
+    rows, Cc = x.shape
+    if vals is None:
+        vals = torch.empty(rows, max(k, 0), dtype=torch.float32, device=x.device)
+    if idx is None:
+        idx = torch.empty(rows, max(k, 0), dtype=torch.int32, device=x.device)
+    assert vals.dtype == torch.float32 and idx.dtype == torch.int32 and vals.shape[0] == idx.shape[0] == rows
+    L.check(L.lib().afft_topk_rows(_p(x), ldx, rows, Cc, k, _p(vals), _rowmajor(vals, "vals"), _p(idx), _rowmajor(idx, "idx"), _stream()),
+            "topk_rows")
+    return vals, idx
+
+
 def zero_mask_frames(x: Tensor, k: int, key: int):
     """x fp32 [B, T, ...] contiguous: zero k random frames of every clip in place."""
     assert x.is_contiguous() and x.dtype == torch.float32 and x.dim() >= 2

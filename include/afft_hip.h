@@ -592,6 +592,21 @@ int afft_label_rank(const float* logits, int64_t row_stride, int32_t rows, int32
  * every run, whatever the order (no float atomics anywhere in this library).  One launch. */
 int afft_recall_accumulate(const int32_t* rank, const int64_t* label, int32_t rows, int32_t C, int32_t k, int32_t* tps, int32_t* nums,
                            void* stream);
+/* Row-wise sorted top-k: the k best classes of every row, best first (the 100 best of 3806 action scores per segment of an
+ * EPIC-KITCHENS-100 submission, challenge.py:367-368, where the reference runs np.argpartition + sorted once per row on the host).
+ * Row r is read at x + r * ldx (ldx >= C: a view is walked where it lies, as afft_label_rank does).  For j < k:
+ *   idx[r * ldi + j]  = the class at position j of the row's order,   vals[r * ldv + j] = x[r, idx[r, j]] bit for bit.
+ * ORDER (this project's definition, the TIE RULE of afft_label_rank extended to a total order; numpy and torch.topk leave it open):
+ *   class a comes before class b when x[a] > x[b], or x[a] == x[b] and a < b;
+ *   -0.0 and +0.0 are equal (the lower index first); the stored value keeps its sign bit;
+ *   a NaN ranks below every number, -inf included; among NaNs the lower index comes first (the stored value keeps its payload).
+ * On a row without NaN this is the order afft_label_rank counts in: rank[r] < k implies idx[r, rank[r]] == label.
+ * rows >= 1 (no upper limit), 1 <= k <= C <= AFFT_TOPK_MAX_C, ldv >= k, ldi >= k, no null pointer.  Columns >= k of vals / idx are not
+ * written.  One workgroup per row sorts the whole row as 64-bit (score image, ~class) keys in LDS (8 bytes per key of the next power of
+ * two >= C: 64 KiB at the limit).  One launch; no allocation, no host sync, no scratch, no atomics: two runs give the same bits. */
+#define AFFT_TOPK_MAX_C 8192
+int afft_topk_rows(const float* x, int64_t ldx, int32_t rows, int32_t C, int32_t k, float* vals, int64_t ldv, int32_t* idx, int64_t ldi,
+                   void* stream);
 /* Token means of the fusers without a modality token (models/fusion.py:114-116 CMFuser: mean over the M tokens of a
  * frame; :207-210 T-SA-Fuser: mean over the M modality tokens of a frame position): x fp32 [G, S, W] contiguous,
  *   afft_group_sum:   y[g, :]     = scale * sum_s x[g, s, :]
