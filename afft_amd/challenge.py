@@ -315,6 +315,106 @@ def get_epic_marginalize_late_fuse(resdirs, weights=1.0, mp_best_weights=None, n
     return accuracies, combined, ds
 
 
+def device_sweep(xs, labels, weights, k=5, classes=None, sets_per_call=512):
+    """compute_accuracy of sum_i weights[j, i] * xs[i] for every weight set j, without any of the sums being formed: three float64
+    vectors of length nsets, (top-1, top-k, mean top-k recall) in percent.  xs: R <= MAX_DEVICE_RUNS score matrices [N, C] of one space
+    (arrays or device tensors; they go to the device once), labels [N] integer, weights [nsets, R].  Per chunk of sets_per_call sets:
+    one ops.fused_label_rank (the label's rank under every set of the chunk, counted while the runs' rows stream past), one
+    ops.rank_counts_sets, and one copy of the chunk's integer counters (2 hits and C true positives per set) to the host; the C class
+    counts come back once.  Nothing of width N * C leaves the device.  The numbers follow from the integer counts in float64, in the
+    order of operations of compute_accuracy: hits / N * 100, and the recall mean summed in ascending class order over the classes with
+    a row (restricted to `classes`, a {name: class id} subset, when given).  Labels outside [0, C) are never a hit, stay in the accuracy
+    denominators and out of the recall (device_accuracy's rule).  Ties rank as include/afft_hip.h says (the lower class index first); on
+    tie-free scores the three numbers are compute_accuracy's of the materialised combination, bit for bit."""
+    xs = [_on_device(x) for x in xs]
+    xs = [x.reshape(-1, x.shape[-1]) for x in xs]
+    if not 1 <= len(xs) <= MAX_DEVICE_RUNS:
+        raise ValueError(f'device_sweep takes 1 to {MAX_DEVICE_RUNS} runs, got {len(xs)}')
+    if any(x.shape != xs[0].shape for x in xs):
+        raise ValueError(f'every run must cover the same rows and classes, got {[tuple(x.shape) for x in xs]}')
+    if any(x.stride(-1) != 1 or x.stride(0) != xs[0].stride(0) for x in xs):
+        xs = [x.contiguous() for x in xs]
+    dev = xs[0].device
+    N, C = xs[0].shape
+    k = min(int(k), C)
+    w = torch.as_tensor(np.asarray(weights, dtype=np.float32).reshape(-1, len(xs))).to(dev)
+    nsets = w.shape[0]
+    lab = torch.as_tensor(np.asarray(labels).reshape(-1).astype(np.int64)).to(dev) if not isinstance(labels, torch.Tensor) \
+        else labels.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+    per_call = max(1, min(int(sets_per_call), nsets))
+    rank = torch.empty(per_call, N, dtype=torch.int32, device=dev)
+    hits = np.empty((nsets, 2), np.int64)
+    tps = np.empty((nsets, C), np.int64)
+    nums = None
+    for at in range(0, nsets, per_call):
+        m = min(per_call, nsets - at)
+        counters = torch.zeros(m * (2 + C) + C, dtype=torch.int32, device=dev)      # hits [m, 2] | tps [m, C] | nums [C]
+        ops.fused_label_rank(xs, w[at:at + m], lab, rank=rank[:m])
+        ops.rank_counts_sets(rank[:m], lab, C, k, counters[:2 * m], counters[2 * m:m * (2 + C)], counters[m * (2 + C):])
+        back = (counters if nums is None else counters[:m * (2 + C)]).cpu().numpy()
+        hits[at:at + m] = back[:2 * m].reshape(m, 2)
+        tps[at:at + m] = back[2 * m:m * (2 + C)].reshape(m, C)
+        if nums is None:
+            nums = back[m * (2 + C):].astype(np.int64)
+    seen = nums > 0
+    if classes is not None:
+        subset = np.zeros(C, dtype=bool)
+        subset[[int(c) for c in classes.values() if 0 <= int(c) < C]] = True
+        seen &= subset
+    top1 = hits[:, 0] / N * 100
+    topk = hits[:, 1] / N * 100
+    per_class = tps[:, seen] / nums[seen]
+    recall = np.asarray([sum(row.tolist()) / per_class.shape[1] * 100 if per_class.shape[1] else float('nan') for row in per_class])
+    return top1, topk, recall
+
+
+def late_fuse_sweep(resdirs, weights, mp_best_weights=None, n_best=5, uid_key='narration_id', dataset=None):
+    """The weight search of challenge.py:287-351 (get_epic_marginalize_late_fuse over a list of weight combinations, which the reference
+    runs under multiprocessing) with every combination scored on the device by device_sweep: one call per space (verb, noun, action),
+    no combination is materialised, and what comes back per combination is integer counters.  resdirs are read as
+    get_epic_marginalize_late_fuse reads them and weights takes the same forms under the same assertions.  Every run must cover all rows of
+    dataset.df and there may be at most MAX_DEVICE_RUNS of them: otherwise ValueError (get_epic_marginalize_late_fuse handles those, on
+    the host).  Returns a list with one accuracies dict per weight combination: the keys of compute_accuracies_epic without the many-shot
+    option (the *_ms entries are NaN).  mp_best_weights (optional list, updated in place) keeps the n_best (amt5r, weights) pairs seen,
+    ascending, by the rule of get_epic_marginalize_late_fuse.  Ties rank as include/afft_hip.h says (the lower class index first); on
+    tie-free scores every number is the one get_epic_marginalize_late_fuse reports for that combination."""
+    ds = _dataset(dataset)
+    if not isinstance(resdirs, list):
+        resdirs = [resdirs]
+    if isinstance(weights, float):
+        weights = [[weights] * len(resdirs)]
+    elif not isinstance(weights, np.ndarray) and not contains_list_or_tuple(weights):
+        assert len(weights) == len(resdirs)
+        weights = [weights]
+    else:
+        assert all(len(weight) == len(resdirs) for weight in weights)
+    if len(resdirs) > MAX_DEVICE_RUNS:
+        raise ValueError(f'late_fuse_sweep combines at most {MAX_DEVICE_RUNS} runs on the device, got {len(resdirs)}: use '
+                         f'get_epic_marginalize_late_fuse')
+    mp_best_weights = [] if mp_best_weights is None else mp_best_weights
+    all_scores = read_all_single_models(resdirs, uid_key=uid_key, dataset=ds)
+    uids = _uids(ds, uid_key)
+    if not all(len(per_space) == len(uids) for run in all_scores for per_space in run):
+        raise ValueError('late_fuse_sweep needs complete runs (every run covering all rows of dataset.df): use '
+                         'get_epic_marginalize_late_fuse, which sums such runs per uid')
+    table = np.asarray([[float(x) for x in weight] for weight in weights], dtype=np.float32)
+    results = [{} for _ in weights]
+    for space, (short, key) in enumerate((('v', 'verb'), ('n', 'noun'), ('a', 'action'))):
+        xs = [np.stack([run[space][u] for u in uids]) for run in all_scores]
+        top1, top5, mt5r = device_sweep(xs, getattr(ds.df, f'{key}_class').values, table)
+        for j, res in enumerate(results):
+            res[f'{short}top1'], res[f'{short}top5'], res[f'{short}mt5r'] = float(top1[j]), float(top5[j]), float(mt5r[j])
+            res[f'{short}mt5r_ms'] = float('nan')
+    for weight, accuracies in zip(weights, results):
+        metric = accuracies['amt5r']
+        if len(mp_best_weights) == 0 or metric > mp_best_weights[0][0]:
+            at = sum(1 for m, _ in mp_best_weights if m <= metric)
+            mp_best_weights.insert(at, (metric, weight))
+            if len(mp_best_weights) > n_best:
+                mp_best_weights.pop(0)
+    return results
+
+
 def struct_outputs_from_scores(scores, dataset, uid_key='narration_id', k=100, uids=None):
     """The `results` dict of challenge.py:358-377 from scores = [verb, noun, action], arrays or device tensors whose rows follow
     dataset.df (or `uids`, where given).  Per uid: 'verb' / 'noun' {str(class): score} over every class; 'action' {"verb,noun": score}

@@ -128,6 +128,125 @@ __global__ __launch_bounds__(256) void recall_accumulate_kernel(const int32_t* _
   if (rank[r] < k) atomicAdd(tps + l, 1);
 }
 
+// ----------------------------------------------------------------------------- late-fusion weight search (afft_fused_label_rank)
+// WT weight sets share one pass over the n rows.  The accumulation is weighted_sum_fwd_kernel's (elementwise.hip) with the contraction
+// hipcc applies there written out: s = 0, then s = fma(w[i], x_i, s) in run order (v_fmac_f32 in the built library).
+constexpr int FLR_WT = 8;
+struct FusePtrs { const float* x[8]; };
+
+template <int N>
+__device__ __forceinline__ float fuse_scores(const float (&w)[N], const float (&x)[N]) {
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < N; ++i) s = __fmaf_rn(w[i], x[i], s);
+  return s;
+}
+
+// walk_row over N rows at once: fn(c, {x_0[c], ..., x_{N-1}[c]}) for every c in [0, C), the same 16-byte / scalar split
+template <int N, typename Fn>
+__device__ __forceinline__ void walk_rows(const float* const (&x)[N], int C, bool vec, Fn fn) {
+  const int tid = threadIdx.x;
+  float v[N];
+  if (vec) {
+    const int C4 = C & ~3;
+    for (int64_t c = tid * 4; c < C4; c += 1024) {      // 64-bit: c + 1024 may pass 2^31 on the last trip
+      f32x4 q[N];
+#pragma unroll
+      for (int i = 0; i < N; ++i) q[i] = *(const f32x4*)(x[i] + c);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) v[i] = q[i][e];
+        fn((int)c + e, v);
+      }
+    }
+    for (int64_t c = C4 + tid; c < C; c += 256) {
+#pragma unroll
+      for (int i = 0; i < N; ++i) v[i] = x[i][c];
+      fn((int)c, v);
+    }
+  } else {
+    for (int64_t c = tid; c < C; c += 256) {
+#pragma unroll
+      for (int i = 0; i < N; ++i) v[i] = x[i][c];
+      fn((int)c, v);
+    }
+  }
+}
+
+// One workgroup per (row, tile of FLR_WT weight sets).  The weights and the label scores depend on blockIdx only (wave-uniform: the
+// weights are read by scalar loads and stay in SGPRs); per lane: the N x 4 loaded scores, FLR_WT sums in flight and FLR_WT counters.
+// The surplus sets of a partial last tile repeat the last set's weights (nothing is read past w) and are never stored.
+// hipcc -O3 --offload-arch=gfx950 (kernel-resource-usage), FLR_WT = 8: N = 8: 59 VGPRs, 106 SGPRs, scratch 0, 7 waves / SIMD; the 64 weights
+// and the compare masks exceed the SGPR file, so 66 SGPRs are parked in VGPR lanes (v_readlane inside the loop; no memory).  N = 3: 43 VGPRs,
+// 106 SGPRs, scratch 0, the parked SGPRs are touched outside the loop only; the sums of two sets share one v_pk_fma_f32.
+template <int N>
+__global__ __launch_bounds__(256) void fused_label_rank_kernel(FusePtrs p, int64_t ldx, const float* __restrict__ w, int64_t ldw,
+                                                               int nsets, int C, int vec, const int64_t* __restrict__ labels,
+                                                               int32_t* __restrict__ rank, int64_t ldr) {
+  __shared__ int shi[4];
+  const int64_t row = blockIdx.x;
+  const int j0 = blockIdx.y * FLR_WT;
+  const int64_t lab = labels[row];
+  if (lab < 0 || lab >= C) {      // uniform per block: never a hit; nothing is read at the label's position
+    if (threadIdx.x < FLR_WT && j0 + (int)threadIdx.x < nsets) rank[(int64_t)(j0 + threadIdx.x) * ldr + row] = C;
+    return;
+  }
+  const int l = (int)lab;
+  float wt[FLR_WT][N];
+#pragma unroll
+  for (int j = 0; j < FLR_WT; ++j) {
+    const int64_t js = j0 + j < nsets ? j0 + j : nsets - 1;
+#pragma unroll
+    for (int i = 0; i < N; ++i) wt[j][i] = w[js * ldw + i];
+  }
+  const float* xr[N];
+  float xl[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) { xr[i] = p.x[i] + row * ldx; xl[i] = xr[i][l]; }
+  float sl[FLR_WT];
+  int cnt[FLR_WT];
+#pragma unroll
+  for (int j = 0; j < FLR_WT; ++j) { sl[j] = fuse_scores<N>(wt[j], xl); cnt[j] = 0; }
+  walk_rows<N>(xr, C, vec != 0, [&](int c, const float (&v)[N]) {
+    const bool other = c != l, lower = c < l;
+#pragma unroll
+    for (int j = 0; j < FLR_WT; ++j) {
+      const float s = fuse_scores<N>(wt[j], v);
+      cnt[j] += (other && (s > sl[j] || (s == sl[j] && lower))) ? 1 : 0;
+    }
+  });
+#pragma unroll
+  for (int j = 0; j < FLR_WT; ++j) {
+    const int n = block_sum_int(cnt[j], shi);
+    if (threadIdx.x == 0 && j0 + j < nsets) rank[(int64_t)(j0 + j) * ldr + row] = n;
+  }
+}
+
+// grid (row blocks, sets): thread = one (row, set).  hits: one pair of integer atomics per workgroup; tps: one per top-k row; nums: the
+// workgroups of set 0 only, so that every row counts once.
+__global__ __launch_bounds__(256) void rank_counts_sets_kernel(const int32_t* __restrict__ rank, int64_t ldr, int nsets,
+                                                               const int64_t* __restrict__ label, int rows, int C, int k,
+                                                               int32_t* __restrict__ hits, int32_t* __restrict__ tps,
+                                                               int32_t* __restrict__ nums) {
+  __shared__ int shi[4];
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool live = r < rows;
+  const int64_t l = live ? label[r] : -1;
+  const bool counted = l >= 0 && l < C;
+  if (blockIdx.y == 0 && counted) atomicAdd(nums + l, 1);
+  for (int j = blockIdx.y; j < nsets; j += gridDim.y) {      // gridDim.y < nsets only beyond 65535 sets
+    const int v = live ? rank[(int64_t)j * ldr + r] : k;
+    if (counted && v < k) atomicAdd(tps + (int64_t)j * C + l, 1);
+    const int h1 = block_sum_int(live && v < 1 ? 1 : 0, shi);
+    const int hk = block_sum_int(live && v < k ? 1 : 0, shi);
+    if (threadIdx.x == 0) {
+      if (h1) atomicAdd(hits + 2 * (int64_t)j, h1);
+      if (hk) atomicAdd(hits + 2 * (int64_t)j + 1, hk);
+    }
+  }
+}
+
 // Sort key of one score: high word = an unsigned image of the float that orders as the ORDER of include/afft_hip.h says (-0.0 folded
 // onto +0.0 first, NaN -> 0, below the image 0x007fffff of -inf), low word = ~class, so that among equal scores the LOWER class has the
 // LARGER key.  Integer arithmetic only: nothing here depends on the denormal mode.  Key 0 pads the row: below every real key.
@@ -208,6 +327,51 @@ extern "C" int afft_label_rank(const float* logits, int64_t row_stride, int32_t 
     hipLaunchKernelGGL(rank_hits_kernel, dim3(1), dim3(256), 0, stream, rank, rows, k, acc_scale, acc);
     AFFT_LAUNCH_CHECK();
   }
+  return 0;
+}
+
+extern "C" int afft_fused_label_rank(const float* const* x, int64_t ldx, int32_t n, const float* w, int64_t ldw, int32_t nsets,
+                                     int32_t rows, int32_t C, const int64_t* labels, int32_t* rank, int64_t ldr, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  AFFT_CHECK(n >= 1 && n <= 8, "fused_label_rank: 1 <= n <= 8 runs (got %d)", n);
+  AFFT_CHECK(rows >= 1 && C >= 1, "fused_label_rank: rows >= 1 and C >= 1 (got %d, %d)", rows, C);
+  AFFT_CHECK(nsets >= 1 && nsets <= 65535 * FLR_WT, "fused_label_rank: 1 <= nsets <= %d (got %d)", 65535 * FLR_WT, nsets);
+  AFFT_CHECK(ldx >= C, "fused_label_rank: ldx %lld < C = %d", (long long)ldx, C);
+  AFFT_CHECK(ldw >= n, "fused_label_rank: ldw %lld < n = %d", (long long)ldw, n);
+  AFFT_CHECK(ldr >= rows, "fused_label_rank: ldr %lld < rows = %d", (long long)ldr, rows);
+  AFFT_CHECK(x && w && labels && rank, "fused_label_rank: null x / w / labels / rank");
+  FusePtrs p;
+  int vec = (ldx & 3) == 0;
+  for (int i = 0; i < 8; ++i) {
+    p.x[i] = i < n ? x[i] : nullptr;
+    AFFT_CHECK(i >= n || x[i], "fused_label_rank: x[%d] is null", i);
+    vec = vec && ((uintptr_t)p.x[i] & 15) == 0;
+  }
+  const dim3 grid((unsigned)rows, (unsigned)((nsets + FLR_WT - 1) / FLR_WT));
+#define AFFT_FLR_LAUNCH(N)                                                                                                          \
+  case N:                                                                                                                           \
+    hipLaunchKernelGGL(fused_label_rank_kernel<N>, grid, dim3(256), 0, stream, p, ldx, w, ldw, nsets, C, vec, labels, rank, ldr); \
+    break;
+  switch (n) {
+    AFFT_FLR_LAUNCH(1) AFFT_FLR_LAUNCH(2) AFFT_FLR_LAUNCH(3) AFFT_FLR_LAUNCH(4)
+    AFFT_FLR_LAUNCH(5) AFFT_FLR_LAUNCH(6) AFFT_FLR_LAUNCH(7) AFFT_FLR_LAUNCH(8)
+  }
+#undef AFFT_FLR_LAUNCH
+  AFFT_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int afft_rank_counts_sets(const int32_t* rank, int64_t ldr, int32_t nsets, const int64_t* label, int32_t rows, int32_t C,
+                                     int32_t k, int32_t* hits, int32_t* tps, int32_t* nums, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  AFFT_CHECK(rank && label && hits && tps && nums, "rank_counts_sets: null pointer");
+  AFFT_CHECK(rows >= 1 && C >= 1, "rank_counts_sets: rows >= 1 and C >= 1 (got %d, %d)", rows, C);
+  AFFT_CHECK(k >= 1 && k <= C, "rank_counts_sets: 1 <= k <= C (got k = %d, C = %d)", k, C);
+  AFFT_CHECK(nsets >= 1, "rank_counts_sets: nsets >= 1 (got %d)", nsets);
+  AFFT_CHECK(ldr >= rows, "rank_counts_sets: ldr %lld < rows = %d", (long long)ldr, rows);
+  const dim3 grid((unsigned)(((int64_t)rows + 255) / 256), (unsigned)(nsets < 65535 ? nsets : 65535));
+  hipLaunchKernelGGL(rank_counts_sets_kernel, grid, dim3(256), 0, stream, rank, ldr, nsets, label, rows, C, k, hits, tps, nums);
+  AFFT_LAUNCH_CHECK();
   return 0;
 }
 

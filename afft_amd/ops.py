@@ -903,6 +903,37 @@ def recall_accumulate(rank: Tensor, label: Tensor, k: int, tps: Tensor, nums: Te
     L.check(L.lib().afft_recall_accumulate(_p(rank), _p(label), rows, tps.numel(), k, _p(tps), _p(nums), _stream()), "recall_accumulate")
 
 
+def fused_label_rank(xs: Sequence[Tensor], w: Tensor, labels: Tensor, rank: Optional[Tensor] = None):
+    """rank int32 [nsets, rows]: rank[j] = the label ranks of sum_i w[j, i] * xs[i], which is never written (afft_fused_label_rank,
+    include/afft_hip.h: bit for bit label_rank of weighted_sum_fwd's output).  xs: up to 8 fp32 [rows, C] VIEWS with unit column stride
+    and one row stride; w fp32 [nsets, len(xs)]; labels int64 [rows].  rank may be given (a wider buffer keeps its padding)."""
+    rows, cols = xs[0].shape
+    ld = _rowmajor(xs[0], "x")
+    assert all(x.shape == xs[0].shape and x.dtype == torch.float32 for x in xs)
+    if any(_rowmajor(x, "x") != ld for x in xs):      # the C-ABI has one ldx: there is nothing to hand it for a second stride
+        raise RuntimeError(f"afft_amd: fused_label_rank: every run must have the row stride of the first ({ld})")
+    nsets = w.shape[0]
+    assert w.dtype == torch.float32 and w.shape[1] == len(xs)
+    assert labels.dtype == torch.int64 and labels.numel() == rows and labels.is_contiguous()
+    if rank is None:
+        rank = torch.empty(nsets, rows, dtype=torch.int32, device=xs[0].device)
+    assert rank.dtype == torch.int32 and tuple(rank.shape) == (nsets, rows)
+    L.check(L.lib().afft_fused_label_rank(_ptr_array(xs), ld, len(xs), _p(w), _rowmajor(w, "w"), nsets, rows, cols,
+                                          _p(labels), _p(rank), _rowmajor(rank, "rank"), _stream()), "fused_label_rank")
+    return rank
+
+
+def rank_counts_sets(rank: Tensor, labels: Tensor, C_: int, k: int, hits: Tensor, tps: Tensor, nums: Tensor):
+    """hits int32 [nsets, 2] += (#{rank < 1}, #{rank < k}) of every row of rank int32 [nsets, rows]; tps int32 [nsets, C] += the per-class
+    top-k hits of every set; nums int32 [C] += the per-class row counts, once (afft_rank_counts_sets, include/afft_hip.h)."""
+    nsets, rows = rank.shape
+    assert rank.dtype == torch.int32 and labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() == rows
+    assert hits.dtype == tps.dtype == nums.dtype == torch.int32 and hits.is_contiguous() and tps.is_contiguous() and nums.is_contiguous()
+    assert hits.numel() == 2 * nsets and tps.numel() == nsets * C_ and nums.numel() == C_
+    L.check(L.lib().afft_rank_counts_sets(_p(rank), _rowmajor(rank, "rank"), nsets, _p(labels), rows, C_, k, _p(hits), _p(tps), _p(nums),
+                                          _stream()), "rank_counts_sets")
+
+
 def topk_rows(x: Tensor, k: int, vals: Optional[Tensor] = None, idx: Optional[Tensor] = None):
     """x fp32 [rows, C] VIEW with unit column stride, C <= TOPK_MAX_C; returns (vals fp32 [rows, k], idx int32 [rows, k]): the k best
     classes of every row, best first, in the total order of include/afft_hip.h (the lower class first among equal scores, NaN last).

@@ -592,6 +592,31 @@ int afft_label_rank(const float* logits, int64_t row_stride, int32_t rows, int32
  * every run, whatever the order (no float atomics anywhere in this library).  One launch. */
 int afft_recall_accumulate(const int32_t* rank, const int64_t* label, int32_t rows, int32_t C, int32_t k, int32_t* tps, int32_t* nums,
                            void* stream);
+/* Late-fusion weight search (the sweep of challenge.py:287-351, which scores one weight combination per pass over the runs): the rank of
+ * the label under nsets weighted sums of n runs' scores at once, WITHOUT the sums being written anywhere.  x[i] fp32 [rows, C], i < n <= 8,
+ * all with the row stride ldx (views are walked where they lie); w fp32 [nsets, n], row stride ldw; labels int64 [rows].
+ *   s_j[r, c]       = sum_{i<n} w[j, i] * x_i[r, c]                                      (registers only)
+ *   rank[j*ldr + r] = #{ c != l : s_j[r, c] > s_j[r, l]  or  (s_j[r, c] == s_j[r, l] and c < l) },   l = labels[r]
+ * which is afft_label_rank's comparator, TIE RULE (the lower class first) and rule for LABELS OUTSIDE [0, C) (rank = C, nothing is read at
+ * the label's position); NaN follows from the comparator: a NaN label score is beaten by nothing, a NaN score beats nothing.
+ * ARITHMETIC: s_j is bit for bit what afft_weighted_sum_fwd computes for the same inputs, so rank[j] equals afft_label_rank of that
+ * kernel's output: s = 0, then s = fma(w[j, i], x_i, s) for i = 0 .. n-1.  hipcc contracts that kernel's `s += w * x` to v_fmac_f32
+ * (one rounding per run); the accumulation here is written with __fmaf_rn, so it does not depend on the contraction mode.
+ * One workgroup of 256 threads per (row, tile of 8 weight sets) walks the n rows once (16-byte loads when every x[i] is 16-byte aligned
+ * and ldx is a multiple of 4, scalar loads otherwise), forms the 8 sums per element and bumps 8 integer counters; HBM traffic is one read
+ * of the n matrices per 8 sets.  1 <= n <= 8, rows >= 1, C >= 1 (no upper limit on either), 1 <= nsets <= 65535 * 8, ldx >= C, ldw >= n,
+ * ldr >= rows, no null pointer; rank int32 [nsets, rows] with row stride ldr (the padding is not written).  One launch; no allocation,
+ * no host sync, no scratch, no atomics: two runs give the same bits. */
+int afft_fused_label_rank(const float* const* x, int64_t ldx, int32_t n, const float* w, int64_t ldw, int32_t nsets, int32_t rows,
+                          int32_t C, const int64_t* labels, int32_t* rank, int64_t ldr, void* stream);
+/* The counters of nsets rank vectors at once (rank int32 [nsets, rows], row stride ldr, as afft_fused_label_rank wrote them; label int64
+ * [rows]).  For every set j:  hits[2j] += #{r : rank[j, r] < 1},  hits[2j + 1] += #{r : rank[j, r] < k}  over ALL rows (the counts of
+ * afft_label_rank's acc);  tps[j*C + label[r]] += (rank[j, r] < k)  for the rows whose label lies in [0, C).  nums[label[r]] += 1 once per
+ * such row, not per set.  hits int32 [nsets, 2], tps int32 [nsets, C], nums int32 [C], all ADDED to with integer atomics, as
+ * afft_recall_accumulate does: the same bits on every run.  rows >= 1, C >= 1, 1 <= k <= C, nsets >= 1, ldr >= rows, no null pointer.
+ * One launch. */
+int afft_rank_counts_sets(const int32_t* rank, int64_t ldr, int32_t nsets, const int64_t* label, int32_t rows, int32_t C, int32_t k,
+                          int32_t* hits, int32_t* tps, int32_t* nums, void* stream);
 /* Row-wise sorted top-k: the k best classes of every row, best first (the 100 best of 3806 action scores per segment of an
  * EPIC-KITCHENS-100 submission, challenge.py:367-368, where the reference runs np.argpartition + sorted once per row on the host).
  * Row r is read at x + r * ldx (ldx >= C: a view is walked where it lies, as afft_label_rank does).  For j < k:
