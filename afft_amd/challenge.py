@@ -139,16 +139,125 @@ def compute_accuracies_epic(probs, dataset, compute_manyshot_unseen_tail: bool =
     return res
 
 
-def marginalize_verb_noun(res_action, dataset, to_prob: bool = True, compute_manyshot_unseen_tail: bool = False):
+GROUP_ALL, GROUP_UNSEEN, GROUP_TAIL = 0, 1, 2      # the row groups of the EPIC-KITCHENS-100 report: bit g of row_groups()[space][r]
+
+
+def row_groups(dataset) -> Dict[str, np.ndarray]:
+    """{'verb': uint32 [N], 'noun': ..., 'action': ...}: the membership words afft_rank_counts_groups takes, one per row of dataset.df.
+    Bit GROUP_ALL is set for every row, bit GROUP_UNSEEN for the rows whose narration_id is in validation_unseen_participants_ids.csv,
+    bit GROUP_TAIL for the rows in that space's validation_tail_{verb,noun,action}s_ids.csv: the files and the matching of
+    epic100_unseen_tail_eval (challenge.py:109-135).  Host code only."""
+    import os.path as osp  # noqa: PLC0415
+    narration = np.asarray(dataset.df.narration_id.values).astype(str)
+
+    def rows_of(name):
+        return np.isin(narration, _read_id_column(osp.join(dataset.rulstm_annotation_dir, name))).astype(np.uint32)
+    unseen = rows_of("validation_unseen_participants_ids.csv")
+    return {key: (np.uint32(1 << GROUP_ALL) | (unseen << np.uint32(GROUP_UNSEEN))
+                  | (rows_of(f"validation_tail_{key}s_ids.csv") << np.uint32(GROUP_TAIL))).astype(np.uint32)
+            for key in ("verb", "noun", "action")}
+
+
+def _class_subset(classes, C: int):
+    """bool [C] of a {name: class id} subset (ids outside [0, C) name no class); None = every class"""
+    if classes is None:
+        return None
+    subset = np.zeros(C, dtype=bool)
+    subset[[int(c) for c in classes.values() if 0 <= int(c) < C]] = True
+    return subset
+
+
+def _recall_percent(tps: np.ndarray, nums: np.ndarray, subset=None) -> np.ndarray:
+    """float64 [m]: the mean top-k recall in percent of m counter rows tps int [m, C] over the classes with a row (nums int [C] > 0, and in
+    `subset` where given), in compute_accuracy's order of operations: the per-class shares summed in ascending class order, divided by
+    their number, times 100.  NaN where no class qualifies."""
+    seen = nums > 0
+    if subset is not None:
+        seen = seen & subset
+    per_class = tps[:, seen] / nums[seen]
+    n = per_class.shape[1]
+    return np.asarray([sum(row.tolist()) / n * 100 if n else float('nan') for row in per_class], dtype=np.float64)
+
+
+def _member_tensor(member, rows: int, dev) -> torch.Tensor:
+    """membership words on the device as int32 with the bits of the uint32 (torch has no arithmetic on uint32; the kernel reads bits)"""
+    if isinstance(member, torch.Tensor):
+        member = member.reshape(-1)
+        member = member if member.dtype in (torch.int32, torch.uint32) else member.to(torch.int32)
+        member = member.to(dev).contiguous()
+    else:
+        member = torch.from_numpy(np.ascontiguousarray(np.asarray(member).reshape(-1).astype(np.uint32)).view(np.int32)).to(dev)
+    if member.numel() != rows:
+        raise ValueError(f'one membership word per row: got {member.numel()} for {rows} rows')
+    return member
+
+
+def device_accuracies_epic(probs, dataset, compute_manyshot_unseen_tail: bool = False) -> Dict[str, float]:
+    """compute_accuracies_epic (challenge.py:161-193) for score matrices that stay on the device: probs = [verb, noun, action] as device
+    tensors (or anything _on_device takes); the same dict, keys in the same order, NaN where that function has NaN.  Per space: one
+    ops.label_rank, one ops.rank_counts_groups over that one rank vector, and one copy of the space's integer counters to the host
+    (ngroups * (2 C + 3) int32).  With compute_manyshot_unseen_tail on a dataset of version EPIC100_VERSION the rows are counted in
+    three groups (row_groups: all, unseen participants, the space's tail classes); otherwise in one, and no id table is read (the
+    reference's rule, challenge.py:190).  Many-shot recall = group GROUP_ALL's counters restricted to dataset.classes_manyshot[space],
+    as device_accuracy restricts them.  Every percentage is finished on the host in float64 from the integers, in compute_accuracy's
+    order of operations (hits / N * 100; _recall_percent) -- not through afft_label_rank's fp32 acc.  Labels outside [0, C) are never
+    a hit, stay in the accuracy denominators and out of the recalls; ties rank as include/afft_hip.h says (the lower class index
+    first): on tie-free scores the dict is compute_accuracies_epic's."""
+    assert len(probs) == 3, 'Probs should contain probs for verb, noun and action'
+    many = dataset.classes_manyshot
+    grouped = bool(compute_manyshot_unseen_tail) and getattr(dataset, "version", None) == EPIC100_VERSION
+    groups = row_groups(dataset) if grouped else None
+    G = 3 if grouped else 1
+    res, tail, unseen = {}, {}, {}
+    for short, key, p in (("v", "verb", probs[0]), ("n", "noun", probs[1]), ("a", "action", probs[2])):
+        scores = _on_device(p)
+        scores = scores.reshape(-1, scores.shape[-1])
+        scores = scores if scores.stride(-1) == 1 else scores.contiguous()
+        dev = scores.device
+        N, C = scores.shape
+        k = min(5, C)
+        labels = getattr(dataset.df, f"{key}_class").values
+        labels = torch.as_tensor(np.asarray(labels).reshape(-1).astype(np.int64)).to(dev)
+        rank = torch.empty(1, N, dtype=torch.int32, device=dev)
+        lab = torch.empty(N, dtype=torch.int64, device=dev)
+        counters = torch.zeros(G * (2 * C + 3), dtype=torch.int32, device=dev)      # hits [G, 2] | tps [G, C] | nums [G, C] | rows [G]
+        ops.label_rank(scores, C, labels=labels, k=k, rank=rank[0], label_out=lab)
+        ops.rank_counts_groups(rank, lab, C, k, _member_tensor(groups[key], N, dev) if grouped else None, G, counters[:2 * G],
+                               counters[2 * G:G * (2 + C)], counters[G * (2 + C):G * (2 + 2 * C)], counters[G * (2 + 2 * C):])
+        back = counters.cpu().numpy().astype(np.int64)
+        hits = back[:2 * G].reshape(G, 2)
+        tps = back[2 * G:G * (2 + C)].reshape(G, C)
+        nums = back[G * (2 + C):G * (2 + 2 * C)].reshape(G, C)
+        res[f"{short}top1"], res[f"{short}top5"] = float(hits[0, 0] / N * 100), float(hits[0, 1] / N * 100)
+        res[f"{short}mt5r"] = float(_recall_percent(tps[:1], nums[0])[0])
+        res[f"{short}mt5r_ms"] = float("nan")
+        if key in many and compute_manyshot_unseen_tail:
+            res[f"{short}mt5r_ms"] = float(_recall_percent(tps[:1], nums[0], _class_subset(many[key], C))[0])
+        if grouped:
+            tail[f"{short}mt5r_tail"] = float(_recall_percent(tps[GROUP_TAIL:GROUP_TAIL + 1], nums[GROUP_TAIL])[0])
+            unseen[f"{short}mt5r_unseen"] = float(_recall_percent(tps[GROUP_UNSEEN:GROUP_UNSEEN + 1], nums[GROUP_UNSEEN])[0])
+    res.update(tail)
+    res.update(unseen)
+    return res
+
+
+def marginalize_verb_noun(res_action, dataset, to_prob: bool = True, compute_manyshot_unseen_tail: bool = False,
+                          device_metrics: bool = False):
     """challenge.py:196-210 with the same signature and return value: (accuracies, [verb, noun, action] as numpy arrays).
     res_action: action logits, a device tensor (kept on the device for the softmax and the two mapping GEMMs) or anything
-    torch.as_tensor accepts (moved to cuda:0)."""
+    torch.as_tensor accepts (moved to cuda:0).  device_metrics=True: the accuracies come from device_accuracies_epic on the three
+    matrices while they are on the device, in place of compute_accuracies_epic's sorts of their host copies; the scores returned are
+    the same."""
     x = torch.as_tensor(res_action)
     if not x.is_cuda:
         x = x.cuda()
     verb, noun, action = marginalize_scores(x.float(), dataset.class_mappings, to_prob=to_prob)
-    scores = [t.detach().cpu().numpy() for t in (verb, noun, action.reshape(-1, action.shape[-1]))]
-    return compute_accuracies_epic(scores, dataset, compute_manyshot_unseen_tail), scores
+    on_device = (verb, noun, action.reshape(-1, action.shape[-1]))
+    accuracies = device_accuracies_epic(on_device, dataset, compute_manyshot_unseen_tail) if device_metrics else None
+    scores = [t.detach().cpu().numpy() for t in on_device]
+    if accuracies is None:
+        accuracies = compute_accuracies_epic(scores, dataset, compute_manyshot_unseen_tail)
+    return accuracies, scores
 
 
 LOGITS_DIR = 'logits'        # challenge.py:28
@@ -315,7 +424,7 @@ def get_epic_marginalize_late_fuse(resdirs, weights=1.0, mp_best_weights=None, n
     return accuracies, combined, ds
 
 
-def device_sweep(xs, labels, weights, k=5, classes=None, sets_per_call=512):
+def device_sweep(xs, labels, weights, k=5, classes=None, sets_per_call=512, member=None, ngroups=1):
     """compute_accuracy of sum_i weights[j, i] * xs[i] for every weight set j, without any of the sums being formed: three float64
     vectors of length nsets, (top-1, top-k, mean top-k recall) in percent.  xs: R <= MAX_DEVICE_RUNS score matrices [N, C] of one space
     (arrays or device tensors; they go to the device once), labels [N] integer, weights [nsets, R].  Per chunk of sets_per_call sets:
@@ -325,7 +434,17 @@ def device_sweep(xs, labels, weights, k=5, classes=None, sets_per_call=512):
     order of operations of compute_accuracy: hits / N * 100, and the recall mean summed in ascending class order over the classes with
     a row (restricted to `classes`, a {name: class id} subset, when given).  Labels outside [0, C) are never a hit, stay in the accuracy
     denominators and out of the recall (device_accuracy's rule).  Ties rank as include/afft_hip.h says (the lower class index first); on
-    tie-free scores the three numbers are compute_accuracy's of the materialised combination, bit for bit."""
+    tie-free scores the three numbers are compute_accuracy's of the materialised combination, bit for bit.
+
+    ROW GROUPS.  With member (uint32 [N], bit g = row r is in group g < ngroups <= 8: row_groups) the chunk's counting launch is
+    ops.rank_counts_groups and the return value is FOUR float64 arrays of shape [nsets, ngroups], (top-1, top-k, recall, recall_in_classes):
+    column g holds the numbers of the rows of group g alone -- the accuracies over that group's rows (NaN for a group without rows), the
+    recall over the classes with a row in the group.  `classes` does not narrow the third array there: the fourth is the recall narrowed
+    to `classes` (NaN throughout without `classes`), so that one pass yields both the overall and the many-shot recall of the
+    EPIC-KITCHENS-100 report.  Without member (and ngroups = 1) the call sequence and the three vectors are as described above."""
+    grouped = member is not None
+    if not grouped and ngroups != 1:
+        raise ValueError(f'device_sweep: ngroups = {ngroups} needs the membership words (member)')
     xs = [_on_device(x) for x in xs]
     xs = [x.reshape(-1, x.shape[-1]) for x in xs]
     if not 1 <= len(xs) <= MAX_DEVICE_RUNS:
@@ -343,6 +462,8 @@ def device_sweep(xs, labels, weights, k=5, classes=None, sets_per_call=512):
         else labels.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
     per_call = max(1, min(int(sets_per_call), nsets))
     rank = torch.empty(per_call, N, dtype=torch.int32, device=dev)
+    if grouped:
+        return _grouped_sweep(xs, w, lab, rank, k, _class_subset(classes, C), _member_tensor(member, N, dev), int(ngroups))
     hits = np.empty((nsets, 2), np.int64)
     tps = np.empty((nsets, C), np.int64)
     nums = None
@@ -368,7 +489,41 @@ def device_sweep(xs, labels, weights, k=5, classes=None, sets_per_call=512):
     return top1, topk, recall
 
 
-def late_fuse_sweep(resdirs, weights, mp_best_weights=None, n_best=5, uid_key='narration_id', dataset=None):
+def _grouped_sweep(xs, w, lab, rank, k, subset, member, G):
+    """device_sweep's loop with the counters kept per row group: per chunk one ops.fused_label_rank, one ops.rank_counts_groups and one
+    copy of hits [m, G, 2] | tps [m, G, C]; nums [G, C] | group rows [G] come back with the first chunk only"""
+    dev = xs[0].device
+    N, C = xs[0].shape
+    nsets, per_call = w.shape[0], rank.shape[0]
+    hits = np.empty((nsets, G, 2), np.int64)
+    tps = np.empty((nsets, G, C), np.int64)
+    nums = group_rows = None
+    for at in range(0, nsets, per_call):
+        m = min(per_call, nsets - at)
+        per_set = m * G * (2 + C)
+        counters = torch.zeros(per_set + G * (C + 1), dtype=torch.int32, device=dev)
+        ops.fused_label_rank(xs, w[at:at + m], lab, rank=rank[:m])
+        ops.rank_counts_groups(rank[:m], lab, C, k, member, G, counters[:2 * m * G], counters[2 * m * G:per_set],
+                               counters[per_set:per_set + G * C], counters[per_set + G * C:])
+        back = (counters if nums is None else counters[:per_set]).cpu().numpy()
+        hits[at:at + m] = back[:2 * m * G].reshape(m, G, 2)
+        tps[at:at + m] = back[2 * m * G:per_set].reshape(m, G, C)
+        if nums is None:
+            nums = back[per_set:per_set + G * C].reshape(G, C).astype(np.int64)
+            group_rows = back[per_set + G * C:].astype(np.int64)
+    out = [np.full((nsets, G), np.nan, dtype=np.float64) for _ in range(4)]
+    for g in range(G):
+        if group_rows[g]:
+            out[0][:, g] = hits[:, g, 0] / group_rows[g] * 100
+            out[1][:, g] = hits[:, g, 1] / group_rows[g] * 100
+        out[2][:, g] = _recall_percent(tps[:, g], nums[g])
+        if subset is not None:
+            out[3][:, g] = _recall_percent(tps[:, g], nums[g], subset)
+    return tuple(out)
+
+
+def late_fuse_sweep(resdirs, weights, mp_best_weights=None, n_best=5, uid_key='narration_id', dataset=None,
+                    compute_manyshot_unseen_tail=False):
     """The weight search of challenge.py:287-351 (get_epic_marginalize_late_fuse over a list of weight combinations, which the reference
     runs under multiprocessing) with every combination scored on the device by device_sweep: one call per space (verb, noun, action),
     no combination is materialised, and what comes back per combination is integer counters.  resdirs are read as
@@ -377,7 +532,10 @@ def late_fuse_sweep(resdirs, weights, mp_best_weights=None, n_best=5, uid_key='n
     the host).  Returns a list with one accuracies dict per weight combination: the keys of compute_accuracies_epic without the many-shot
     option (the *_ms entries are NaN).  mp_best_weights (optional list, updated in place) keeps the n_best (amt5r, weights) pairs seen,
     ascending, by the rule of get_epic_marginalize_late_fuse.  Ties rank as include/afft_hip.h says (the lower class index first); on
-    tie-free scores every number is the one get_epic_marginalize_late_fuse reports for that combination."""
+    tie-free scores every number is the one get_epic_marginalize_late_fuse reports for that combination.
+    compute_manyshot_unseen_tail=True: every dict is compute_accuracies_epic(combination, dataset, True)'s instead -- the *_ms entries
+    from dataset.classes_manyshot and, on a dataset of version EPIC100_VERSION, the *_tail and *_unseen recalls of row_groups' groups.
+    Each chunk still makes one ops.fused_label_rank per space; its counting launch is ops.rank_counts_groups (device_sweep with member)."""
     ds = _dataset(dataset)
     if not isinstance(resdirs, list):
         resdirs = [resdirs]
@@ -399,12 +557,31 @@ def late_fuse_sweep(resdirs, weights, mp_best_weights=None, n_best=5, uid_key='n
                          'get_epic_marginalize_late_fuse, which sums such runs per uid')
     table = np.asarray([[float(x) for x in weight] for weight in weights], dtype=np.float32)
     results = [{} for _ in weights]
+    report = bool(compute_manyshot_unseen_tail)
+    grouped = report and getattr(ds, 'version', None) == EPIC100_VERSION      # the rule of compute_accuracies_epic (challenge.py:190)
+    groups = row_groups(ds) if grouped else None
+    tails, unseens = [{} for _ in weights], [{} for _ in weights]
     for space, (short, key) in enumerate((('v', 'verb'), ('n', 'noun'), ('a', 'action'))):
         xs = [np.stack([run[space][u] for u in uids]) for run in all_scores]
-        top1, top5, mt5r = device_sweep(xs, getattr(ds.df, f'{key}_class').values, table)
+        labels = getattr(ds.df, f'{key}_class').values
+        if not report:
+            top1, top5, mt5r = device_sweep(xs, labels, table)
+            for j, res in enumerate(results):
+                res[f'{short}top1'], res[f'{short}top5'], res[f'{short}mt5r'] = float(top1[j]), float(top5[j]), float(mt5r[j])
+                res[f'{short}mt5r_ms'] = float('nan')
+            continue
+        member = groups[key] if grouped else np.full(len(uids), 1 << GROUP_ALL, dtype=np.uint32)
+        top1, top5, mt5r, ms = device_sweep(xs, labels, table, classes=ds.classes_manyshot.get(key), member=member,
+                                            ngroups=3 if grouped else 1)
         for j, res in enumerate(results):
-            res[f'{short}top1'], res[f'{short}top5'], res[f'{short}mt5r'] = float(top1[j]), float(top5[j]), float(mt5r[j])
-            res[f'{short}mt5r_ms'] = float('nan')
+            res[f'{short}top1'], res[f'{short}top5'] = float(top1[j, GROUP_ALL]), float(top5[j, GROUP_ALL])
+            res[f'{short}mt5r'], res[f'{short}mt5r_ms'] = float(mt5r[j, GROUP_ALL]), float(ms[j, GROUP_ALL])
+            if grouped:
+                tails[j][f'{short}mt5r_tail'] = float(mt5r[j, GROUP_TAIL])
+                unseens[j][f'{short}mt5r_unseen'] = float(mt5r[j, GROUP_UNSEEN])
+    for res, tail, unseen in zip(results, tails, unseens):      # compute_accuracies_epic's key order: the tail numbers, then the unseen ones
+        res.update(tail)
+        res.update(unseen)
     for weight, accuracies in zip(weights, results):
         metric = accuracies['amt5r']
         if len(mp_best_weights) == 0 or metric > mp_best_weights[0][0]:

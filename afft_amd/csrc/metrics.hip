@@ -247,6 +247,47 @@ __global__ __launch_bounds__(256) void rank_counts_sets_kernel(const int32_t* __
   }
 }
 
+// rank_counts_sets_kernel with the counters kept per row group: bit g of member[r] puts row r into group g (member == nullptr: every row
+// is in group 0, the only one).  `present` (the groups with a row in this workgroup) is uniform, so the reductions of an absent group
+// are skipped as a whole and it gets no atomic.  The two hit counts of a (set, group) are at most 256 each and share one reduction:
+// #{rank < 1} in the low half of the word, #{rank < k} in the high half.
+__global__ __launch_bounds__(256) void rank_counts_groups_kernel(const int32_t* __restrict__ rank, int64_t ldr, int nsets,
+                                                                 const int64_t* __restrict__ label,
+                                                                 const uint32_t* __restrict__ member, int ngroups, int rows, int C, int k,
+                                                                 int32_t* __restrict__ hits, int32_t* __restrict__ tps,
+                                                                 int32_t* __restrict__ nums, int32_t* __restrict__ group_rows) {
+  __shared__ int shi[4];
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool live = r < rows;
+  const int64_t l = live ? label[r] : -1;
+  const bool counted = l >= 0 && l < C;
+  const unsigned m = !live ? 0u : member ? member[r] & ((1u << ngroups) - 1u) : 1u;      // ngroups <= 8: the shift is defined
+  unsigned present = 0;
+  for (int g = 0; g < ngroups; ++g) {
+    const int n = block_sum_int((int)((m >> g) & 1u), shi);
+    if (!n) continue;
+    present |= 1u << g;
+    if (blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(group_rows + g, n);
+  }
+  if (blockIdx.y == 0 && counted)
+    for (unsigned b = m; b; b &= b - 1) atomicAdd(nums + (int64_t)(__ffs((int)b) - 1) * C + l, 1);
+  for (int j = blockIdx.y; j < nsets; j += gridDim.y) {      // gridDim.y < nsets only beyond 65535 sets
+    const int v = live ? rank[(int64_t)j * ldr + r] : k;
+    const int mine = (v < 1 ? 1 : 0) | (v < k ? 1 << 16 : 0);
+    if (counted && v < k)
+      for (unsigned b = m; b; b &= b - 1) atomicAdd(tps + ((int64_t)j * ngroups + (__ffs((int)b) - 1)) * C + l, 1);
+    for (int g = 0; g < ngroups; ++g) {
+      if (!((present >> g) & 1u)) continue;
+      const int h = block_sum_int(((m >> g) & 1u) ? mine : 0, shi);
+      if (threadIdx.x == 0) {
+        int32_t* at = hits + 2 * ((int64_t)j * ngroups + g);
+        if (h & 0xffff) atomicAdd(at, h & 0xffff);
+        if (h >> 16) atomicAdd(at + 1, h >> 16);
+      }
+    }
+  }
+}
+
 // Sort key of one score: high word = an unsigned image of the float that orders as the ORDER of include/afft_hip.h says (-0.0 folded
 // onto +0.0 first, NaN -> 0, below the image 0x007fffff of -inf), low word = ~class, so that among equal scores the LOWER class has the
 // LARGER key.  Integer arithmetic only: nothing here depends on the denormal mode.  Key 0 pads the row: below every real key.
@@ -371,6 +412,24 @@ extern "C" int afft_rank_counts_sets(const int32_t* rank, int64_t ldr, int32_t n
   AFFT_CHECK(ldr >= rows, "rank_counts_sets: ldr %lld < rows = %d", (long long)ldr, rows);
   const dim3 grid((unsigned)(((int64_t)rows + 255) / 256), (unsigned)(nsets < 65535 ? nsets : 65535));
   hipLaunchKernelGGL(rank_counts_sets_kernel, grid, dim3(256), 0, stream, rank, ldr, nsets, label, rows, C, k, hits, tps, nums);
+  AFFT_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int afft_rank_counts_groups(const int32_t* rank, int64_t ldr, int32_t nsets, const int64_t* label, const uint32_t* member,
+                                       int32_t ngroups, int32_t rows, int32_t C, int32_t k, int32_t* hits, int32_t* tps, int32_t* nums,
+                                       int32_t* group_rows, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  AFFT_CHECK(ngroups >= 1 && ngroups <= 8, "rank_counts_groups: 1 <= ngroups <= 8 (got %d)", ngroups);
+  AFFT_CHECK(rank && label && hits && tps && nums && group_rows, "rank_counts_groups: null pointer");
+  AFFT_CHECK(member || ngroups == 1, "rank_counts_groups: null member with ngroups = %d (allowed with one group only)", ngroups);
+  AFFT_CHECK(rows >= 1 && C >= 1, "rank_counts_groups: rows >= 1 and C >= 1 (got %d, %d)", rows, C);
+  AFFT_CHECK(k >= 1 && k <= C, "rank_counts_groups: 1 <= k <= C (got k = %d, C = %d)", k, C);
+  AFFT_CHECK(nsets >= 1, "rank_counts_groups: nsets >= 1 (got %d)", nsets);
+  AFFT_CHECK(ldr >= rows, "rank_counts_groups: ldr %lld < rows = %d", (long long)ldr, rows);
+  const dim3 grid((unsigned)(((int64_t)rows + 255) / 256), (unsigned)(nsets < 65535 ? nsets : 65535));
+  hipLaunchKernelGGL(rank_counts_groups_kernel, grid, dim3(256), 0, stream, rank, ldr, nsets, label, member, ngroups, rows, C, k, hits, tps,
+                     nums, group_rows);
   AFFT_LAUNCH_CHECK();
   return 0;
 }

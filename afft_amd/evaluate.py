@@ -4,10 +4,11 @@
 The reference copies every batch of logits to the host (``.detach().cpu().numpy()``, a device sync per batch),
 concatenates there and marginalises verbs / nouns in numpy.  Here the logits of the branch the reference keeps (the only
 modality, or 'all-fused') stay on the device, are concatenated once, marginalised by ``afft_amd.challenge.
-marginalize_scores`` (row softmax + two fp32 MFMA GEMMs) and leave the device in ONE copy per result.  The accuracy
-bookkeeping over the dataset's annotations (``challenge.compute_accuracies_epic``) stays with the caller; for score matrices
-that should not leave the device at all, ``challenge.device_accuracy(scores, labels, classes)`` gives top-1 / top-5 / mean top-5
-recall from label ranks and integer per-class counters computed there.
+marginalize_scores`` (row softmax + two fp32 MFMA GEMMs) and leave the device in ONE copy per result.  ``evaluate`` is
+``test.py:evaluate`` itself: the full EPIC-KITCHENS-100 report (overall, many-shot, unseen participants, tail classes) from
+``challenge.device_accuracies_epic``, which counts label ranks per row group on the device and copies integer counters back.
+For a caller with scores of its own, the host bookkeeping (``challenge.compute_accuracies_epic``) and ``challenge.
+device_accuracy(scores, labels, classes)`` (top-1 / top-5 / mean top-5 recall of one matrix) remain.
 """
 from __future__ import annotations
 
@@ -76,6 +77,20 @@ def evaluate_scores(model, class_mappings, data_loader: Iterable, device, to_pro
     _, logits = collect_logits(model, data_loader, device, precision=precision)
     verb, noun, action = marginalize_scores(logits, class_mappings, to_prob=to_prob)
     return {"verb": verb.cpu().numpy(), "noun": noun.cpu().numpy(), "action": action.cpu().numpy()}
+
+
+@torch.no_grad()
+def evaluate(model, dataset, data_loader: Iterable, device, precision: Optional[str] = None) -> Dict[str, float]:
+    """test.py:64-98: the verb / noun / action performance overall, on the many-shot classes, on unseen participants and on the tail
+    classes.  collect_logits, then challenge.marginalize_scores (to_prob=True), then challenge.device_accuracies_epic with
+    compute_manyshot_unseen_tail=True, then print_accuracies_epic; returns the accuracies dict (the reference prints it only).  Nothing
+    of width N x C leaves the device: what comes back per space is 2 C + 3 integer counters per row group."""
+    from . import challenge  # noqa: PLC0415
+    _, logits = collect_logits(model, data_loader, device, precision=precision)
+    verb, noun, action = marginalize_scores(logits, dataset.class_mappings, to_prob=True)
+    accuracies = challenge.device_accuracies_epic([verb, noun, action], dataset, compute_manyshot_unseen_tail=True)
+    challenge.print_accuracies_epic(accuracies)
+    return accuracies
 
 
 def store_append(endpoints: Dict[str, np.ndarray], output_dir: str, save_file_name: str) -> str:

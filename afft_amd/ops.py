@@ -934,6 +934,24 @@ def rank_counts_sets(rank: Tensor, labels: Tensor, C_: int, k: int, hits: Tensor
                                           _stream()), "rank_counts_sets")
 
 
+def rank_counts_groups(rank: Tensor, labels: Tensor, C_: int, k: int, member: Optional[Tensor], ngroups: int, hits: Tensor, tps: Tensor,
+                       nums: Tensor, group_rows: Tensor):
+    """rank_counts_sets per row group: member uint32-as-int32 [rows] (bit g = row r is in group g; None with ngroups = 1: every row);
+    hits int32 [nsets, ngroups, 2], tps int32 [nsets, ngroups, C], nums int32 [ngroups, C], group_rows int32 [ngroups], all ADDED to
+    (afft_rank_counts_groups, include/afft_hip.h).  torch has no arithmetic on uint32: an int32 tensor with the same bits is taken too."""
+    nsets, rows = rank.shape
+    assert rank.dtype == torch.int32 and labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() == rows
+    if member is not None:
+        assert member.dtype in (torch.int32, torch.uint32) and member.is_contiguous() and member.numel() == rows
+    assert hits.dtype == tps.dtype == nums.dtype == group_rows.dtype == torch.int32
+    assert hits.is_contiguous() and tps.is_contiguous() and nums.is_contiguous() and group_rows.is_contiguous()
+    g = int(ngroups)
+    if 1 <= g <= 8:      # any other count is the library's to refuse: no buffer size would be right for it
+        assert hits.numel() == 2 * nsets * g and tps.numel() == nsets * g * C_ and nums.numel() == g * C_ and group_rows.numel() == g
+    L.check(L.lib().afft_rank_counts_groups(_p(rank), _rowmajor(rank, "rank"), nsets, _p(labels), _p(member), ngroups, rows, C_, k,
+                                            _p(hits), _p(tps), _p(nums), _p(group_rows), _stream()), "rank_counts_groups")
+
+
 def topk_rows(x: Tensor, k: int, vals: Optional[Tensor] = None, idx: Optional[Tensor] = None):
     """x fp32 [rows, C] VIEW with unit column stride, C <= TOPK_MAX_C; returns (vals fp32 [rows, k], idx int32 [rows, k]): the k best
     classes of every row, best first, in the total order of include/afft_hip.h (the lower class first among equal scores, NaN last).

@@ -617,6 +617,22 @@ int afft_fused_label_rank(const float* const* x, int64_t ldx, int32_t n, const f
  * One launch. */
 int afft_rank_counts_sets(const int32_t* rank, int64_t ldr, int32_t nsets, const int64_t* label, int32_t rows, int32_t C, int32_t k,
                           int32_t* hits, int32_t* tps, int32_t* nums, void* stream);
+/* afft_rank_counts_sets with the counters kept per ROW GROUP, for the EPIC-KITCHENS-100 validation report (challenge.py:109-193: overall,
+ * unseen participants, tail classes are the same counts over different subsets of the rows).  member uint32 [rows]: bit g set = row r
+ * belongs to group g, g < ngroups; bits at or above ngroups are ignored; a row may belong to several groups or to none.  member == NULL is
+ * allowed with ngroups == 1 only and puts every row into group 0.  For every set j and group g:
+ *   hits[(j*ngroups + g)*2]     += #{r in g : rank[j, r] < 1},   hits[(j*ngroups + g)*2 + 1] += #{r in g : rank[j, r] < k}
+ *     over ALL rows of the group, those whose label lies outside [0, C) included (their rank is C: never a hit);
+ *   tps[(j*ngroups + g)*C + label[r]] += (rank[j, r] < k)   for the rows of g whose label lies in [0, C);
+ *   nums[g*C + label[r]] += 1   once per such row, not per set;      group_rows[g] += #{r in g}   once, not per set.
+ * hits int32 [nsets, ngroups, 2], tps int32 [nsets, ngroups, C], nums int32 [ngroups, C], group_rows int32 [ngroups], all ADDED to with
+ * integer atomics: the same bits on every run.  The hit counts are summed in the workgroup (256 rows) first: one atomic per workgroup,
+ * set, group and counter, and none for a group without a row in the workgroup.  With ngroups == 1 and member == NULL hits / tps / nums
+ * are afft_rank_counts_sets', integer for integer.  rows >= 1, C >= 1, 1 <= k <= C, nsets >= 1, 1 <= ngroups <= 8, ldr >= rows, no null
+ * pointer but member as said.  One launch; no allocation, no host sync, no scratch, no float atomics. */
+int afft_rank_counts_groups(const int32_t* rank, int64_t ldr, int32_t nsets, const int64_t* label, const uint32_t* member, int32_t ngroups,
+                            int32_t rows, int32_t C, int32_t k, int32_t* hits, int32_t* tps, int32_t* nums, int32_t* group_rows,
+                            void* stream);
 /* Row-wise sorted top-k: the k best classes of every row, best first (the 100 best of 3806 action scores per segment of an
  * EPIC-KITCHENS-100 submission, challenge.py:367-368, where the reference runs np.argpartition + sorted once per row on the host).
  * Row r is read at x + r * ldx (ldx >= C: a view is walked where it lies, as afft_label_rank does).  For j < k:
