@@ -11,8 +11,9 @@ __device__ __forceinline__ bool masked(int mask, int period, int i, int j) {
 
 // LDS tile [R][hd] bf16; 32-byte unit u of row r is stored at unit u ^ (r & 7): conflict-free transposed reads,
 // 2-way (harmless here) ds_read_b128 row reads.
-__device__ __forceinline__ int swz(int row, int row_bytes) {   // XOR stays inside the row: rows hold row_bytes/32 units
-  return row & 7 & ((row_bytes >> 5) - 1);
+__device__ __forceinline__ int swz(int row, int row_bytes) {   // XOR stays inside the row: rows hold n = row_bytes/32 units, and only the
+  const int n = row_bytes >> 5;                                //   bits below n's lowest set bit may flip (n = 6, the 96-channel slices of
+  return row & 7 & ((n & -n) - 1);                             //   hd = 384: bit 0 alone; n - 1 = 5 sent units 2, 3 into the next row)
 }
 __device__ __forceinline__ int tile_off(int row, int chunk16, int row_bytes) {
   return row * row_bytes + ((chunk16 ^ (swz(row, row_bytes) << 1)) << 4);

@@ -1,0 +1,273 @@
+"""Every case of tests/attention_cases.py -- every instantiation of the short attention kernels (L <= 128: attention.hip,
+attention_mfma.hip) -- ELEMENTWISE against float64, with every operand in a NaN frame of its own and every result in a sentinel frame.
+
+Reference (reference()): float64 scores, mask, softmax, the dropout mask of the integer replica (kernel_doubles.drop_keep at index
+((seq * H + h) * L + i) * L + j, scaled by 1 / (1 - p)), P'V, and the backward products written out.  Beside every output element it
+forms the magnitude sum S: the same expression with absolute values at every product and sum (for probs, which is all positive, the
+first-order image of the score's magnitude sum A = scale * sum |q| |k| through the softmax: S = p * (1 + A_ij + sum_j p_ij A_ij)).
+The test asserts |got - ref| <= c * u * S for every element, where u is the unit roundoff of the narrowest rounding on the path:
+2^-24 fp32 kernels and every probs; 2^-9 bf16 outputs and gradients (P', dS and the stored result are rounded to bf16) and the bf16
+copy; 2^-21 out assembled from its two fp16 planes; 2^-11 the hi plane alone.  (Round-to-nearest bf16 is off by up to 2^-9 of the
+binade's upper end, 2^-8 of its lower end: the two roundings the count expects read as up to 4 in these units.)
+
+The backward runs twice: on the kernel's own probs, and on the float64 probabilities rounded to fp32, both held to the same bars -- a
+backward that is right only on its own forward's rounding fails the second.  An a8 case runs a third time on frame-free 16-byte
+aligned gradient buffers (the column-sliced kernel); both are compared with float64, never with each other.  The relative-L2 bars of
+test_kernels_gpu.py (test_attention_fwd_bwd, test_attention_fwd_split) are kept as a second assertion.
+
+c is twice the worst |got - ref| / (u S) measured over the table on an MI355X, rounded up to a power of two (MEASURED below: the
+worst per kernel path and output kind, gradients over both probs sources; C: the bars).
+"""
+import math
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(__file__))
+import kernel_doubles as kd  # noqa: E402
+from attention_cases import BLOCK, CASES, CAUSAL, DIAG, frame_cols  # noqa: E402
+from helpers import rel_l2  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+PAD_ROWS, PAD_FLAT, SENTINEL, KEY = 2, 64, 512.0, 0x9E3779B9
+U = {"f32": 2.0 ** -24, "bf16": 2.0 ** -9, "planes": 2.0 ** -21, "hi": 2.0 ** -11}
+
+# worst |got - ref| / (u S) over the table, MI355X: path -> kind -> value
+MEASURED = {
+    "generic_f32": dict(out=7.76, probs=5.88, dq=3.19, dk=2.75, dv=7.29),
+    "generic_bf16": dict(out=1.99, probs=2.70, dq=0.461, dk=0.720, dv=1.95),
+    "mfma_fwd": dict(out=3.33, probs=0.758),
+    "mfma_bwd": dict(dq=0.556, dk=1.17, dv=3.62),
+    "sliced_bwd": dict(dq=0.415, dk=0.370, dv=3.25),
+    "split_pl1": dict(out=42.1, outf=0.458, copy=1.93, hi=0.981, probs=1.24),
+    "split_pl2": dict(out=56.7, outf=0.425, copy=1.97, hi=0.970, probs=0.986),
+}
+# The bars: twice the worst measured, rounded up to a power of two.  All stay within 8 (bf16, planes) and 64 (fp32, probs) but one: out
+# of the fp16x2 forward against u S alone (128).  Its worst elements are small outputs under dropout (few kept keys, S ~ 1e-3), where
+# the fp16 planes' ABSOLUTE floor shows, not a relative error: a lo part below 2^-14 is subnormal and off by up to 2^-25, which is 64
+# u S at S = 2^-10.  Without dropout the same kernels measure 2.5.  "outf" holds the same elements to u S plus that floor (see
+# run_case), and measures 0.46: that is the tight bar, the 128 is kept because it is the plain form.
+C = {path: {kind: 2.0 ** math.ceil(math.log2(2.0 * w)) for kind, w in kinds.items()} for path, kinds in MEASURED.items()}
+assert C["split_pl2"] == dict(out=128.0, outf=1.0, copy=4.0, hi=2.0, probs=2.0) and C["generic_f32"]["out"] == 16.0 and C["mfma_bwd"]["dv"] == 8.0
+# relative L2, as test_kernels_gpu.py holds them
+L2 = {"f32": dict(out=2e-5, probs=2e-5, grads=3e-5), "bf16": dict(out=1e-2, probs=2e-3, grads=2e-2),
+      "split": dict(out=2e-5, probs=2e-5, copy=4e-3, hi=5e-4)}
+
+
+def dev():
+    return torch.device("cuda:0")
+
+
+def rnd(*shape, seed):
+    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
+
+
+def path_of(c, kind):
+    """the kernel path the bar of one output kind of case c is filed under: out / probs / copy / hi by the forward kernel, the gradients
+    by the backward kernel (the twin of an a8 case ran the column-sliced one)"""
+    if c.entry == "split":
+        return "split_pl1" if c.storage == "f16x2" else "split_pl2"
+    if not c.mfma:
+        return "generic_" + c.storage
+    if kind[:2] in ("dq", "dk", "dv"):
+        return "sliced_bwd" if "_sliced_" in c.bwd or kind.endswith("/twin") else "mfma_bwd"
+    return "mfma_fwd"
+
+
+def framed(R, C_, fill, dtype, pad_cols, planes=1):
+    """[planes] buffers of (R + 2 PAD_ROWS) x (C_ + pad_cols) filled with `fill`; the [R, C_] view of plane 0; elements between planes"""
+    buf = torch.full((planes, R + 2 * PAD_ROWS, C_ + pad_cols), fill, dtype=dtype, device=dev())
+    return buf, buf[0, PAD_ROWS:PAD_ROWS + R, :C_], (R + 2 * PAD_ROWS) * (C_ + pad_cols)
+
+
+def frame_untouched(buf, R, C_):
+    b = buf.float().cpu()
+    edge = torch.cat([b[:, :PAD_ROWS].flatten(), b[:, PAD_ROWS + R:].flatten(), b[:, PAD_ROWS:PAD_ROWS + R, C_:].flatten()])
+    return bool((edge == SENTINEL).all())
+
+
+def flat_framed(n, fill=SENTINEL):
+    buf = torch.full((n + 2 * PAD_FLAT,), fill, device=dev())
+    return buf, buf[PAD_FLAT:PAD_FLAT + n]
+
+
+def flat_untouched(buf):
+    b = buf.cpu()
+    return bool((b[:PAD_FLAT] == SENTINEL).all()) and bool((b[-PAD_FLAT:] == SENTINEL).all())
+
+
+def banned_pairs(L, mask, period):
+    """bool [L, L]: (query i, key j) pairs the mask removes.  Block-causal with period 1 IS no mask and with period L IS the causal mask:
+    those two are written that way, not through the modulo rule"""
+    i, j = np.arange(L)[:, None], np.arange(L)[None, :]
+    if mask == DIAG:
+        return i == j
+    if mask == CAUSAL or (mask == BLOCK and period == L):
+        return j > i
+    if mask == BLOCK and period > 1:
+        return (j % period) > (i % period)
+    return np.zeros((L, L), dtype=bool)
+
+
+def keep_scale(nseq, H, L, p, key):
+    """float64 [nseq, H, L, L]: 0 or 1 / (1 - p) by the replica mask (p as the C float the kernels get)"""
+    if p <= 0:
+        return np.ones((nseq, H, L, L)), None
+    idx = np.arange(nseq * H * L * L, dtype=np.uint64).reshape(nseq, H, L, L)      # ((seq * H + h) * L + i) * L + j
+    keep = kd.drop_keep(key, idx, p)
+    return np.where(keep, 1.0 / (1.0 - float(np.float32(p))), 0.0), keep
+
+
+def reference(q, k, v, do, scale, banned, ks):
+    """float64 [nseq, H, L, hd] operands -> {kind: (value, magnitude sum S)}"""
+    T = lambda x: np.swapaxes(x, -1, -2)      # noqa: E731
+    aq, ak, av, ado = np.abs(q), np.abs(k), np.abs(v), np.abs(do)
+    s = np.where(banned, -np.inf, scale * (q @ T(k)))
+    A = scale * (aq @ T(ak))
+    e = np.exp(s - s.max(-1, keepdims=True))
+    p = e / e.sum(-1, keepdims=True)
+    r = {"probs": (p, p * (1.0 + A + (p * A).sum(-1, keepdims=True)))}
+    pd = p * ks                                # P': after dropout
+    r["out"] = (pd @ v, pd @ av)
+    r["dv"] = (T(pd) @ do, T(pd) @ ado)
+    dp, dpm = (do @ T(v)) * ks, (ado @ T(av)) * ks
+    dot, dotm = (p * dp).sum(-1, keepdims=True), (p * dpm).sum(-1, keepdims=True)
+    ds, dsm = p * (dp - dot) * scale, p * (dpm + dotm) * scale
+    r["dq"] = (ds @ k, dsm @ ak)
+    r["dk"] = (T(ds) @ q, T(dsm) @ aq)
+    return r
+
+
+def rows(x):
+    """[nseq, H, L, hd] -> the [nseq * L, H * hd] layout of the operands"""
+    n, H, L, hd = x.shape
+    return np.ascontiguousarray(x.transpose(0, 2, 1, 3)).reshape(n * L, H * hd)
+
+
+def heads(x, nseq, L, H, hd):
+    return x.reshape(nseq, L, H, hd).transpose(0, 2, 1, 3)
+
+
+def worst_ratio(got, ref, S, u, floor=0.0):
+    """max (|got - ref| - floor) / (u S); where S is 0 the result must be the reference exactly (to the floor)"""
+    got = got.detach().double().cpu().numpy().reshape(ref.shape)
+    err = np.maximum(np.abs(got - ref) - floor, 0.0)
+    if not np.isfinite(got).all() or bool((err[S == 0] != 0).any()):
+        return math.inf
+    nz = S > 0
+    return float((err[nz] / (u * S[nz])).max()) if nz.any() else 0.0
+
+
+def run_case(c):
+    """runs case c -> (ratios {kind: worst |got - ref| / (u S)}, l2 {kind: relative L2}, facts {name: bool})"""
+    from afft_amd import ops
+    nseq, L, H, hd = c.nseq, c.L, c.H, c.hd
+    d, R = H * hd, nseq * L
+    scale = hd ** -0.5
+    split = c.entry == "split"
+    tdt = {"f32": torch.float32, "bf16": torch.bfloat16}.get(c.storage, torch.float16)
+    ci, co = frame_cols(c, False, d), frame_cols(c, True, d)
+    ratios, l2, facts = {}, {}, {}
+
+    # ---- operands: seeded on the CPU, rounded to the storage type; the reference sees the rounded values
+    qkv, dout = rnd(R, 3 * d, seed=1), rnd(R, d, seed=2)
+    nplanes = 2 if c.storage == "f16x2" else 1
+    if split:
+        sp = ops.Split(qkv.to(dev()), f16=True)
+        planes = [sp.planes[i][:R, :3 * d] for i in range(nplanes)]
+        seen = sum(pl.double().cpu() for pl in planes)
+    else:
+        if c.storage == "bf16":
+            qkv, dout = qkv.to(tdt).float(), dout.to(tdt).float()
+        planes, seen = [qkv.to(tdt).to(dev())], qkv.double()
+    ins, in_lo = [], 0
+    for i in range(3):      # q, k, v: each in a NaN frame of its own (planes: hi and lo in one buffer, in_lo elements apart)
+        buf, view, stride = framed(R, d, float("nan"), tdt, ci, nplanes)
+        for pl in range(nplanes):
+            buf[pl, PAD_ROWS:PAD_ROWS + R, :d] = planes[pl][:, i * d:(i + 1) * d]
+        ins.append(view)
+        in_lo = stride if nplanes == 2 else 0
+    q, k, v = ins
+    q64, k64, v64 = (heads(seen[:, i * d:(i + 1) * d].numpy(), nseq, L, H, hd) for i in range(3))
+    ks, keep = keep_scale(nseq, H, L, c.drop_p, KEY)
+    banned = banned_pairs(L, c.mask, c.period)
+    ref = reference(q64, k64, v64, heads(dout.double().numpy(), nseq, L, H, hd), float(np.float32(scale)), banned, ks)
+
+    # ---- forward
+    pbuf, pflat = flat_framed(nseq * H * L * L)
+    probs = pflat.view(nseq, H, L, L)
+    if split:
+        obuf, out, out_lo = framed(R, d, SENTINEL, tdt, co, 2)
+        cbuf, copy, _ = framed(R, d, SENTINEL, torch.bfloat16, co)
+        ops.attention_fwd_split(q, k, v, in_lo, nseq, L, H, hd, scale, c.mask, out, out_lo, copy, probs, drop_p=c.drop_p, drop_key=KEY,
+                                mask_period=c.period)
+        torch.cuda.synchronize()
+        o_ref, o_S = rows(ref["out"][0]), rows(ref["out"][1])
+        hi, lo = obuf[0, PAD_ROWS:PAD_ROWS + R, :d].float().cpu(), obuf[1, PAD_ROWS:PAD_ROWS + R, :d].float().cpu()
+        for kind, got, u in (("out", hi.double() + lo.double(), U["planes"]), ("copy", copy.float().cpu(), U["bf16"]), ("hi", hi, U["hi"])):
+            ratios[kind] = worst_ratio(got, o_ref, o_S, u)
+            l2[kind] = rel_l2(got, torch.from_numpy(o_ref))
+        # fp16 has an absolute floor: a lo part below 2^-14 is subnormal and lands on multiples of 2^-24, off by up to 2^-25 -- once in
+        # the stored lo plane (|out| < 2^-3), once in the lo half of every kept probability (P' < 2^-3), which multiplies |v|
+        floor = 2.0 ** -25 * (1.0 + rows((ref["probs"][0] * ks > 0).astype(np.float64) @ np.abs(v64)))
+        ratios["outf"] = worst_ratio(hi.double() + lo.double(), o_ref, o_S, U["planes"], floor)
+        facts["frames"] = frame_untouched(obuf, R, d) and frame_untouched(cbuf, R, d) and flat_untouched(pbuf)
+    else:
+        obuf, out, _ = framed(R, d, SENTINEL, tdt, co)
+        ops.attention_fwd(q, k, v, nseq, L, H, hd, scale, c.mask, out, probs, drop_p=c.drop_p, drop_key=KEY, mask_period=c.period)
+        torch.cuda.synchronize()
+        ratios["out"] = worst_ratio(out.float(), rows(ref["out"][0]), rows(ref["out"][1]), U[c.storage])
+        l2["out"] = rel_l2(out.float().cpu(), torch.from_numpy(rows(ref["out"][0])))
+        facts["frames"] = frame_untouched(obuf, R, d) and flat_untouched(pbuf)
+    # probs: the PRE-dropout probabilities, exactly 0 at masked pairs (S is 0 there: worst_ratio asks for the reference's 0)
+    ratios["probs"] = worst_ratio(probs, ref["probs"][0], ref["probs"][1], U["f32"])
+    l2["probs"] = rel_l2(probs.cpu(), torch.from_numpy(ref["probs"][0]))
+    facts["masked_probs_zero"] = float(probs.cpu()[..., torch.from_numpy(banned)].abs().sum()) == 0.0
+    if keep is not None:      # the share of kept pairs over the valid ones: 4 standard deviations of the binomial (test_kernel_doubles_cpu.py)
+        valid = keep[..., ~banned]
+        p = float(np.float32(c.drop_p))
+        facts["keep_share"] = abs(float(valid.mean()) - (1.0 - p)) <= 4.0 * math.sqrt(p * (1.0 - p) / valid.size)
+    if split:
+        return ratios, l2, facts
+
+    # ---- backward: on the kernel's own probs, then on the float64 probabilities rounded to fp32
+    _, do, _ = framed(R, d, float("nan"), tdt, ci)
+    do.copy_(dout.to(tdt))
+    rbuf, rflat = flat_framed(nseq * H * L * L)
+    rflat.copy_(torch.from_numpy(ref["probs"][0]).float().flatten())
+    runs = [("own", probs, co), ("ref", rflat.view(nseq, H, L, L), co)]
+    if c.align == "a8":      # the twin on 16-byte aligned, frame-free gradient buffers: the column-sliced kernel
+        runs.append(("twin", probs, 0))
+    for tag, pr, pad in runs:
+        if pad:
+            bufs = [framed(R, d, SENTINEL, tdt, pad) for _ in range(3)]
+        else:
+            bufs = [(None, t, 0) for t in torch.full((3, R, d), SENTINEL, dtype=tdt, device=dev())]
+        ops.attention_bwd(do, q, k, v, pr, nseq, L, H, hd, scale, bufs[0][1], bufs[1][1], bufs[2][1], drop_p=c.drop_p, drop_key=KEY)
+        torch.cuda.synchronize()
+        for kind, (buf, g, _) in zip(("dq", "dk", "dv"), bufs):
+            ratios[f"{kind}/{tag}"] = worst_ratio(g.float(), rows(ref[kind][0]), rows(ref[kind][1]), U[c.storage])
+            if buf is not None:
+                facts["frames"] = facts["frames"] and frame_untouched(buf, R, d)
+        got = torch.cat([b[1].float().cpu() for b in bufs], dim=1)
+        l2["grads/" + tag] = rel_l2(got, torch.from_numpy(np.concatenate([rows(ref[kd_][0]) for kd_ in ("dq", "dk", "dv")], axis=1)))
+    facts["frames"] = facts["frames"] and flat_untouched(pbuf) and flat_untouched(rbuf)
+    return ratios, l2, facts
+
+
+@pytest.mark.parametrize("c", CASES, ids=lambda c: c.name)
+def test_attention_short_case(c):
+    ratios, l2, facts = run_case(c)
+    print(f"attention_short {c.name}: " + " ".join(f"{k} {v:.3g}" for k, v in ratios.items()) + " | L2 "
+          + " ".join(f"{k} {v:.2e}" for k, v in l2.items()))
+    for kind, r in ratios.items():
+        bar = C[path_of(c, kind)][kind.split("/")[0]]
+        assert r <= bar, f"{c.name}: {kind} is off by {r:.3g} u S, the bar is {bar}"
+    bars = L2["split" if c.entry == "split" else c.storage]
+    for kind, e in l2.items():
+        assert e < bars[kind.split("/")[0]], (c.name, kind, e)
+    assert all(facts.values()), (c.name, facts)
