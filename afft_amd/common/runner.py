@@ -40,27 +40,51 @@ def accuracy(output, target, topk=(1,)):
 
 
 class MultiDimCrossEntropy(nn.Module):
-    """Flattens the leading dimensions, then per-row cross entropy (reduction='none', ignore_index=-1)."""
+    """Flattens the leading dimensions, then per-row cross entropy (reduction='none', ignore_index=-1).
+    weight ([C], any float type) / label_smoothing: as in nn.CrossEntropyLoss, which the reference's criterion is -- applied to hard
+    labels, soft (MixUp) targets and the boolean row filter alike; nothing is divided by the labels' weights (reduction='none': the
+    Runner takes the mean over rows).  With neither, the kernel calls are those of the plain loss."""
 
-    def __init__(self, ignore_index: int = -1, reduction: str = 'none'):
+    def __init__(self, ignore_index: int = -1, reduction: str = 'none', weight: Optional[torch.Tensor] = None,
+                 label_smoothing: float = 0.0):
         super().__init__()
         assert ignore_index == -1 and reduction == 'none', "the AFFT path uses ignore_index=-1, reduction='none'"
+        if not 0.0 <= float(label_smoothing) <= 1.0:
+            raise ValueError(f"label_smoothing must lie in [0, 1], got {label_smoothing}")
+        if weight is not None:
+            weight = torch.as_tensor(weight)
+            assert weight.dim() == 1, "weight: one entry per class"
+        self.register_buffer('weight', weight)
+        self.label_smoothing = float(label_smoothing)
+
+    def _options(self, inp):
+        """() for the plain loss -- SoftmaxCE.apply then takes its five arguments, as before --, else (weight, smoothing) with the
+        weight as the kernel wants it: fp32, contiguous, on the logits' device (converted once, at first use)"""
+        if self.weight is None and self.label_smoothing == 0.0:
+            return ()
+        w = self.weight
+        if w is not None:
+            assert w.numel() == inp.size(-1), f"weight has {w.numel()} entries, the logits {inp.size(-1)} classes"
+            if w.dtype != torch.float32 or w.device != inp.device or not w.is_contiguous():
+                w = self.weight = w.to(device=inp.device, dtype=torch.float32).contiguous()
+        return (w, self.label_smoothing)
 
     def forward(self, inp, tgt, one_hot: bool = False, ignore_index: Union[torch.Tensor, None] = None):
         C = inp.size(-1)
         landing = getattr(inp, "_afft_landing", None)
+        opts = self._options(inp)
         # a (clips, frames, C) view with contiguous classes (one half of the merged classifier output) is walked where it lies;
         # anything else is flattened to rows (a copy when the leading dimensions do not collapse)
         inp2 = inp if (inp.dim() == 3 and inp.stride(2) == 1 and inp.dtype == torch.float32) else inp.reshape(-1, C)
         rows = inp.numel() // C
         if not one_hot:
             labels = tgt.reshape(-1).to(torch.int64).contiguous()
-            return F_.SoftmaxCE.apply(inp2, labels, None, None, landing)
+            return F_.SoftmaxCE.apply(inp2, labels, None, None, landing, *opts)
         soft = tgt.reshape(-1, C).to(torch.float32).contiguous()
         keep = None
         if ignore_index is not None:
             keep = (~ignore_index.reshape(-1)).to(torch.uint8).contiguous()
-        row_loss = F_.SoftmaxCE.apply(inp2, None, soft, keep, landing)
+        row_loss = F_.SoftmaxCE.apply(inp2, None, soft, keep, landing, *opts)
         if keep is not None:
             row_loss = row_loss * (float(rows) / keep.sum().clamp(min=1).to(torch.float32))
         return row_loss
@@ -69,9 +93,16 @@ class MultiDimCrossEntropy(nn.Module):
 class BasicLossAccuracy(nn.Module):
     """acc1 / acc5 / mt5r inputs and the three loss terms."""
 
-    def __init__(self, compute_metrics: bool = True, lazy_host: bool = False, device_metrics: bool = False):
+    def __init__(self, compute_metrics: bool = True, lazy_host: bool = False, device_metrics: bool = False,
+                 cls_weight: Optional[Dict[str, torch.Tensor]] = None, label_smoothing: float = 0.0):
+        """cls_weight: target type ('action', 'verb', ...) -> [C] class weights (common.class_weights.class_weights makes them from
+        counts); a type that is missing has none.  label_smoothing applies to every type.  One criterion per target type serves its
+        future and its past term; cls_criterion (no weights) serves the types cls_weight does not name."""
         super().__init__()
-        self.cls_criterion = MultiDimCrossEntropy(ignore_index=-1, reduction='none')
+        self.cls_criterion = MultiDimCrossEntropy(ignore_index=-1, reduction='none', label_smoothing=label_smoothing)
+        self.cls_criteria = nn.ModuleDict({
+            t: MultiDimCrossEntropy(ignore_index=-1, reduction='none', weight=w, label_smoothing=label_smoothing)
+            for t, w in (cls_weight or {}).items() if w is not None})
         self.compute_metrics = compute_metrics
         self.lazy_host = lazy_host        # host copies of the logits / labels as LazyHostArray instead of a blocking .cpu()
         self.device_metrics = device_metrics    # label ranks by ops.label_rank: nothing of width C is cloned or leaves the device
@@ -87,9 +118,12 @@ class BasicLossAccuracy(nn.Module):
         a, b = a[:, skip:], b[:, skip:]
         return F_.MSE.apply(a.reshape(-1, C).contiguous(), b.reshape(-1, C).contiguous())
 
+    def criterion_for(self, tgt_type: Optional[str]):
+        return self.cls_criteria[tgt_type] if tgt_type in self.cls_criteria else self.cls_criterion
+
     def forward_future_action(self, logits, tgt_val, mixup_enable, losses, metrics, acc1_key, acc5_key, mt5r_key,
-                              loss_key, key_suffix=''):
-        losses[loss_key + key_suffix] = self.cls_criterion(logits, tgt_val, one_hot=mixup_enable)
+                              loss_key, key_suffix='', tgt_type: Optional[str] = None):
+        losses[loss_key + key_suffix] = self.criterion_for(tgt_type)(logits, tgt_val, one_hot=mixup_enable)
         if not self.compute_metrics:
             return
         sequence_index = 0
@@ -148,15 +182,16 @@ class BasicLossAccuracy(nn.Module):
         metrics[acc5_key] = acc[1]
 
     def forward_past_action(self, past_logits, past_target, mixup_enable, losses, loss_key,
-                            past_target_ignore_index=None, key_suffix=''):
+                            past_target_ignore_index=None, key_suffix='', tgt_type: Optional[str] = None):
+        criterion = self.criterion_for(tgt_type)
         if mixup_enable:
             assert past_logits.shape == past_target.shape
             assert past_target_ignore_index is not None
-            loss = self.cls_criterion(past_logits, past_target, one_hot=True, ignore_index=past_target_ignore_index)
+            loss = criterion(past_logits, past_target, one_hot=True, ignore_index=past_target_ignore_index)
         else:
             past_target = past_target.squeeze(-1)
             assert past_logits.shape[:-1] == past_target.shape
-            loss = self.cls_criterion(past_logits, past_target)
+            loss = criterion(past_logits, past_target)
         losses[loss_key + key_suffix] = loss
 
     def forward(self, outputs, target, target_subclips, mixup_enable: bool = False,
@@ -168,13 +203,13 @@ class BasicLossAccuracy(nn.Module):
                 assert len(logits.shape) == 3
                 self.forward_future_action(logits, tgt_val, mixup_enable, losses, metrics,
                                            f'acc1_{tgt_type}_{modk}', f'acc5_{tgt_type}_{modk}',
-                                           f'mt5r_{tgt_type}_{modk}', f'cls_{tgt_type}_{modk}')
+                                           f'mt5r_{tgt_type}_{modk}', f'cls_{tgt_type}_{modk}', tgt_type=tgt_type)
             past_key = f'{PAST_LOGITS_PREFIX}logits/{tgt_type}'
             if past_key in outputs and target_subclips is not None:
                 for modk in outputs[past_key]:
                     ign = None if target_subclips_ignore_index is None else target_subclips_ignore_index[tgt_type]
                     self.forward_past_action(outputs[past_key][modk], target_subclips[tgt_type], mixup_enable,
-                                             losses, f'past_cls_{tgt_type}_{modk}', ign)
+                                             losses, f'past_cls_{tgt_type}_{modk}', ign, tgt_type=tgt_type)
             if 'orig_past' in outputs and 'past_futures' in outputs:
                 for modk, upd in outputs['past_futures'].items():
                     if modk not in outputs['orig_past']:
@@ -372,9 +407,12 @@ class Runner:
     device_metrics (None: AFFT_DEVICE_METRICS=1, or afft_amd.install_as_models(device_metrics=True); off by default): acc1 / acc5
       are 0-dim device tensors and the recall meter's entry is {'rank', 'labels', 'k'} -- device vectors of length B from one
       ops.label_rank call, for afft_amd.common.metric_tracking.MeanTopKRecallMeter; the (B, C) logits are neither cloned nor copied
-      to the host.  Logits that are not on the GPU take the host path whatever this says."""
+      to the host.  Logits that are not on the GPU take the host path whatever this says.
+    cls_weight ({target type: [C] class weights}) / label_smoothing: nn.CrossEntropyLoss's weight= and label_smoothing= for the future
+      and past classification terms (BasicLossAccuracy); the defaults leave the loss and its kernel calls as they were."""
 
-    def __init__(self, model, device, loss_wts, compute_metrics: bool = True, async_metrics=None, device_metrics=None):
+    def __init__(self, model, device, loss_wts, compute_metrics: bool = True, async_metrics=None, device_metrics=None,
+                 cls_weight: Optional[Dict[str, torch.Tensor]] = None, label_smoothing: float = 0.0):
         import os
         if async_metrics is None:
             async_metrics = False if os.environ.get("AFFT_RUNNER_SYNC", "0") == "1" else "lazy"
@@ -384,7 +422,8 @@ class Runner:
         self.model = model
         self.device = device
         self.device_metrics = bool(device_metrics)
-        self.loss_acc_fn = BasicLossAccuracy(compute_metrics, lazy_host=bool(async_metrics), device_metrics=self.device_metrics)
+        self.loss_acc_fn = BasicLossAccuracy(compute_metrics, lazy_host=bool(async_metrics), device_metrics=self.device_metrics,
+                                             cls_weight=cls_weight, label_smoothing=label_smoothing)
         self.loss_wts = loss_wts
         self.async_metrics = async_metrics
 

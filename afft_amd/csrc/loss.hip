@@ -16,6 +16,17 @@ __device__ __forceinline__ float block_reduce(float v, float* sh, bool is_max) {
   return r;
 }
 
+// a_c of the weighted / smoothed cross-entropy (include/afft_hip.h): soft target t: w_c ((1 - eps) t_c + eps / C); hard label y:
+// (eps / C) w_c + (1 - eps) w_y [c == y] (own = (1 - eps) w_y, 0 for a label out of range).  w NULL = all ones.
+__device__ __forceinline__ float ce_coef(const float* __restrict__ w, const float* __restrict__ t, int c, int64_t lab, float unif,
+                                         float sharp, float own) {
+  const float wc = w ? w[c] : 1.f;
+  return t ? wc * (sharp * t[c] + unif) : unif * wc + (c == lab ? own : 0.f);
+}
+
+// W = false: plain cross-entropy (no class weights, no smoothing; `weight` and `smoothing` are not read).  W = true: the row's
+// per-class coefficient a_c (ce_coef), A = sum_c a_c:  loss = lse * A - sum_c a_c x_c,  dloss/dx_j = p_j * A - a_j.
+template <bool W>
 __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict__ logits, int64_t ldl, int C,
                                                          const int64_t* __restrict__ labels,
                                                          const float* __restrict__ soft, int64_t lds,
@@ -23,7 +34,8 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
                                                          const float* __restrict__ row_g,
                                                          void* __restrict__ dlogits,
                                                          int64_t ldd, int d_dtype, float* __restrict__ row_loss,
-                                                         int period, int64_t lgs, int64_t dgs) {
+                                                         int period, int64_t lgs, int64_t dgs,
+                                                         const float* __restrict__ weight, float smoothing) {
   // row r = frame r % period of clip r / period: logits at clip * lgs + frame * ldl, its gradient at clip * dgs + frame * ldd
   // (a (B, n, C) slice of a wider (B, L, C) tensor is walked where it lies; period = rows: plain [rows, C])
   __shared__ float sh[4];
@@ -46,8 +58,39 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
   float m = -INFINITY;
   for (int c = tid; c < C; c += 256) m = fmaxf(m, x[c]);
   m = block_reduce(m, sh, true);
-  float se = 0.f, tsum = 0.f, tx = 0.f;
   const float* t = soft ? soft + (int64_t)row * lds : nullptr;
+  if constexpr (W) {
+    // smoothing / C for every class, (1 - smoothing) on the target; the label's own weight is ONE load, and a label out of range reads
+    // none.  weight (<= 15 KB at C = 3806) is read in the same column loops as x and stays in cache.
+    const float unif = smoothing / (float)C, sharp = 1.f - smoothing;
+    const float own = t || bad ? 0.f : sharp * (weight ? weight[lab] : 1.f);
+    float se = 0.f, asum = 0.f, ax = 0.f;
+    for (int c = tid; c < C; c += 256) {
+      se += expf(x[c] - m);
+      const float a = ce_coef(weight, t, c, lab, unif, sharp, own);
+      asum += a;
+      ax += a * x[c];
+    }
+    se = block_reduce(se, sh, false);
+    asum = block_reduce(asum, sh, false);
+    ax = block_reduce(ax, sh, false);
+    const float lse = m + logf(se);
+    if (tid == 0 && row_loss) row_loss[row] = bad ? NAN : lse * asum - ax;
+    if (dlogits) {
+      const float inv = 1.0f / se;
+      if (row_g) gscale *= row_g[row];
+      for (int c = tid; c < ldd; c += 256) {
+        float g = 0.f;
+        if (c < C) {
+          const float p = expf(x[c] - m) * inv;
+          g = bad ? NAN : gscale * (p * asum - ce_coef(weight, t, c, lab, unif, sharp, own));
+        }
+        st_any(dlogits, drow + c, d_dtype, g);
+      }
+    }
+    return;
+  }
+  float se = 0.f, tsum = 0.f, tx = 0.f;
   for (int c = tid; c < C; c += 256) {
     se += expf(x[c] - m);
     if (t) { tsum += t[c]; tx += t[c] * x[c]; }
@@ -214,8 +257,8 @@ extern "C" int afft_softmax_ce(const float* logits, int64_t ldl, int32_t rows, i
   AFFT_CHECK(C > 0 && ldl >= C && (!dlogits || ldd >= C), "softmax_ce: bad sizes");
   AFFT_CHECK(!loss_sum || row_loss, "softmax_ce: loss_sum is the ordered sum of row_loss: give row_loss as well");
   if (rows == 0) return 0;
-  hipLaunchKernelGGL(softmax_ce_kernel, dim3(rows), dim3(256), 0, stream, logits, ldl, C, labels, soft, lds, keep,
-                     gscale, row_g, dlogits, ldd, d_dtype, row_loss, rows, (int64_t)0, (int64_t)0);
+  hipLaunchKernelGGL(softmax_ce_kernel<false>, dim3(rows), dim3(256), 0, stream, logits, ldl, C, labels, soft, lds, keep,
+                     gscale, row_g, dlogits, ldd, d_dtype, row_loss, rows, (int64_t)0, (int64_t)0, (const float*)nullptr, 0.f);
   AFFT_LAUNCH_CHECK();
   if (loss_sum) {
     hipLaunchKernelGGL(ordered_sum_kernel, dim3(1), dim3(256), 0, stream, row_loss, (int64_t)rows, 1.0f, loss_sum, 1);
@@ -233,8 +276,51 @@ extern "C" int afft_softmax_ce_frames(const float* logits, int64_t clip_stride, 
   AFFT_CHECK((labels != nullptr) != (soft != nullptr), "softmax_ce_frames: give exactly one of labels / soft targets");
   AFFT_CHECK(C > 0 && ldl >= C && (!dlogits || ldd >= C) && frames > 0, "softmax_ce_frames: bad sizes");
   if (clips == 0) return 0;
-  hipLaunchKernelGGL(softmax_ce_kernel, dim3(clips * frames), dim3(256), 0, stream, logits, ldl, C, labels, soft, lds, keep,
-                     gscale, row_g, dlogits, ldd, d_dtype, row_loss, frames, clip_stride, d_clip_stride);
+  hipLaunchKernelGGL(softmax_ce_kernel<false>, dim3(clips * frames), dim3(256), 0, stream, logits, ldl, C, labels, soft, lds, keep,
+                     gscale, row_g, dlogits, ldd, d_dtype, row_loss, frames, clip_stride, d_clip_stride, (const float*)nullptr, 0.f);
+  AFFT_LAUNCH_CHECK();
+  return 0;
+}
+
+// Class weights and label smoothing.  A null weight with smoothing == 0 IS the plain loss: the sibling's launch, the sibling's bits.
+extern "C" int afft_softmax_ce_w(const float* logits, int64_t ldl, int32_t rows, int32_t C, const int64_t* labels,
+                                 const float* soft, int64_t lds, const uint8_t* keep, float gscale, const float* row_g,
+                                 float* loss_sum, void* dlogits, int64_t ldd, int32_t d_dtype, float* row_loss,
+                                 const float* weight, float smoothing, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  AFFT_CHECK(smoothing >= 0.f && smoothing <= 1.f, "softmax_ce_w: smoothing must lie in [0, 1] (got %g)", (double)smoothing);
+  if (!weight && smoothing == 0.f)
+    return afft_softmax_ce(logits, ldl, rows, C, labels, soft, lds, keep, gscale, row_g, loss_sum, dlogits, ldd, d_dtype, row_loss, stream_);
+  AFFT_CHECK(logits, "softmax_ce_w: null logits");
+  AFFT_CHECK((labels != nullptr) != (soft != nullptr), "softmax_ce_w: give exactly one of labels / soft targets");
+  AFFT_CHECK(C > 0 && ldl >= C && (!dlogits || ldd >= C), "softmax_ce_w: bad sizes");
+  AFFT_CHECK(!loss_sum || row_loss, "softmax_ce_w: loss_sum is the ordered sum of row_loss: give row_loss as well");
+  if (rows == 0) return 0;
+  hipLaunchKernelGGL(softmax_ce_kernel<true>, dim3(rows), dim3(256), 0, stream, logits, ldl, C, labels, soft, lds, keep,
+                     gscale, row_g, dlogits, ldd, d_dtype, row_loss, rows, (int64_t)0, (int64_t)0, weight, smoothing);
+  AFFT_LAUNCH_CHECK();
+  if (loss_sum) {
+    hipLaunchKernelGGL(ordered_sum_kernel, dim3(1), dim3(256), 0, stream, row_loss, (int64_t)rows, 1.0f, loss_sum, 1);
+    AFFT_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+extern "C" int afft_softmax_ce_frames_w(const float* logits, int64_t clip_stride, int64_t ldl, int32_t clips, int32_t frames, int32_t C,
+                                        const int64_t* labels, const float* soft, int64_t lds, const uint8_t* keep, float gscale,
+                                        const float* row_g, void* dlogits, int64_t d_clip_stride, int64_t ldd, int32_t d_dtype,
+                                        float* row_loss, const float* weight, float smoothing, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  AFFT_CHECK(smoothing >= 0.f && smoothing <= 1.f, "softmax_ce_frames_w: smoothing must lie in [0, 1] (got %g)", (double)smoothing);
+  if (!weight && smoothing == 0.f)
+    return afft_softmax_ce_frames(logits, clip_stride, ldl, clips, frames, C, labels, soft, lds, keep, gscale, row_g, dlogits,
+                                  d_clip_stride, ldd, d_dtype, row_loss, stream_);
+  AFFT_CHECK(logits, "softmax_ce_frames_w: null logits");
+  AFFT_CHECK((labels != nullptr) != (soft != nullptr), "softmax_ce_frames_w: give exactly one of labels / soft targets");
+  AFFT_CHECK(C > 0 && ldl >= C && (!dlogits || ldd >= C) && frames > 0, "softmax_ce_frames_w: bad sizes");
+  if (clips == 0) return 0;
+  hipLaunchKernelGGL(softmax_ce_kernel<true>, dim3(clips * frames), dim3(256), 0, stream, logits, ldl, C, labels, soft, lds, keep,
+                     gscale, row_g, dlogits, ldd, d_dtype, row_loss, frames, clip_stride, d_clip_stride, weight, smoothing);
   AFFT_LAUNCH_CHECK();
   return 0;
 }

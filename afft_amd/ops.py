@@ -576,6 +576,63 @@ def softmax_ce_frames(logits3: Tensor, C_: int, *, labels: Optional[Tensor] = No
                                            _dt(dlogits3) if dlogits3 is not None else 0, _p(row_loss), _stream()), "softmax_ce_frames")
 
 
+def _ce_weight(weight: Optional[Tensor], C_: int, logits: Tensor):
+    """the checks softmax_ce_w / softmax_ce_frames_w add to their siblings' (the library itself refuses a smoothing outside [0, 1])"""
+    if weight is not None:
+        if weight.dtype != torch.float32 or not weight.is_contiguous() or weight.numel() != C_:
+            raise ValueError(f"afft_amd: class weights must be a contiguous fp32 vector of {C_} entries, got {weight.dtype} "
+                             f"{tuple(weight.shape)} {weight.stride()}")
+        if weight.device != logits.device:
+            raise ValueError(f"afft_amd: class weights live on {weight.device}, the logits on {logits.device}")
+
+
+def softmax_ce_w(logits: Tensor, C_: int, *, labels: Optional[Tensor] = None, soft: Optional[Tensor] = None,
+                 keep: Optional[Tensor] = None, gscale: float = 1.0, row_g: Optional[Tensor] = None,
+                 loss_sum: Optional[Tensor] = None, dlogits: Optional[Tensor] = None, row_loss: Optional[Tensor] = None,
+                 weight: Optional[Tensor] = None, smoothing: float = 0.0):
+    """softmax_ce with class weights (fp32 [C] on the logits' device, None = ones) and label smoothing in [0, 1]
+    (afft_softmax_ce_w: the formulas are in include/afft_hip.h).  weight None and smoothing 0 run softmax_ce's kernel."""
+    rows = logits.shape[0]
+    assert logits.dtype == torch.float32
+    if labels is not None:
+        assert labels.dtype == torch.int64 and labels.numel() == rows and labels.is_contiguous()
+    if soft is not None:
+        assert soft.dtype == torch.float32 and soft.shape[0] == rows
+    if keep is not None:
+        assert keep.dtype == torch.uint8 and keep.numel() == rows
+    _ce_weight(weight, C_, logits)
+    L.check(L.lib().afft_softmax_ce_w(_p(logits), _rowmajor(logits, "logits"), rows, C_, _p(labels), _p(soft),
+                                      _rowmajor(soft, "soft") if soft is not None else 0, _p(keep), gscale,
+                                      _p(row_g), _p(loss_sum), _p(dlogits),
+                                      _rowmajor(dlogits, "dlogits") if dlogits is not None else 0,
+                                      _dt(dlogits) if dlogits is not None else 0, _p(row_loss), _p(weight), float(smoothing),
+                                      _stream()), "softmax_ce_w")
+
+
+def softmax_ce_frames_w(logits3: Tensor, C_: int, *, labels: Optional[Tensor] = None, soft: Optional[Tensor] = None,
+                        keep: Optional[Tensor] = None, row_g: Optional[Tensor] = None, dlogits3: Optional[Tensor] = None,
+                        row_loss: Optional[Tensor] = None, weight: Optional[Tensor] = None, smoothing: float = 0.0):
+    """softmax_ce_frames with class weights and label smoothing (afft_softmax_ce_frames_w), as softmax_ce_w"""
+    clips, frames = logits3.shape[0], logits3.shape[1]
+    assert logits3.dtype == torch.float32 and logits3.dim() == 3 and logits3.stride(2) == 1
+    rows = clips * frames
+    if labels is not None:
+        assert labels.dtype == torch.int64 and labels.numel() == rows and labels.is_contiguous()
+    if soft is not None:
+        assert soft.dtype == torch.float32 and soft.shape[0] == rows
+    if keep is not None:
+        assert keep.dtype == torch.uint8 and keep.numel() == rows
+    if dlogits3 is not None:
+        assert dlogits3.dim() == 3 and dlogits3.shape[:2] == logits3.shape[:2] and dlogits3.stride(2) == 1
+    _ce_weight(weight, C_, logits3)
+    L.check(L.lib().afft_softmax_ce_frames_w(_p(logits3), logits3.stride(0), logits3.stride(1), clips, frames, C_, _p(labels), _p(soft),
+                                             _rowmajor(soft, "soft") if soft is not None else 0, _p(keep), 1.0, _p(row_g),
+                                             _p(dlogits3), dlogits3.stride(0) if dlogits3 is not None else 0,
+                                             dlogits3.stride(1) if dlogits3 is not None else 0,
+                                             _dt(dlogits3) if dlogits3 is not None else 0, _p(row_loss), _p(weight), float(smoothing),
+                                             _stream()), "softmax_ce_frames_w")
+
+
 def loss_reduce(vals, weights, means: Optional[Tensor], total: Tensor):
     """means[i] = mean(vals[i]), total[0] = sum_i weights[i] * means[i]: Runner._reduce_loss in one launch (afft_loss_reduce)"""
     n = len(vals)

@@ -433,6 +433,26 @@ int afft_softmax_ce(const float* logits, int64_t ldl, int32_t rows, int32_t C, c
 int afft_softmax_ce_frames(const float* logits, int64_t clip_stride, int64_t ldl, int32_t clips, int32_t frames, int32_t C,
                            const int64_t* labels, const float* soft, int64_t lds, const uint8_t* keep, float gscale, const float* row_g,
                            void* dlogits, int64_t d_clip_stride, int64_t ldd, int32_t d_dtype, float* row_loss, void* stream);
+/* Both with class weights and label smoothing (what nn.CrossEntropyLoss(weight=, label_smoothing=, reduction='none') adds).
+ * weight: fp32 [C], contiguous, NULL = all ones; smoothing eps in [0, 1] (anything else, NaN included, is a host error before any launch).
+ * With x a row of logits, lse = logsumexp(x), p = softmax(x), the row has one coefficient per class,
+ *   hard label y != -1:  a_c = (eps / C) w_c + (1 - eps) w_y [c == y]
+ *   soft target t:       a_c = w_c ((1 - eps) t_c + eps / C)          (ignore_index plays no part, as in torch)
+ * and, with A = sum_c a_c,
+ *   row_loss = lse * A - sum_c a_c x_c        dlogits[j] = gscale * row_g * (p_j * A - a_j).
+ * Nothing is divided by sum w_y: the reduction is 'none', the caller takes the mean over rows.  Ignored rows (label -1, keep == 0) give
+ * loss 0 and a zero gradient row; a label outside [-1, C) gives a NaN row and reads nothing out of bounds, weight included; a row whose
+ * A is 0 (eps == 0 and a label, or every class of a soft target, of weight 0) gives exactly 0.  Everything else -- row addressing, keep, gscale, row_g, row_loss,
+ * loss_sum, d_dtype, the zeroed columns C..ldd-1 -- is the sibling's.  Three fixed-order block sums, no atomics: same inputs, same bits.
+ * weight == NULL with smoothing == 0 runs the sibling's kernel and returns its bits. */
+int afft_softmax_ce_w(const float* logits, int64_t ldl, int32_t rows, int32_t C, const int64_t* labels,
+                      const float* soft, int64_t lds, const uint8_t* keep, float gscale, const float* row_g,
+                      float* loss_sum, void* dlogits, int64_t ldd, int32_t d_dtype, float* row_loss,
+                      const float* weight, float smoothing, void* stream);
+int afft_softmax_ce_frames_w(const float* logits, int64_t clip_stride, int64_t ldl, int32_t clips, int32_t frames, int32_t C,
+                             const int64_t* labels, const float* soft, int64_t lds, const uint8_t* keep, float gscale, const float* row_g,
+                             void* dlogits, int64_t d_clip_stride, int64_t ldd, int32_t d_dtype, float* row_loss,
+                             const float* weight, float smoothing, void* stream);
 /* Runner._reduce_loss (common/runner.py:198-213) in one launch: term i = n[i] fp32 per-row losses at x[i] (HOST arrays of nterms <= 8
  * device pointers / counts / weights); means[i] = mean(x[i]) (may be NULL), total[0] = sum_i w[i] * means[i], in a fixed order (bit-stable).
  * afft_loss_reduce_bwd: g[i][0 .. n[i]) = g_total[0] * w[i] / n[i] (g_total NULL = 1; g[i] NULL skips a term): the upstream
