@@ -1,5 +1,6 @@
 """Class weights for the weighted cross-entropy (MultiDimCrossEntropy(weight=...), Runner(cls_weight=...)) from per-class sample
-counts.  Host arithmetic only."""
+counts, and the logit adjustment (MultiDimCrossEntropy(logit_adjust=...), Runner(logit_adjust=...)) from the same counts.  Host
+arithmetic only."""
 from __future__ import annotations
 
 import numpy as np
@@ -30,3 +31,21 @@ def class_weights(counts, scheme: str = 'inverse', power: float = 1.0, beta: flo
     else:
         raise ValueError(f"class_weights: unknown scheme {scheme!r} ('inverse' or 'effective')")
     return w * (n.sum() / np.dot(n, w))
+
+
+def logit_adjustment(counts, tau: float = 1.0) -> np.ndarray:
+    """counts: [C] non-negative sample counts per class.  Returns float32 [C]: tau * log(counts_c / sum(counts)), the logit adjustment
+    of Menon et al. 2021 (tau = 1: "balanced softmax") for MultiDimCrossEntropy(logit_adjust=...) / Runner(logit_adjust={type: ...}).
+
+    A class without samples takes the smallest positive count present: log 0 would be -inf, and the kernel wants finite entries;
+    such a class is then treated as the rarest class seen (the total in the denominator stays the true sum of the counts)."""
+    n = np.asarray(counts, dtype=np.float64).reshape(-1)
+    if n.size == 0 or not np.all(np.isfinite(n)) or np.any(n < 0):
+        raise ValueError("logit_adjustment: counts must be finite and non-negative, one per class")
+    if not np.isfinite(tau):
+        raise ValueError(f"logit_adjustment: tau must be finite, got {tau}")
+    seen = n > 0
+    if not seen.any():
+        raise ValueError("logit_adjustment: every count is 0")
+    filled = np.where(seen, n, n[seen].min())
+    return (float(tau) * np.log(filled / n.sum())).astype(np.float32)

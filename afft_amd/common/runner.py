@@ -43,31 +43,50 @@ class MultiDimCrossEntropy(nn.Module):
     """Flattens the leading dimensions, then per-row cross entropy (reduction='none', ignore_index=-1).
     weight ([C], any float type) / label_smoothing: as in nn.CrossEntropyLoss, which the reference's criterion is -- applied to hard
     labels, soft (MixUp) targets and the boolean row filter alike; nothing is divided by the labels' weights (reduction='none': the
-    Runner takes the mean over rows).  With neither, the kernel calls are those of the plain loss."""
+    Runner takes the mean over rows).  With neither, the kernel calls are those of the plain loss.
+    focal_gamma (>= 0, finite): the focal loss's exponent, rows the model already gets right count for less.  logit_adjust ([C], any
+    float type; common.class_weights.logit_adjustment makes tau * log prior from counts): added to the logits INSIDE the loss only --
+    the caller's logits, and with them every metric and the evaluation, stay raw.  It is a plain attribute, not a buffer: it is no
+    part of the state dict, and is brought to the logits' device at first use.  With gamma 0 and no adjustment the calls are those of
+    the weighted / plain loss."""
 
     def __init__(self, ignore_index: int = -1, reduction: str = 'none', weight: Optional[torch.Tensor] = None,
-                 label_smoothing: float = 0.0):
+                 label_smoothing: float = 0.0, focal_gamma: float = 0.0, logit_adjust: Optional[torch.Tensor] = None):
         super().__init__()
         assert ignore_index == -1 and reduction == 'none', "the AFFT path uses ignore_index=-1, reduction='none'"
         if not 0.0 <= float(label_smoothing) <= 1.0:
             raise ValueError(f"label_smoothing must lie in [0, 1], got {label_smoothing}")
+        if not 0.0 <= float(focal_gamma) < float('inf'):
+            raise ValueError(f"focal_gamma must be finite and >= 0, got {focal_gamma}")
         if weight is not None:
             weight = torch.as_tensor(weight)
             assert weight.dim() == 1, "weight: one entry per class"
+        if logit_adjust is not None:
+            logit_adjust = torch.as_tensor(logit_adjust)
+            assert logit_adjust.dim() == 1, "logit_adjust: one entry per class"
         self.register_buffer('weight', weight)
         self.label_smoothing = float(label_smoothing)
+        self.focal_gamma = float(focal_gamma)
+        self.logit_adjust = logit_adjust
+
+    def _as_kernel_vector(self, name, inp):
+        """the [C] vector `name` as the kernel wants it: fp32, contiguous, on the logits' device (converted once, at first use)"""
+        v = getattr(self, name)
+        if v is not None:
+            assert v.numel() == inp.size(-1), f"{name} has {v.numel()} entries, the logits {inp.size(-1)} classes"
+            if v.dtype != torch.float32 or v.device != inp.device or not v.is_contiguous():
+                v = v.to(device=inp.device, dtype=torch.float32).contiguous()
+                setattr(self, name, v)
+        return v
 
     def _options(self, inp):
-        """() for the plain loss -- SoftmaxCE.apply then takes its five arguments, as before --, else (weight, smoothing) with the
-        weight as the kernel wants it: fp32, contiguous, on the logits' device (converted once, at first use)"""
-        if self.weight is None and self.label_smoothing == 0.0:
+        """() for the plain loss -- SoftmaxCE.apply then takes its five arguments, as before --, else (weight, smoothing), and with a
+        focal exponent or a logit adjustment (weight, smoothing, adjust, gamma)"""
+        focal = self.logit_adjust is not None or self.focal_gamma != 0.0
+        if self.weight is None and self.label_smoothing == 0.0 and not focal:
             return ()
-        w = self.weight
-        if w is not None:
-            assert w.numel() == inp.size(-1), f"weight has {w.numel()} entries, the logits {inp.size(-1)} classes"
-            if w.dtype != torch.float32 or w.device != inp.device or not w.is_contiguous():
-                w = self.weight = w.to(device=inp.device, dtype=torch.float32).contiguous()
-        return (w, self.label_smoothing)
+        opts = (self._as_kernel_vector('weight', inp), self.label_smoothing)
+        return opts + (self._as_kernel_vector('logit_adjust', inp), self.focal_gamma) if focal else opts
 
     def forward(self, inp, tgt, one_hot: bool = False, ignore_index: Union[torch.Tensor, None] = None):
         C = inp.size(-1)
@@ -94,15 +113,22 @@ class BasicLossAccuracy(nn.Module):
     """acc1 / acc5 / mt5r inputs and the three loss terms."""
 
     def __init__(self, compute_metrics: bool = True, lazy_host: bool = False, device_metrics: bool = False,
-                 cls_weight: Optional[Dict[str, torch.Tensor]] = None, label_smoothing: float = 0.0):
+                 cls_weight: Optional[Dict[str, torch.Tensor]] = None, label_smoothing: float = 0.0,
+                 focal_gamma: float = 0.0, logit_adjust: Optional[Dict[str, torch.Tensor]] = None):
         """cls_weight: target type ('action', 'verb', ...) -> [C] class weights (common.class_weights.class_weights makes them from
-        counts); a type that is missing has none.  label_smoothing applies to every type.  One criterion per target type serves its
-        future and its past term; cls_criterion (no weights) serves the types cls_weight does not name."""
+        counts); a type that is missing has none.  logit_adjust: target type -> [C] logit adjustment (common.class_weights.
+        logit_adjustment), likewise; it enters the loss only, the metrics below see the raw logits.  label_smoothing and focal_gamma
+        apply to every type.  One criterion per target type serves its future and its past term; cls_criterion (no weights, no
+        adjustment) serves the types neither dictionary names."""
         super().__init__()
-        self.cls_criterion = MultiDimCrossEntropy(ignore_index=-1, reduction='none', label_smoothing=label_smoothing)
+        cls_weight = {t: w for t, w in (cls_weight or {}).items() if w is not None}
+        logit_adjust = {t: b for t, b in (logit_adjust or {}).items() if b is not None}
+        self.cls_criterion = MultiDimCrossEntropy(ignore_index=-1, reduction='none', label_smoothing=label_smoothing,
+                                                  focal_gamma=focal_gamma)
         self.cls_criteria = nn.ModuleDict({
-            t: MultiDimCrossEntropy(ignore_index=-1, reduction='none', weight=w, label_smoothing=label_smoothing)
-            for t, w in (cls_weight or {}).items() if w is not None})
+            t: MultiDimCrossEntropy(ignore_index=-1, reduction='none', weight=cls_weight.get(t), label_smoothing=label_smoothing,
+                                    focal_gamma=focal_gamma, logit_adjust=logit_adjust.get(t))
+            for t in list(cls_weight) + [t for t in logit_adjust if t not in cls_weight]})
         self.compute_metrics = compute_metrics
         self.lazy_host = lazy_host        # host copies of the logits / labels as LazyHostArray instead of a blocking .cpu()
         self.device_metrics = device_metrics    # label ranks by ops.label_rank: nothing of width C is cloned or leaves the device
@@ -409,10 +435,13 @@ class Runner:
       ops.label_rank call, for afft_amd.common.metric_tracking.MeanTopKRecallMeter; the (B, C) logits are neither cloned nor copied
       to the host.  Logits that are not on the GPU take the host path whatever this says.
     cls_weight ({target type: [C] class weights}) / label_smoothing: nn.CrossEntropyLoss's weight= and label_smoothing= for the future
-      and past classification terms (BasicLossAccuracy); the defaults leave the loss and its kernel calls as they were."""
+      and past classification terms (BasicLossAccuracy); the defaults leave the loss and its kernel calls as they were.
+    focal_gamma / logit_adjust ({target type: [C] adjustment}): the focal exponent and the logit adjustment of the same terms; the
+      adjustment enters the loss only -- the returned logits, the metrics and evaluation see raw logits.  Defaults: as they were."""
 
     def __init__(self, model, device, loss_wts, compute_metrics: bool = True, async_metrics=None, device_metrics=None,
-                 cls_weight: Optional[Dict[str, torch.Tensor]] = None, label_smoothing: float = 0.0):
+                 cls_weight: Optional[Dict[str, torch.Tensor]] = None, label_smoothing: float = 0.0,
+                 focal_gamma: float = 0.0, logit_adjust: Optional[Dict[str, torch.Tensor]] = None):
         import os
         if async_metrics is None:
             async_metrics = False if os.environ.get("AFFT_RUNNER_SYNC", "0") == "1" else "lazy"
@@ -423,7 +452,8 @@ class Runner:
         self.device = device
         self.device_metrics = bool(device_metrics)
         self.loss_acc_fn = BasicLossAccuracy(compute_metrics, lazy_host=bool(async_metrics), device_metrics=self.device_metrics,
-                                             cls_weight=cls_weight, label_smoothing=label_smoothing)
+                                             cls_weight=cls_weight, label_smoothing=label_smoothing, focal_gamma=focal_gamma,
+                                             logit_adjust=logit_adjust)
         self.loss_wts = loss_wts
         self.async_metrics = async_metrics
 

@@ -122,6 +122,144 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
   }
 }
 
+// The row's maximum WITH its index: ties go to the lower index, whatever the order of the combine (lane tree, then the four waves front
+// to back), so the class that focal_terms treats as the arg-max is a function of the row alone.
+__device__ __forceinline__ void block_argmax(float& m, int& idx, float* shv, int* shi) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float om = __shfl_xor(m, o, 64);
+    const int oi = __shfl_xor(idx, o, 64);
+    if (om > m || (om == m && oi < idx)) { m = om; idx = oi; }
+  }
+  __syncthreads();
+  if (lane == 0) { shv[wave] = m; shi[wave] = idx; }
+  __syncthreads();
+  m = shv[0]; idx = shi[0];
+  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {
+    const float om = shv[w];
+    const int oi = shi[w];
+    if (om > m || (om == m && oi < idx)) { m = om; idx = oi; }
+  }
+}
+
+// One class of a focal row (include/afft_hip.h): p, q = 1 - p, f = q^gamma l, g = q^gamma + gamma p q^(gamma - 1) l, with l = lse - z.
+// r = sum over the classes other than the arg-max of exp(z - m), inv = 1 / (1 + r), l1p = log1p(r).  The arg-max is the one class
+// whose 1 - p cancels: its q and l come from r; every other class has p <= 1/2.
+__device__ __forceinline__ void focal_terms(float z, bool is_max, float m, float r, float inv, float l1p, float gamma,
+                                            float& p, float& q, float& f, float& g) {
+  // q^gamma: the arg-max's q may be tiny (its relative accuracy is what a dominant row's loss has), so it takes powf -- once per row;
+  // elsewhere q lies in [1/2, 1], |log2 q| <= 1, and exp2(gamma log2 q) on the hardware's log2 / exp2 is good to ~gamma ulp
+  float l, qg;
+  if (is_max) {
+    p = inv; q = r * inv; l = l1p;
+    qg = gamma == 0.f ? 1.f : powf(q, gamma);
+  } else {
+    p = expf(z - m) * inv; q = 1.f - p; l = (m - z) + l1p;
+    qg = gamma == 0.f ? 1.f : __builtin_amdgcn_exp2f(gamma * __builtin_amdgcn_logf(q));
+  }
+  f = qg * l;
+  g = qg + (q > 0.f ? gamma * p * qg * (l / q) : 0.f);
+}
+
+// Focal / logit-adjusted cross-entropy: z = x + adjust, row_loss = sum_c a_c q_c^gamma l_c, dlogits[j] = p_j G - a_j g_j with
+// G = sum_c a_c g_c (a_c: ce_coef, as in softmax_ce_kernel<true>).  Passes over the row: arg-max; r and A; the loss and G; the gradient.
+// A hard label without smoothing has ONE non-zero a_c: its loss and G are one term, the third pass is skipped and the gradient pass
+// takes no power.  The arg-max's own gradient element is p (G - a g) - q a g: no 1 - p there either.
+__global__ __launch_bounds__(256) void softmax_ce_focal_kernel(const float* __restrict__ logits, int64_t ldl, int C,
+                                                               const int64_t* __restrict__ labels,
+                                                               const float* __restrict__ soft, int64_t lds,
+                                                               const uint8_t* __restrict__ keep, float gscale,
+                                                               const float* __restrict__ row_g,
+                                                               void* __restrict__ dlogits,
+                                                               int64_t ldd, int d_dtype, float* __restrict__ row_loss,
+                                                               int period, int64_t lgs, int64_t dgs,
+                                                               const float* __restrict__ weight, float smoothing,
+                                                               const float* __restrict__ adjust, float gamma) {
+  __shared__ float sh[4];
+  __shared__ int shi[4];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const int clip = row / period, frame = row - clip * period;
+  const float* x = logits + (int64_t)clip * lgs + (int64_t)frame * ldl;
+  const int64_t drow = (int64_t)clip * dgs + (int64_t)frame * ldd;
+  bool kept = true;
+  int64_t lab = -1;
+  if (labels) { lab = labels[row]; kept = lab != -1; }
+  const bool bad = labels && (lab >= C || lab < -1);      // as in softmax_ce_kernel: nothing is read at `lab`, the row comes out NaN
+  if (keep) kept = kept && keep[row] != 0;
+  if (!kept) {  // uniform per block
+    if (dlogits) for (int c = tid; c < ldd; c += 256) st_any(dlogits, drow + c, d_dtype, 0.f);
+    if (row_loss && tid == 0) row_loss[row] = 0.f;
+    return;
+  }
+  float m = -INFINITY;
+  int am = 0x7fffffff;
+  for (int c = tid; c < C; c += 256) {
+    const float z = x[c] + (adjust ? adjust[c] : 0.f);
+    if (z > m) { m = z; am = c; }
+  }
+  block_argmax(m, am, sh, shi);
+  const float* t = soft ? soft + (int64_t)row * lds : nullptr;
+  const float unif = smoothing / (float)C, sharp = 1.f - smoothing;
+  const float own = t || bad ? 0.f : sharp * (weight ? weight[lab] : 1.f);
+  const bool single = !t && unif == 0.f;      // a hard label, no smoothing: a_c = own [c == lab]
+  float r = 0.f, asum = 0.f;
+  for (int c = tid; c < C; c += 256) {
+    const float z = x[c] + (adjust ? adjust[c] : 0.f);
+    r += c == am ? 0.f : expf(z - m);
+    if (!single) asum += ce_coef(weight, t, c, lab, unif, sharp, own);
+  }
+  r = block_reduce(r, sh, false);
+  asum = single ? own : block_reduce(asum, sh, false);
+  const float inv = 1.0f / (1.0f + r), l1p = log1pf(r);
+  // loss; G in two parts: the arg-max's own term a g (g_max) and the sum of the others (g_rest)
+  float loss = 0.f, g_rest = 0.f, g_max = 0.f, g_lab = 0.f;
+  if (single) {
+    const float z = bad ? 0.f : x[lab] + (adjust ? adjust[lab] : 0.f);
+    float p, q, f, g;
+    focal_terms(z, lab == am, m, r, inv, l1p, gamma, p, q, f, g);
+    loss = own * f;
+    g_lab = own * g;
+    if (lab == am) g_max = g_lab; else g_rest = g_lab;
+  } else {
+    for (int c = tid; c < C; c += 256) {
+      const float z = x[c] + (adjust ? adjust[c] : 0.f);
+      const float a = ce_coef(weight, t, c, lab, unif, sharp, own);
+      float p, q, f, g;
+      focal_terms(z, c == am, m, r, inv, l1p, gamma, p, q, f, g);
+      loss += a * f;
+      if (c == am) g_max = a * g; else g_rest += a * g;
+    }
+    if (row_loss) loss = block_reduce(loss, sh, false);
+    if (dlogits) {
+      g_rest = block_reduce(g_rest, sh, false);
+      g_max = block_reduce(g_max, sh, false);      // one non-zero term: exact
+    }
+  }
+  if (tid == 0 && row_loss) row_loss[row] = bad ? NAN : loss;
+  if (dlogits) {
+    const float gsum = g_rest + g_max;
+    if (row_g) gscale *= row_g[row];
+    for (int c = tid; c < ldd; c += 256) {
+      float d = 0.f;
+      if (c < C) {
+        const float z = x[c] + (adjust ? adjust[c] : 0.f);
+        if (c == am) {
+          d = inv * g_rest - r * inv * g_max;
+        } else if (single) {
+          d = expf(z - m) * inv * gsum - (c == lab ? g_lab : 0.f);
+        } else {
+          float p, q, f, g;
+          focal_terms(z, false, m, r, inv, l1p, gamma, p, q, f, g);
+          d = p * gsum - ce_coef(weight, t, c, lab, unif, sharp, own) * g;
+        }
+        d = bad ? NAN : gscale * d;
+      }
+      st_any(dlogits, drow + c, d_dtype, d);
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void mse_kernel(const float* __restrict__ a, int64_t lda, const float* __restrict__ b,
                                                   int64_t ldb, int rows, int d, float gscale,
                                                   const float* __restrict__ g_dev, float lscale,
@@ -321,6 +459,53 @@ extern "C" int afft_softmax_ce_frames_w(const float* logits, int64_t clip_stride
   if (clips == 0) return 0;
   hipLaunchKernelGGL(softmax_ce_kernel<true>, dim3(clips * frames), dim3(256), 0, stream, logits, ldl, C, labels, soft, lds, keep,
                      gscale, row_g, dlogits, ldd, d_dtype, row_loss, frames, clip_stride, d_clip_stride, weight, smoothing);
+  AFFT_LAUNCH_CHECK();
+  return 0;
+}
+
+// Focal exponent and logit adjustment.  gamma == 0 with a null adjust IS the weighted loss: the sibling's call, the sibling's bits.
+extern "C" int afft_softmax_ce_focal(const float* logits, int64_t ldl, int32_t rows, int32_t C, const int64_t* labels,
+                                     const float* soft, int64_t lds, const uint8_t* keep, float gscale, const float* row_g,
+                                     float* loss_sum, void* dlogits, int64_t ldd, int32_t d_dtype, float* row_loss,
+                                     const float* weight, float smoothing, const float* adjust, float gamma, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  AFFT_CHECK(gamma >= 0.f && gamma < INFINITY, "softmax_ce_focal: gamma must be finite and >= 0 (got %g)", (double)gamma);
+  if (!adjust && gamma == 0.f)
+    return afft_softmax_ce_w(logits, ldl, rows, C, labels, soft, lds, keep, gscale, row_g, loss_sum, dlogits, ldd, d_dtype, row_loss,
+                             weight, smoothing, stream_);
+  AFFT_CHECK(smoothing >= 0.f && smoothing <= 1.f, "softmax_ce_focal: smoothing must lie in [0, 1] (got %g)", (double)smoothing);
+  AFFT_CHECK(logits, "softmax_ce_focal: null logits");
+  AFFT_CHECK((labels != nullptr) != (soft != nullptr), "softmax_ce_focal: give exactly one of labels / soft targets");
+  AFFT_CHECK(C > 0 && ldl >= C && (!dlogits || ldd >= C), "softmax_ce_focal: bad sizes");
+  AFFT_CHECK(!loss_sum || row_loss, "softmax_ce_focal: loss_sum is the ordered sum of row_loss: give row_loss as well");
+  if (rows == 0) return 0;
+  hipLaunchKernelGGL(softmax_ce_focal_kernel, dim3(rows), dim3(256), 0, stream, logits, ldl, C, labels, soft, lds, keep,
+                     gscale, row_g, dlogits, ldd, d_dtype, row_loss, rows, (int64_t)0, (int64_t)0, weight, smoothing, adjust, gamma);
+  AFFT_LAUNCH_CHECK();
+  if (loss_sum) {
+    hipLaunchKernelGGL(ordered_sum_kernel, dim3(1), dim3(256), 0, stream, row_loss, (int64_t)rows, 1.0f, loss_sum, 1);
+    AFFT_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+extern "C" int afft_softmax_ce_frames_focal(const float* logits, int64_t clip_stride, int64_t ldl, int32_t clips, int32_t frames, int32_t C,
+                                            const int64_t* labels, const float* soft, int64_t lds, const uint8_t* keep, float gscale,
+                                            const float* row_g, void* dlogits, int64_t d_clip_stride, int64_t ldd, int32_t d_dtype,
+                                            float* row_loss, const float* weight, float smoothing, const float* adjust, float gamma,
+                                            void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  AFFT_CHECK(gamma >= 0.f && gamma < INFINITY, "softmax_ce_frames_focal: gamma must be finite and >= 0 (got %g)", (double)gamma);
+  if (!adjust && gamma == 0.f)
+    return afft_softmax_ce_frames_w(logits, clip_stride, ldl, clips, frames, C, labels, soft, lds, keep, gscale, row_g, dlogits,
+                                    d_clip_stride, ldd, d_dtype, row_loss, weight, smoothing, stream_);
+  AFFT_CHECK(smoothing >= 0.f && smoothing <= 1.f, "softmax_ce_frames_focal: smoothing must lie in [0, 1] (got %g)", (double)smoothing);
+  AFFT_CHECK(logits, "softmax_ce_frames_focal: null logits");
+  AFFT_CHECK((labels != nullptr) != (soft != nullptr), "softmax_ce_frames_focal: give exactly one of labels / soft targets");
+  AFFT_CHECK(C > 0 && ldl >= C && (!dlogits || ldd >= C) && frames > 0, "softmax_ce_frames_focal: bad sizes");
+  if (clips == 0) return 0;
+  hipLaunchKernelGGL(softmax_ce_focal_kernel, dim3(clips * frames), dim3(256), 0, stream, logits, ldl, C, labels, soft, lds, keep,
+                     gscale, row_g, dlogits, ldd, d_dtype, row_loss, frames, clip_stride, d_clip_stride, weight, smoothing, adjust, gamma);
   AFFT_LAUNCH_CHECK();
   return 0;
 }

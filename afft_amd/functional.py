@@ -1920,39 +1920,40 @@ class SoftmaxCE(torch.autograd.Function):
     logits: [rows, C], or a (clips, frames, C) view with contiguous classes (a half of the merged classifier output): walked in
     place.  landing = (GradLanding, half) makes backward write the gradient straight into the record's buffer.
     weight (fp32 [C] on the logits' device) / smoothing: nn.CrossEntropyLoss's weight= and label_smoothing= (ops.softmax_ce_w);
-    with neither, the calls are ops.softmax_ce / ops.softmax_ce_frames, exactly as without the two arguments."""
+    with neither, the calls are ops.softmax_ce / ops.softmax_ce_frames, exactly as without the two arguments.
+    adjust (fp32 [C] on the logits' device) / gamma: logit adjustment and focal exponent (ops.softmax_ce_focal); they come as a pair
+    behind weight and smoothing, and with adjust None and gamma 0 the calls are those of the seven-argument form."""
 
     @staticmethod
     def forward(ctx, logits, labels, soft, keep, *rest):
-        assert len(rest) <= 3
-        landing, weight, smoothing = (rest + (None, None, 0.0)[len(rest):])
+        assert len(rest) <= 3 or len(rest) == 5
+        landing, weight, smoothing, adjust, gamma = (rest + (None, None, 0.0, None, 0.0)[len(rest):])
         ctx.landing, ctx.nargs = landing, 4 + len(rest)
-        plain = weight is None and smoothing == 0
-        ctx.opts = None if plain else dict(weight=weight, smoothing=smoothing)
+        # the narrowest wrapper that serves the options: "" (plain), "_w", "_focal" -- the defaults make the calls made without them
+        if adjust is not None or gamma != 0:
+            ctx.kind, ctx.opts = "_focal", dict(weight=weight, smoothing=smoothing, adjust=adjust, gamma=gamma)
+        elif weight is not None or smoothing != 0:
+            ctx.kind, ctx.opts = "_w", dict(weight=weight, smoothing=smoothing)
+        else:
+            ctx.kind, ctx.opts = "", {}
         if logits.dim() == 3:
             clips, frames, C = logits.shape
             assert logits.stride(2) == 1
             row_loss = torch.empty(clips * frames, dtype=torch.float32, device=logits.device)
-            if plain:
-                ops.softmax_ce_frames(logits, C, labels=labels, soft=soft, keep=keep, row_loss=row_loss)
-            else:
-                ops.softmax_ce_frames_w(logits, C, labels=labels, soft=soft, keep=keep, row_loss=row_loss, **ctx.opts)
+            getattr(ops, "softmax_ce_frames" + ctx.kind)(logits, C, labels=labels, soft=soft, keep=keep, row_loss=row_loss, **ctx.opts)
             ctx.save_for_backward(logits, labels, soft, keep)
             return row_loss
         rows, C = logits.shape
         row_loss = torch.empty(rows, dtype=torch.float32, device=logits.device)
         lg = logits if logits.stride(1) == 1 else logits.contiguous()
-        if plain:
-            ops.softmax_ce(lg, C, labels=labels, soft=soft, keep=keep, row_loss=row_loss)
-        else:
-            ops.softmax_ce_w(lg, C, labels=labels, soft=soft, keep=keep, row_loss=row_loss, **ctx.opts)
+        getattr(ops, "softmax_ce" + ctx.kind)(lg, C, labels=labels, soft=soft, keep=keep, row_loss=row_loss, **ctx.opts)
         ctx.save_for_backward(lg, labels, soft, keep)
         return row_loss
 
     @staticmethod
     def backward(ctx, g_rows):
         lg, labels, soft, keep = ctx.saved_tensors
-        none = (None,) * (ctx.nargs - 1)      # one slot per argument of apply: five at the old call sites, seven with weight / smoothing
+        none = (None,) * (ctx.nargs - 1)      # one slot per argument of apply: five at the old call sites, seven with weight / smoothing, nine with adjust / gamma
         if lg.dim() == 3:
             C = lg.shape[2]
             d = None
@@ -1961,18 +1962,13 @@ class SoftmaxCE(torch.autograd.Function):
                 assert d is None or d.shape == lg.shape
             if d is None:
                 d = torch.empty(lg.shape, dtype=torch.float32, device=lg.device)
-            if ctx.opts is None:
-                ops.softmax_ce_frames(lg, C, labels=labels, soft=soft, keep=keep, dlogits3=d, row_g=g_rows.contiguous())
-            else:
-                ops.softmax_ce_frames_w(lg, C, labels=labels, soft=soft, keep=keep, dlogits3=d, row_g=g_rows.contiguous(), **ctx.opts)
+            getattr(ops, "softmax_ce_frames" + ctx.kind)(lg, C, labels=labels, soft=soft, keep=keep, dlogits3=d, row_g=g_rows.contiguous(),
+                                                         **ctx.opts)
             flush_ready()
             return (d,) + none
         rows, C = lg.shape
         d = torch.empty(rows, C, dtype=torch.float32, device=lg.device)
-        if ctx.opts is None:
-            ops.softmax_ce(lg, C, labels=labels, soft=soft, keep=keep, dlogits=d, row_g=g_rows.contiguous())
-        else:
-            ops.softmax_ce_w(lg, C, labels=labels, soft=soft, keep=keep, dlogits=d, row_g=g_rows.contiguous(), **ctx.opts)
+        getattr(ops, "softmax_ce" + ctx.kind)(lg, C, labels=labels, soft=soft, keep=keep, dlogits=d, row_g=g_rows.contiguous(), **ctx.opts)
         flush_ready()
         return (d,) + none
 

@@ -3,6 +3,7 @@ streams only; every computation below runs in the hand-written HIP kernels of li
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -631,6 +632,71 @@ def softmax_ce_frames_w(logits3: Tensor, C_: int, *, labels: Optional[Tensor] = 
                                              dlogits3.stride(1) if dlogits3 is not None else 0,
                                              _dt(dlogits3) if dlogits3 is not None else 0, _p(row_loss), _p(weight), float(smoothing),
                                              _stream()), "softmax_ce_frames_w")
+
+
+def _ce_focal(adjust: Optional[Tensor], gamma: float, C_: int, logits: Tensor):
+    """the checks softmax_ce_focal / softmax_ce_frames_focal add to the _w wrappers' (the library refuses the same gamma)"""
+    gamma = float(gamma)
+    if not (gamma >= 0.0 and math.isfinite(gamma)):
+        raise ValueError(f"afft_amd: the focal exponent gamma must be finite and >= 0, got {gamma}")
+    if adjust is not None:
+        if adjust.dtype != torch.float32 or not adjust.is_contiguous() or adjust.dim() != 1 or adjust.numel() != C_:
+            raise ValueError(f"afft_amd: the logit adjustment must be a contiguous fp32 vector of {C_} entries, got {adjust.dtype} "
+                             f"{tuple(adjust.shape)} {adjust.stride()}")
+        if adjust.device != logits.device:
+            raise ValueError(f"afft_amd: the logit adjustment lives on {adjust.device}, the logits on {logits.device}")
+    return gamma
+
+
+def softmax_ce_focal(logits: Tensor, C_: int, *, labels: Optional[Tensor] = None, soft: Optional[Tensor] = None,
+                     keep: Optional[Tensor] = None, gscale: float = 1.0, row_g: Optional[Tensor] = None,
+                     loss_sum: Optional[Tensor] = None, dlogits: Optional[Tensor] = None, row_loss: Optional[Tensor] = None,
+                     weight: Optional[Tensor] = None, smoothing: float = 0.0, adjust: Optional[Tensor] = None, gamma: float = 0.0):
+    """softmax_ce_w with a focusing exponent gamma >= 0 (focal loss) and a logit adjustment (fp32 [C] on the logits' device, None = 0,
+    added to the logits inside the loss only): afft_softmax_ce_focal, the formulas are in include/afft_hip.h.  gamma 0 and adjust None
+    run softmax_ce_w's kernel."""
+    rows = logits.shape[0]
+    assert logits.dtype == torch.float32
+    if labels is not None:
+        assert labels.dtype == torch.int64 and labels.numel() == rows and labels.is_contiguous()
+    if soft is not None:
+        assert soft.dtype == torch.float32 and soft.shape[0] == rows
+    if keep is not None:
+        assert keep.dtype == torch.uint8 and keep.numel() == rows
+    _ce_weight(weight, C_, logits)
+    gamma = _ce_focal(adjust, gamma, C_, logits)
+    L.check(L.lib().afft_softmax_ce_focal(_p(logits), _rowmajor(logits, "logits"), rows, C_, _p(labels), _p(soft),
+                                          _rowmajor(soft, "soft") if soft is not None else 0, _p(keep), gscale,
+                                          _p(row_g), _p(loss_sum), _p(dlogits),
+                                          _rowmajor(dlogits, "dlogits") if dlogits is not None else 0,
+                                          _dt(dlogits) if dlogits is not None else 0, _p(row_loss), _p(weight), float(smoothing),
+                                          _p(adjust), gamma, _stream()), "softmax_ce_focal")
+
+
+def softmax_ce_frames_focal(logits3: Tensor, C_: int, *, labels: Optional[Tensor] = None, soft: Optional[Tensor] = None,
+                            keep: Optional[Tensor] = None, row_g: Optional[Tensor] = None, dlogits3: Optional[Tensor] = None,
+                            row_loss: Optional[Tensor] = None, weight: Optional[Tensor] = None, smoothing: float = 0.0,
+                            adjust: Optional[Tensor] = None, gamma: float = 0.0):
+    """softmax_ce_frames_w with a focusing exponent and a logit adjustment (afft_softmax_ce_frames_focal), as softmax_ce_focal"""
+    clips, frames = logits3.shape[0], logits3.shape[1]
+    assert logits3.dtype == torch.float32 and logits3.dim() == 3 and logits3.stride(2) == 1
+    rows = clips * frames
+    if labels is not None:
+        assert labels.dtype == torch.int64 and labels.numel() == rows and labels.is_contiguous()
+    if soft is not None:
+        assert soft.dtype == torch.float32 and soft.shape[0] == rows
+    if keep is not None:
+        assert keep.dtype == torch.uint8 and keep.numel() == rows
+    if dlogits3 is not None:
+        assert dlogits3.dim() == 3 and dlogits3.shape[:2] == logits3.shape[:2] and dlogits3.stride(2) == 1
+    _ce_weight(weight, C_, logits3)
+    gamma = _ce_focal(adjust, gamma, C_, logits3)
+    L.check(L.lib().afft_softmax_ce_frames_focal(_p(logits3), logits3.stride(0), logits3.stride(1), clips, frames, C_, _p(labels),
+                                                 _p(soft), _rowmajor(soft, "soft") if soft is not None else 0, _p(keep), 1.0, _p(row_g),
+                                                 _p(dlogits3), dlogits3.stride(0) if dlogits3 is not None else 0,
+                                                 dlogits3.stride(1) if dlogits3 is not None else 0,
+                                                 _dt(dlogits3) if dlogits3 is not None else 0, _p(row_loss), _p(weight), float(smoothing),
+                                                 _p(adjust), gamma, _stream()), "softmax_ce_frames_focal")
 
 
 def loss_reduce(vals, weights, means: Optional[Tensor], total: Tensor):

@@ -753,9 +753,11 @@ class Trainer(_FusedEpilogue):
     def __init__(self, model, loss_wts: Dict[str, float], lr=1e-3, momentum=0.9, weight_decay=1e-6,
                  comm_dtype: str = "fp32", bucket_elems: int = 32 * 1024 * 1024, group=None,
                  overlap_optimizer: bool = True, force_comm: bool = False, grad_clip: Optional[float] = None,
-                 comm_algo: str = "allreduce", cls_weight: Optional[Dict[str, Tensor]] = None, label_smoothing: float = 0.0):
-        """cls_weight / label_smoothing: class weights per target type and label smoothing of the classification terms, as
-        common.runner.Runner takes them; the defaults leave the loss as it was."""
+                 comm_algo: str = "allreduce", cls_weight: Optional[Dict[str, Tensor]] = None, label_smoothing: float = 0.0,
+                 focal_gamma: float = 0.0, logit_adjust: Optional[Dict[str, Tensor]] = None):
+        """cls_weight / label_smoothing / focal_gamma / logit_adjust: class weights per target type, label smoothing, the focal exponent
+        and the logit adjustment per target type of the classification terms, as common.runner.Runner takes them; the defaults leave
+        the loss as it was."""
         from .common.runner import BasicLossAccuracy, Runner
         self.model = model
         self.flat = FlatParams(model, sharded_layout=(comm_algo == "sharded"))
@@ -770,7 +772,8 @@ class Trainer(_FusedEpilogue):
             model.register_state_dict_pre_hook(lambda *a, **k: self.reducer.assert_masters_fresh("state_dict()"))
         if self.reducer.world > 1:
             self.sync_parameters(group)
-        self.loss_fn = BasicLossAccuracy(compute_metrics=False, cls_weight=cls_weight, label_smoothing=label_smoothing)
+        self.loss_fn = BasicLossAccuracy(compute_metrics=False, cls_weight=cls_weight, label_smoothing=label_smoothing,
+                                         focal_gamma=focal_gamma, logit_adjust=logit_adjust)
         self._reduce = Runner._reduce_loss
         self.loss_wts = loss_wts
         self.grad_clip = grad_clip     # opt.grad_clip of the reference's config; needs the whole gradient first

@@ -453,6 +453,33 @@ int afft_softmax_ce_frames_w(const float* logits, int64_t clip_stride, int64_t l
                              const int64_t* labels, const float* soft, int64_t lds, const uint8_t* keep, float gscale, const float* row_g,
                              void* dlogits, int64_t d_clip_stride, int64_t ldd, int32_t d_dtype, float* row_loss,
                              const float* weight, float smoothing, void* stream);
+/* Both with a focusing exponent (focal loss, Lin et al. 2017) and a logit adjustment (Menon et al. 2021; tau = 1: "balanced softmax").
+ * adjust: fp32 [C], contiguous, NULL = 0, finite entries (a non-finite one yields NaN or inf by plain arithmetic, nothing else); it
+ * enters the loss only.  gamma >= 0 and finite (anything else, NaN included, is a host error before any launch).  With x a row of logits,
+ *   z_c = x_c + adjust_c,  lse = logsumexp(z),  p = softmax(z),  l_c = lse - z_c (>= 0),  q_c = 1 - p_c,
+ * the coefficients a_c of afft_softmax_ce_w (hard label, soft target, weight, smoothing) and A = sum_c a_c,
+ *   row_loss   = sum_c a_c q_c^gamma l_c
+ *   g_c        = q_c^gamma + gamma p_c q_c^(gamma - 1) l_c      (0 when q_c = 0 and gamma > 0: the limit, as l_c ~ q_c;  1 when gamma = 0)
+ *   G          = sum_c a_c g_c
+ *   dlogits[j] = gscale * row_g * (p_j G - a_j g_j)              (the gradient with respect to x is the one with respect to z)
+ * gamma = 0 and adjust = 0 give afft_softmax_ce_w's lse A - sum_c a_c x_c and p_j A - a_j; a hard label y with smoothing 0 gives
+ * -w_y (1 - p_y)^gamma log p_y; soft (MixUp) targets and smoothing are the same sum.
+ * Cancellation: 1 - p_c cancels for one class of a row, its arg-max (the FIRST index that attains the maximum of z, found together with
+ * the maximum in a fixed order).  With m = max z and r = sum_{c != argmax} exp(z_c - m) that class takes q = r / (1 + r) and
+ * l = log1p(r), and lse = m + log1p(r); every other class has p_c <= 1/2 and takes q_c = 1 - p_c.  gamma p q^(gamma - 1) l is evaluated
+ * as gamma p q^gamma (l / q), 0 when q = 0, and the arg-max's own gradient element as p (G - a g) - q a g.
+ * Ignored rows (label -1, keep == 0) and rows whose A is 0 give exactly 0; a label outside [-1, C) gives a NaN row and reads nothing out
+ * of bounds, weight and adjust included; columns C..ldd-1 of the gradient are zeroed.  Row addressing, keep, gscale, row_g, row_loss,
+ * loss_sum and d_dtype are the siblings'.  Fixed-order block reductions, no atomics: same inputs, same bits.
+ * gamma == 0 with adjust == NULL calls the _w entry point and returns its bits (the plain kernel's when weight is NULL and smoothing 0). */
+int afft_softmax_ce_focal(const float* logits, int64_t ldl, int32_t rows, int32_t C, const int64_t* labels,
+                          const float* soft, int64_t lds, const uint8_t* keep, float gscale, const float* row_g,
+                          float* loss_sum, void* dlogits, int64_t ldd, int32_t d_dtype, float* row_loss,
+                          const float* weight, float smoothing, const float* adjust, float gamma, void* stream);
+int afft_softmax_ce_frames_focal(const float* logits, int64_t clip_stride, int64_t ldl, int32_t clips, int32_t frames, int32_t C,
+                                 const int64_t* labels, const float* soft, int64_t lds, const uint8_t* keep, float gscale,
+                                 const float* row_g, void* dlogits, int64_t d_clip_stride, int64_t ldd, int32_t d_dtype, float* row_loss,
+                                 const float* weight, float smoothing, const float* adjust, float gamma, void* stream);
 /* Runner._reduce_loss (common/runner.py:198-213) in one launch: term i = n[i] fp32 per-row losses at x[i] (HOST arrays of nterms <= 8
  * device pointers / counts / weights); means[i] = mean(x[i]) (may be NULL), total[0] = sum_i w[i] * means[i], in a fixed order (bit-stable).
  * afft_loss_reduce_bwd: g[i][0 .. n[i]) = g_total[0] * w[i] / n[i] (g_total NULL = 1; g[i] NULL skips a term): the upstream
