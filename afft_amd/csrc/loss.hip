@@ -385,39 +385,64 @@ extern "C" int afft_loss_reduce_bwd_ok(float* const* g, const int64_t* n, const 
   return 0;
 }
 
+// One cross-entropy call, whichever of the six entry points below it came through: they only fill this in, in the order of the
+// frames form's arguments.  The row form is period = rows with clip strides 0; an entry without an option passes its neutral value.
+struct CeCall {
+  const float* logits; int64_t lgs, ldl;      // clip stride, frame (row) stride
+  int32_t rows, period, C;                    // rows = clips * frames, period = frames
+  const int64_t* labels; const float* soft; int64_t lds; const uint8_t* keep; float gscale; const float* row_g;
+  void* dlogits; int64_t dgs, ldd; int32_t d_dtype; float* row_loss;
+  const float* weight; float smoothing; const float* adjust; float gamma;
+  float* loss_sum;                            // row form only: the ordered sum of row_loss
+  bool frames;                                // the caller's form: it names the entry in the messages, and wants period > 0
+  void* stream;
+};
+
+static int ce_launch(const CeCall& c) {
+  hipStream_t stream = (hipStream_t)c.stream;
+  static const char* const names[2][3] = {{"softmax_ce", "softmax_ce_w", "softmax_ce_focal"},
+                                          {"softmax_ce_frames", "softmax_ce_frames_w", "softmax_ce_frames_focal"}};
+  AFFT_CHECK(c.gamma >= 0.f && c.gamma < INFINITY, "%s: gamma must be finite and >= 0 (got %g)", names[c.frames][2], (double)c.gamma);
+  // The kernel is the narrowest one that serves the options, and so are its bits: 2 = softmax_ce_focal_kernel (an adjustment or a
+  // focal exponent), 1 = softmax_ce_kernel<true> (class weights or smoothing), 0 = softmax_ce_kernel<false>.  The messages carry the
+  // name of the entry point of that kernel, whichever entry the call came through.
+  const int kern = c.adjust || c.gamma != 0.f ? 2 : c.weight || c.smoothing != 0.f ? 1 : 0;
+  const char* name = names[c.frames][kern];
+  AFFT_CHECK(c.smoothing >= 0.f && c.smoothing <= 1.f, "%s: smoothing must lie in [0, 1] (got %g)", name, (double)c.smoothing);
+  AFFT_CHECK(c.logits, "%s: null logits", name);
+  AFFT_CHECK((c.labels != nullptr) != (c.soft != nullptr), "%s: give exactly one of labels / soft targets", name);
+  AFFT_CHECK(c.C > 0 && c.ldl >= c.C && (!c.dlogits || c.ldd >= c.C) && (!c.frames || c.period > 0), "%s: bad sizes", name);
+  AFFT_CHECK(!c.loss_sum || c.row_loss, "%s: loss_sum is the ordered sum of row_loss: give row_loss as well", name);
+  if (c.rows == 0) return 0;
+  auto launch = [&](auto kernel, auto... options) {
+    hipLaunchKernelGGL(kernel, dim3(c.rows), dim3(256), 0, stream, c.logits, c.ldl, c.C, c.labels, c.soft, c.lds, c.keep, c.gscale,
+                       c.row_g, c.dlogits, c.ldd, c.d_dtype, c.row_loss, c.period, c.lgs, c.dgs, options...);
+  };
+  if (kern == 0) launch(softmax_ce_kernel<false>, (const float*)nullptr, 0.f);
+  else if (kern == 1) launch(softmax_ce_kernel<true>, c.weight, c.smoothing);
+  else launch(softmax_ce_focal_kernel, c.weight, c.smoothing, c.adjust, c.gamma);
+  AFFT_LAUNCH_CHECK();
+  if (c.loss_sum) {
+    hipLaunchKernelGGL(ordered_sum_kernel, dim3(1), dim3(256), 0, stream, c.row_loss, (int64_t)c.rows, 1.0f, c.loss_sum, 1);
+    AFFT_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
 extern "C" int afft_softmax_ce(const float* logits, int64_t ldl, int32_t rows, int32_t C, const int64_t* labels,
                                const float* soft, int64_t lds, const uint8_t* keep, float gscale, const float* row_g,
                                float* loss_sum, void* dlogits, int64_t ldd, int32_t d_dtype, float* row_loss,
                                void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  AFFT_CHECK(logits, "softmax_ce: null logits");
-  AFFT_CHECK((labels != nullptr) != (soft != nullptr), "softmax_ce: give exactly one of labels / soft targets");
-  AFFT_CHECK(C > 0 && ldl >= C && (!dlogits || ldd >= C), "softmax_ce: bad sizes");
-  AFFT_CHECK(!loss_sum || row_loss, "softmax_ce: loss_sum is the ordered sum of row_loss: give row_loss as well");
-  if (rows == 0) return 0;
-  hipLaunchKernelGGL(softmax_ce_kernel<false>, dim3(rows), dim3(256), 0, stream, logits, ldl, C, labels, soft, lds, keep,
-                     gscale, row_g, dlogits, ldd, d_dtype, row_loss, rows, (int64_t)0, (int64_t)0, (const float*)nullptr, 0.f);
-  AFFT_LAUNCH_CHECK();
-  if (loss_sum) {
-    hipLaunchKernelGGL(ordered_sum_kernel, dim3(1), dim3(256), 0, stream, row_loss, (int64_t)rows, 1.0f, loss_sum, 1);
-    AFFT_LAUNCH_CHECK();
-  }
-  return 0;
+  return afft_softmax_ce_focal(logits, ldl, rows, C, labels, soft, lds, keep, gscale, row_g, loss_sum, dlogits, ldd, d_dtype, row_loss,
+                               nullptr, 0.f, nullptr, 0.f, stream_);
 }
 
 extern "C" int afft_softmax_ce_frames(const float* logits, int64_t clip_stride, int64_t ldl, int32_t clips, int32_t frames, int32_t C,
                                       const int64_t* labels, const float* soft, int64_t lds, const uint8_t* keep, float gscale,
                                       const float* row_g, void* dlogits, int64_t d_clip_stride, int64_t ldd, int32_t d_dtype,
                                       float* row_loss, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  AFFT_CHECK(logits, "softmax_ce_frames: null logits");
-  AFFT_CHECK((labels != nullptr) != (soft != nullptr), "softmax_ce_frames: give exactly one of labels / soft targets");
-  AFFT_CHECK(C > 0 && ldl >= C && (!dlogits || ldd >= C) && frames > 0, "softmax_ce_frames: bad sizes");
-  if (clips == 0) return 0;
-  hipLaunchKernelGGL(softmax_ce_kernel<false>, dim3(clips * frames), dim3(256), 0, stream, logits, ldl, C, labels, soft, lds, keep,
-                     gscale, row_g, dlogits, ldd, d_dtype, row_loss, frames, clip_stride, d_clip_stride, (const float*)nullptr, 0.f);
-  AFFT_LAUNCH_CHECK();
-  return 0;
+  return afft_softmax_ce_frames_focal(logits, clip_stride, ldl, clips, frames, C, labels, soft, lds, keep, gscale, row_g, dlogits,
+                                      d_clip_stride, ldd, d_dtype, row_loss, nullptr, 0.f, nullptr, 0.f, stream_);
 }
 
 // Class weights and label smoothing.  A null weight with smoothing == 0 IS the plain loss: the sibling's launch, the sibling's bits.
@@ -425,68 +450,25 @@ extern "C" int afft_softmax_ce_w(const float* logits, int64_t ldl, int32_t rows,
                                  const float* soft, int64_t lds, const uint8_t* keep, float gscale, const float* row_g,
                                  float* loss_sum, void* dlogits, int64_t ldd, int32_t d_dtype, float* row_loss,
                                  const float* weight, float smoothing, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  AFFT_CHECK(smoothing >= 0.f && smoothing <= 1.f, "softmax_ce_w: smoothing must lie in [0, 1] (got %g)", (double)smoothing);
-  if (!weight && smoothing == 0.f)
-    return afft_softmax_ce(logits, ldl, rows, C, labels, soft, lds, keep, gscale, row_g, loss_sum, dlogits, ldd, d_dtype, row_loss, stream_);
-  AFFT_CHECK(logits, "softmax_ce_w: null logits");
-  AFFT_CHECK((labels != nullptr) != (soft != nullptr), "softmax_ce_w: give exactly one of labels / soft targets");
-  AFFT_CHECK(C > 0 && ldl >= C && (!dlogits || ldd >= C), "softmax_ce_w: bad sizes");
-  AFFT_CHECK(!loss_sum || row_loss, "softmax_ce_w: loss_sum is the ordered sum of row_loss: give row_loss as well");
-  if (rows == 0) return 0;
-  hipLaunchKernelGGL(softmax_ce_kernel<true>, dim3(rows), dim3(256), 0, stream, logits, ldl, C, labels, soft, lds, keep,
-                     gscale, row_g, dlogits, ldd, d_dtype, row_loss, rows, (int64_t)0, (int64_t)0, weight, smoothing);
-  AFFT_LAUNCH_CHECK();
-  if (loss_sum) {
-    hipLaunchKernelGGL(ordered_sum_kernel, dim3(1), dim3(256), 0, stream, row_loss, (int64_t)rows, 1.0f, loss_sum, 1);
-    AFFT_LAUNCH_CHECK();
-  }
-  return 0;
+  return afft_softmax_ce_focal(logits, ldl, rows, C, labels, soft, lds, keep, gscale, row_g, loss_sum, dlogits, ldd, d_dtype, row_loss,
+                               weight, smoothing, nullptr, 0.f, stream_);
 }
 
 extern "C" int afft_softmax_ce_frames_w(const float* logits, int64_t clip_stride, int64_t ldl, int32_t clips, int32_t frames, int32_t C,
                                         const int64_t* labels, const float* soft, int64_t lds, const uint8_t* keep, float gscale,
                                         const float* row_g, void* dlogits, int64_t d_clip_stride, int64_t ldd, int32_t d_dtype,
                                         float* row_loss, const float* weight, float smoothing, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  AFFT_CHECK(smoothing >= 0.f && smoothing <= 1.f, "softmax_ce_frames_w: smoothing must lie in [0, 1] (got %g)", (double)smoothing);
-  if (!weight && smoothing == 0.f)
-    return afft_softmax_ce_frames(logits, clip_stride, ldl, clips, frames, C, labels, soft, lds, keep, gscale, row_g, dlogits,
-                                  d_clip_stride, ldd, d_dtype, row_loss, stream_);
-  AFFT_CHECK(logits, "softmax_ce_frames_w: null logits");
-  AFFT_CHECK((labels != nullptr) != (soft != nullptr), "softmax_ce_frames_w: give exactly one of labels / soft targets");
-  AFFT_CHECK(C > 0 && ldl >= C && (!dlogits || ldd >= C) && frames > 0, "softmax_ce_frames_w: bad sizes");
-  if (clips == 0) return 0;
-  hipLaunchKernelGGL(softmax_ce_kernel<true>, dim3(clips * frames), dim3(256), 0, stream, logits, ldl, C, labels, soft, lds, keep,
-                     gscale, row_g, dlogits, ldd, d_dtype, row_loss, frames, clip_stride, d_clip_stride, weight, smoothing);
-  AFFT_LAUNCH_CHECK();
-  return 0;
+  return afft_softmax_ce_frames_focal(logits, clip_stride, ldl, clips, frames, C, labels, soft, lds, keep, gscale, row_g, dlogits,
+                                      d_clip_stride, ldd, d_dtype, row_loss, weight, smoothing, nullptr, 0.f, stream_);
 }
 
-// Focal exponent and logit adjustment.  gamma == 0 with a null adjust IS the weighted loss: the sibling's call, the sibling's bits.
+// Focal exponent and logit adjustment.  gamma == 0 with a null adjust IS the weighted loss: the sibling's launch, the sibling's bits.
 extern "C" int afft_softmax_ce_focal(const float* logits, int64_t ldl, int32_t rows, int32_t C, const int64_t* labels,
                                      const float* soft, int64_t lds, const uint8_t* keep, float gscale, const float* row_g,
                                      float* loss_sum, void* dlogits, int64_t ldd, int32_t d_dtype, float* row_loss,
                                      const float* weight, float smoothing, const float* adjust, float gamma, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  AFFT_CHECK(gamma >= 0.f && gamma < INFINITY, "softmax_ce_focal: gamma must be finite and >= 0 (got %g)", (double)gamma);
-  if (!adjust && gamma == 0.f)
-    return afft_softmax_ce_w(logits, ldl, rows, C, labels, soft, lds, keep, gscale, row_g, loss_sum, dlogits, ldd, d_dtype, row_loss,
-                             weight, smoothing, stream_);
-  AFFT_CHECK(smoothing >= 0.f && smoothing <= 1.f, "softmax_ce_focal: smoothing must lie in [0, 1] (got %g)", (double)smoothing);
-  AFFT_CHECK(logits, "softmax_ce_focal: null logits");
-  AFFT_CHECK((labels != nullptr) != (soft != nullptr), "softmax_ce_focal: give exactly one of labels / soft targets");
-  AFFT_CHECK(C > 0 && ldl >= C && (!dlogits || ldd >= C), "softmax_ce_focal: bad sizes");
-  AFFT_CHECK(!loss_sum || row_loss, "softmax_ce_focal: loss_sum is the ordered sum of row_loss: give row_loss as well");
-  if (rows == 0) return 0;
-  hipLaunchKernelGGL(softmax_ce_focal_kernel, dim3(rows), dim3(256), 0, stream, logits, ldl, C, labels, soft, lds, keep,
-                     gscale, row_g, dlogits, ldd, d_dtype, row_loss, rows, (int64_t)0, (int64_t)0, weight, smoothing, adjust, gamma);
-  AFFT_LAUNCH_CHECK();
-  if (loss_sum) {
-    hipLaunchKernelGGL(ordered_sum_kernel, dim3(1), dim3(256), 0, stream, row_loss, (int64_t)rows, 1.0f, loss_sum, 1);
-    AFFT_LAUNCH_CHECK();
-  }
-  return 0;
+  return ce_launch({logits, 0, ldl, rows, rows, C, labels, soft, lds, keep, gscale, row_g, dlogits, 0, ldd, d_dtype, row_loss,
+                    weight, smoothing, adjust, gamma, loss_sum, false, stream_});
 }
 
 extern "C" int afft_softmax_ce_frames_focal(const float* logits, int64_t clip_stride, int64_t ldl, int32_t clips, int32_t frames, int32_t C,
@@ -494,20 +476,8 @@ extern "C" int afft_softmax_ce_frames_focal(const float* logits, int64_t clip_st
                                             const float* row_g, void* dlogits, int64_t d_clip_stride, int64_t ldd, int32_t d_dtype,
                                             float* row_loss, const float* weight, float smoothing, const float* adjust, float gamma,
                                             void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  AFFT_CHECK(gamma >= 0.f && gamma < INFINITY, "softmax_ce_frames_focal: gamma must be finite and >= 0 (got %g)", (double)gamma);
-  if (!adjust && gamma == 0.f)
-    return afft_softmax_ce_frames_w(logits, clip_stride, ldl, clips, frames, C, labels, soft, lds, keep, gscale, row_g, dlogits,
-                                    d_clip_stride, ldd, d_dtype, row_loss, weight, smoothing, stream_);
-  AFFT_CHECK(smoothing >= 0.f && smoothing <= 1.f, "softmax_ce_frames_focal: smoothing must lie in [0, 1] (got %g)", (double)smoothing);
-  AFFT_CHECK(logits, "softmax_ce_frames_focal: null logits");
-  AFFT_CHECK((labels != nullptr) != (soft != nullptr), "softmax_ce_frames_focal: give exactly one of labels / soft targets");
-  AFFT_CHECK(C > 0 && ldl >= C && (!dlogits || ldd >= C) && frames > 0, "softmax_ce_frames_focal: bad sizes");
-  if (clips == 0) return 0;
-  hipLaunchKernelGGL(softmax_ce_focal_kernel, dim3(clips * frames), dim3(256), 0, stream, logits, ldl, C, labels, soft, lds, keep,
-                     gscale, row_g, dlogits, ldd, d_dtype, row_loss, frames, clip_stride, d_clip_stride, weight, smoothing, adjust, gamma);
-  AFFT_LAUNCH_CHECK();
-  return 0;
+  return ce_launch({logits, clip_stride, ldl, clips * frames, frames, C, labels, soft, lds, keep, gscale, row_g, dlogits, d_clip_stride,
+                    ldd, d_dtype, row_loss, weight, smoothing, adjust, gamma, nullptr, true, stream_});
 }
 
 extern "C" int afft_mse_frames_bwd(const float* a, int64_t a_clip_stride, int32_t a_off, int32_t a_len, const float* b,

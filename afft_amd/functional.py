@@ -1937,38 +1937,36 @@ class SoftmaxCE(torch.autograd.Function):
         else:
             ctx.kind, ctx.opts = "", {}
         if logits.dim() == 3:
-            clips, frames, C = logits.shape
             assert logits.stride(2) == 1
-            row_loss = torch.empty(clips * frames, dtype=torch.float32, device=logits.device)
-            getattr(ops, "softmax_ce_frames" + ctx.kind)(logits, C, labels=labels, soft=soft, keep=keep, row_loss=row_loss, **ctx.opts)
-            ctx.save_for_backward(logits, labels, soft, keep)
-            return row_loss
-        rows, C = logits.shape
-        row_loss = torch.empty(rows, dtype=torch.float32, device=logits.device)
-        lg = logits if logits.stride(1) == 1 else logits.contiguous()
-        getattr(ops, "softmax_ce" + ctx.kind)(lg, C, labels=labels, soft=soft, keep=keep, row_loss=row_loss, **ctx.opts)
+            lg = logits
+        else:
+            lg = logits if logits.stride(1) == 1 else logits.contiguous()
+        row_loss = torch.empty(lg.shape[:-1].numel(), dtype=torch.float32, device=lg.device)
+        SoftmaxCE._wrapper(ctx, lg)[0](lg, lg.shape[-1], labels=labels, soft=soft, keep=keep, row_loss=row_loss, **ctx.opts)
         ctx.save_for_backward(lg, labels, soft, keep)
         return row_loss
+
+    @staticmethod
+    def _wrapper(ctx, lg):
+        """the wrapper of afft_amd.ops for these logits and options, looked up when it is called, and the name of its gradient keyword"""
+        if lg.dim() == 3:
+            return getattr(ops, "softmax_ce_frames" + ctx.kind), "dlogits3"
+        assert lg.dim() == 2
+        return getattr(ops, "softmax_ce" + ctx.kind), "dlogits"
 
     @staticmethod
     def backward(ctx, g_rows):
         lg, labels, soft, keep = ctx.saved_tensors
         none = (None,) * (ctx.nargs - 1)      # one slot per argument of apply: five at the old call sites, seven with weight / smoothing, nine with adjust / gamma
-        if lg.dim() == 3:
-            C = lg.shape[2]
-            d = None
-            if ctx.landing is not None and ctx.landing[0].shape[2] == C:
-                d = ctx.landing[0].half(ctx.landing[1], lg.device)
-                assert d is None or d.shape == lg.shape
-            if d is None:
-                d = torch.empty(lg.shape, dtype=torch.float32, device=lg.device)
-            getattr(ops, "softmax_ce_frames" + ctx.kind)(lg, C, labels=labels, soft=soft, keep=keep, dlogits3=d, row_g=g_rows.contiguous(),
-                                                         **ctx.opts)
-            flush_ready()
-            return (d,) + none
-        rows, C = lg.shape
-        d = torch.empty(rows, C, dtype=torch.float32, device=lg.device)
-        getattr(ops, "softmax_ce" + ctx.kind)(lg, C, labels=labels, soft=soft, keep=keep, dlogits=d, row_g=g_rows.contiguous(), **ctx.opts)
+        C = lg.shape[-1]
+        d = None
+        if lg.dim() == 3 and ctx.landing is not None and ctx.landing[0].shape[2] == C:
+            d = ctx.landing[0].half(ctx.landing[1], lg.device)
+            assert d is None or d.shape == lg.shape
+        if d is None:
+            d = torch.empty(lg.shape, dtype=torch.float32, device=lg.device)
+        fn, grad = SoftmaxCE._wrapper(ctx, lg)
+        fn(lg, C, labels=labels, soft=soft, keep=keep, row_g=g_rows.contiguous(), **{grad: d}, **ctx.opts)
         flush_ready()
         return (d,) + none
 

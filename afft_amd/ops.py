@@ -534,49 +534,6 @@ def attention_step_bwd(dout: Tensor, q: Tensor, k_cache: Tensor, v_cache: Tensor
                                             gk_cache.stride(0), _stream()), "attention_step_bwd")
 
 
-def softmax_ce(logits: Tensor, C_: int, *, labels: Optional[Tensor] = None, soft: Optional[Tensor] = None,
-               keep: Optional[Tensor] = None, gscale: float = 1.0, row_g: Optional[Tensor] = None,
-               loss_sum: Optional[Tensor] = None, dlogits: Optional[Tensor] = None,
-               row_loss: Optional[Tensor] = None):
-    """logits fp32 [rows, >=C] view. labels int64 [rows] (-1 ignored) or soft fp32 [rows, C]; keep uint8 [rows]."""
-    rows = logits.shape[0]
-    assert logits.dtype == torch.float32
-    if labels is not None:
-        assert labels.dtype == torch.int64 and labels.numel() == rows and labels.is_contiguous()
-    if soft is not None:
-        assert soft.dtype == torch.float32 and soft.shape[0] == rows
-    if keep is not None:
-        assert keep.dtype == torch.uint8 and keep.numel() == rows
-    L.check(L.lib().afft_softmax_ce(_p(logits), _rowmajor(logits, "logits"), rows, C_, _p(labels), _p(soft),
-                                    _rowmajor(soft, "soft") if soft is not None else 0, _p(keep), gscale,
-                                    _p(row_g), _p(loss_sum), _p(dlogits),
-                                    _rowmajor(dlogits, "dlogits") if dlogits is not None else 0,
-                                    _dt(dlogits) if dlogits is not None else 0, _p(row_loss), _stream()), "softmax_ce")
-
-
-def softmax_ce_frames(logits3: Tensor, C_: int, *, labels: Optional[Tensor] = None, soft: Optional[Tensor] = None,
-                      keep: Optional[Tensor] = None, row_g: Optional[Tensor] = None, dlogits3: Optional[Tensor] = None,
-                      row_loss: Optional[Tensor] = None):
-    """softmax_ce on a (clips, frames, >= C) VIEW (e.g. x[:, :n] of a wider tensor): no flattening copy; dlogits3 is a view of the
-    same kind (its own strides).  Row r of labels / soft / keep / row_g / row_loss = frame r % frames of clip r // frames."""
-    clips, frames = logits3.shape[0], logits3.shape[1]
-    assert logits3.dtype == torch.float32 and logits3.dim() == 3 and logits3.stride(2) == 1
-    rows = clips * frames
-    if labels is not None:
-        assert labels.dtype == torch.int64 and labels.numel() == rows and labels.is_contiguous()
-    if soft is not None:
-        assert soft.dtype == torch.float32 and soft.shape[0] == rows
-    if keep is not None:
-        assert keep.dtype == torch.uint8 and keep.numel() == rows
-    if dlogits3 is not None:
-        assert dlogits3.dim() == 3 and dlogits3.shape[:2] == logits3.shape[:2] and dlogits3.stride(2) == 1
-    L.check(L.lib().afft_softmax_ce_frames(_p(logits3), logits3.stride(0), logits3.stride(1), clips, frames, C_, _p(labels), _p(soft),
-                                           _rowmajor(soft, "soft") if soft is not None else 0, _p(keep), 1.0, _p(row_g),
-                                           _p(dlogits3), dlogits3.stride(0) if dlogits3 is not None else 0,
-                                           dlogits3.stride(1) if dlogits3 is not None else 0,
-                                           _dt(dlogits3) if dlogits3 is not None else 0, _p(row_loss), _stream()), "softmax_ce_frames")
-
-
 def _ce_weight(weight: Optional[Tensor], C_: int, logits: Tensor):
     """the checks softmax_ce_w / softmax_ce_frames_w add to their siblings' (the library itself refuses a smoothing outside [0, 1])"""
     if weight is not None:
@@ -585,53 +542,6 @@ def _ce_weight(weight: Optional[Tensor], C_: int, logits: Tensor):
                              f"{tuple(weight.shape)} {weight.stride()}")
         if weight.device != logits.device:
             raise ValueError(f"afft_amd: class weights live on {weight.device}, the logits on {logits.device}")
-
-
-def softmax_ce_w(logits: Tensor, C_: int, *, labels: Optional[Tensor] = None, soft: Optional[Tensor] = None,
-                 keep: Optional[Tensor] = None, gscale: float = 1.0, row_g: Optional[Tensor] = None,
-                 loss_sum: Optional[Tensor] = None, dlogits: Optional[Tensor] = None, row_loss: Optional[Tensor] = None,
-                 weight: Optional[Tensor] = None, smoothing: float = 0.0):
-    """softmax_ce with class weights (fp32 [C] on the logits' device, None = ones) and label smoothing in [0, 1]
-    (afft_softmax_ce_w: the formulas are in include/afft_hip.h).  weight None and smoothing 0 run softmax_ce's kernel."""
-    rows = logits.shape[0]
-    assert logits.dtype == torch.float32
-    if labels is not None:
-        assert labels.dtype == torch.int64 and labels.numel() == rows and labels.is_contiguous()
-    if soft is not None:
-        assert soft.dtype == torch.float32 and soft.shape[0] == rows
-    if keep is not None:
-        assert keep.dtype == torch.uint8 and keep.numel() == rows
-    _ce_weight(weight, C_, logits)
-    L.check(L.lib().afft_softmax_ce_w(_p(logits), _rowmajor(logits, "logits"), rows, C_, _p(labels), _p(soft),
-                                      _rowmajor(soft, "soft") if soft is not None else 0, _p(keep), gscale,
-                                      _p(row_g), _p(loss_sum), _p(dlogits),
-                                      _rowmajor(dlogits, "dlogits") if dlogits is not None else 0,
-                                      _dt(dlogits) if dlogits is not None else 0, _p(row_loss), _p(weight), float(smoothing),
-                                      _stream()), "softmax_ce_w")
-
-
-def softmax_ce_frames_w(logits3: Tensor, C_: int, *, labels: Optional[Tensor] = None, soft: Optional[Tensor] = None,
-                        keep: Optional[Tensor] = None, row_g: Optional[Tensor] = None, dlogits3: Optional[Tensor] = None,
-                        row_loss: Optional[Tensor] = None, weight: Optional[Tensor] = None, smoothing: float = 0.0):
-    """softmax_ce_frames with class weights and label smoothing (afft_softmax_ce_frames_w), as softmax_ce_w"""
-    clips, frames = logits3.shape[0], logits3.shape[1]
-    assert logits3.dtype == torch.float32 and logits3.dim() == 3 and logits3.stride(2) == 1
-    rows = clips * frames
-    if labels is not None:
-        assert labels.dtype == torch.int64 and labels.numel() == rows and labels.is_contiguous()
-    if soft is not None:
-        assert soft.dtype == torch.float32 and soft.shape[0] == rows
-    if keep is not None:
-        assert keep.dtype == torch.uint8 and keep.numel() == rows
-    if dlogits3 is not None:
-        assert dlogits3.dim() == 3 and dlogits3.shape[:2] == logits3.shape[:2] and dlogits3.stride(2) == 1
-    _ce_weight(weight, C_, logits3)
-    L.check(L.lib().afft_softmax_ce_frames_w(_p(logits3), logits3.stride(0), logits3.stride(1), clips, frames, C_, _p(labels), _p(soft),
-                                             _rowmajor(soft, "soft") if soft is not None else 0, _p(keep), 1.0, _p(row_g),
-                                             _p(dlogits3), dlogits3.stride(0) if dlogits3 is not None else 0,
-                                             dlogits3.stride(1) if dlogits3 is not None else 0,
-                                             _dt(dlogits3) if dlogits3 is not None else 0, _p(row_loss), _p(weight), float(smoothing),
-                                             _stream()), "softmax_ce_frames_w")
 
 
 def _ce_focal(adjust: Optional[Tensor], gamma: float, C_: int, logits: Tensor):
@@ -648,6 +558,82 @@ def _ce_focal(adjust: Optional[Tensor], gamma: float, C_: int, logits: Tensor):
     return gamma
 
 
+def _softmax_ce(name: str, logits: Tensor, C_: int, labels, soft, keep, gscale, row_g, loss_sum, dlogits, row_loss,
+                weight=None, smoothing=0.0, adjust=None, gamma=0.0):
+    """the body of the six wrappers below: the checks of `name`, then the C symbol afft_<name>.  A "frames" name takes logits and
+    dlogits as (clips, frames, >= C) views; a name ending in _w adds weight and smoothing, one ending in _focal adjust and gamma as
+    well (the other names neither check nor pass them)."""
+    frames, focal = "frames" in name, name.endswith("_focal")
+    if frames:
+        clips, per_clip = logits.shape[0], logits.shape[1]
+        assert logits.dtype == torch.float32 and logits.dim() == 3 and logits.stride(2) == 1
+        rows = clips * per_clip
+    else:
+        rows = logits.shape[0]
+        assert logits.dtype == torch.float32
+    if labels is not None:
+        assert labels.dtype == torch.int64 and labels.numel() == rows and labels.is_contiguous()
+    if soft is not None:
+        assert soft.dtype == torch.float32 and soft.shape[0] == rows
+    if keep is not None:
+        assert keep.dtype == torch.uint8 and keep.numel() == rows
+    if frames and dlogits is not None:
+        assert dlogits.dim() == 3 and dlogits.shape[:2] == logits.shape[:2] and dlogits.stride(2) == 1
+    if focal or name.endswith("_w"):
+        _ce_weight(weight, C_, logits)
+    if focal:
+        gamma = _ce_focal(adjust, gamma, C_, logits)
+    fn = getattr(L.lib(), "afft_" + name)
+    # the arguments in the order of include/afft_hip.h: the two forms differ in how they size the problem and stride the gradient
+    if frames:
+        args = [_p(logits), logits.stride(0), logits.stride(1), clips, per_clip, C_]
+    else:
+        args = [_p(logits), _rowmajor(logits, "logits"), rows, C_]
+    args += [_p(labels), _p(soft), _rowmajor(soft, "soft") if soft is not None else 0, _p(keep), gscale, _p(row_g)]
+    if frames:
+        args += [_p(dlogits), dlogits.stride(0) if dlogits is not None else 0, dlogits.stride(1) if dlogits is not None else 0]
+    else:
+        args += [_p(loss_sum), _p(dlogits), _rowmajor(dlogits, "dlogits") if dlogits is not None else 0]
+    args += [_dt(dlogits) if dlogits is not None else 0, _p(row_loss)]
+    if focal or name.endswith("_w"):
+        args += [_p(weight), float(smoothing)]
+    if focal:
+        args += [_p(adjust), gamma]
+    L.check(fn(*args, _stream()), name)
+
+
+def softmax_ce(logits: Tensor, C_: int, *, labels: Optional[Tensor] = None, soft: Optional[Tensor] = None,
+               keep: Optional[Tensor] = None, gscale: float = 1.0, row_g: Optional[Tensor] = None,
+               loss_sum: Optional[Tensor] = None, dlogits: Optional[Tensor] = None,
+               row_loss: Optional[Tensor] = None):
+    """logits fp32 [rows, >=C] view. labels int64 [rows] (-1 ignored) or soft fp32 [rows, C]; keep uint8 [rows]."""
+    _softmax_ce("softmax_ce", logits, C_, labels, soft, keep, gscale, row_g, loss_sum, dlogits, row_loss)
+
+
+def softmax_ce_frames(logits3: Tensor, C_: int, *, labels: Optional[Tensor] = None, soft: Optional[Tensor] = None,
+                      keep: Optional[Tensor] = None, row_g: Optional[Tensor] = None, dlogits3: Optional[Tensor] = None,
+                      row_loss: Optional[Tensor] = None):
+    """softmax_ce on a (clips, frames, >= C) VIEW (e.g. x[:, :n] of a wider tensor): no flattening copy; dlogits3 is a view of the
+    same kind (its own strides).  Row r of labels / soft / keep / row_g / row_loss = frame r % frames of clip r // frames."""
+    _softmax_ce("softmax_ce_frames", logits3, C_, labels, soft, keep, 1.0, row_g, None, dlogits3, row_loss)
+
+
+def softmax_ce_w(logits: Tensor, C_: int, *, labels: Optional[Tensor] = None, soft: Optional[Tensor] = None,
+                 keep: Optional[Tensor] = None, gscale: float = 1.0, row_g: Optional[Tensor] = None,
+                 loss_sum: Optional[Tensor] = None, dlogits: Optional[Tensor] = None, row_loss: Optional[Tensor] = None,
+                 weight: Optional[Tensor] = None, smoothing: float = 0.0):
+    """softmax_ce with class weights (fp32 [C] on the logits' device, None = ones) and label smoothing in [0, 1]
+    (afft_softmax_ce_w: the formulas are in include/afft_hip.h).  weight None and smoothing 0 run softmax_ce's kernel."""
+    _softmax_ce("softmax_ce_w", logits, C_, labels, soft, keep, gscale, row_g, loss_sum, dlogits, row_loss, weight, smoothing)
+
+
+def softmax_ce_frames_w(logits3: Tensor, C_: int, *, labels: Optional[Tensor] = None, soft: Optional[Tensor] = None,
+                        keep: Optional[Tensor] = None, row_g: Optional[Tensor] = None, dlogits3: Optional[Tensor] = None,
+                        row_loss: Optional[Tensor] = None, weight: Optional[Tensor] = None, smoothing: float = 0.0):
+    """softmax_ce_frames with class weights and label smoothing (afft_softmax_ce_frames_w), as softmax_ce_w"""
+    _softmax_ce("softmax_ce_frames_w", logits3, C_, labels, soft, keep, 1.0, row_g, None, dlogits3, row_loss, weight, smoothing)
+
+
 def softmax_ce_focal(logits: Tensor, C_: int, *, labels: Optional[Tensor] = None, soft: Optional[Tensor] = None,
                      keep: Optional[Tensor] = None, gscale: float = 1.0, row_g: Optional[Tensor] = None,
                      loss_sum: Optional[Tensor] = None, dlogits: Optional[Tensor] = None, row_loss: Optional[Tensor] = None,
@@ -655,22 +641,8 @@ def softmax_ce_focal(logits: Tensor, C_: int, *, labels: Optional[Tensor] = None
     """softmax_ce_w with a focusing exponent gamma >= 0 (focal loss) and a logit adjustment (fp32 [C] on the logits' device, None = 0,
     added to the logits inside the loss only): afft_softmax_ce_focal, the formulas are in include/afft_hip.h.  gamma 0 and adjust None
     run softmax_ce_w's kernel."""
-    rows = logits.shape[0]
-    assert logits.dtype == torch.float32
-    if labels is not None:
-        assert labels.dtype == torch.int64 and labels.numel() == rows and labels.is_contiguous()
-    if soft is not None:
-        assert soft.dtype == torch.float32 and soft.shape[0] == rows
-    if keep is not None:
-        assert keep.dtype == torch.uint8 and keep.numel() == rows
-    _ce_weight(weight, C_, logits)
-    gamma = _ce_focal(adjust, gamma, C_, logits)
-    L.check(L.lib().afft_softmax_ce_focal(_p(logits), _rowmajor(logits, "logits"), rows, C_, _p(labels), _p(soft),
-                                          _rowmajor(soft, "soft") if soft is not None else 0, _p(keep), gscale,
-                                          _p(row_g), _p(loss_sum), _p(dlogits),
-                                          _rowmajor(dlogits, "dlogits") if dlogits is not None else 0,
-                                          _dt(dlogits) if dlogits is not None else 0, _p(row_loss), _p(weight), float(smoothing),
-                                          _p(adjust), gamma, _stream()), "softmax_ce_focal")
+    _softmax_ce("softmax_ce_focal", logits, C_, labels, soft, keep, gscale, row_g, loss_sum, dlogits, row_loss, weight, smoothing,
+                adjust, gamma)
 
 
 def softmax_ce_frames_focal(logits3: Tensor, C_: int, *, labels: Optional[Tensor] = None, soft: Optional[Tensor] = None,
@@ -678,25 +650,8 @@ def softmax_ce_frames_focal(logits3: Tensor, C_: int, *, labels: Optional[Tensor
                             row_loss: Optional[Tensor] = None, weight: Optional[Tensor] = None, smoothing: float = 0.0,
                             adjust: Optional[Tensor] = None, gamma: float = 0.0):
     """softmax_ce_frames_w with a focusing exponent and a logit adjustment (afft_softmax_ce_frames_focal), as softmax_ce_focal"""
-    clips, frames = logits3.shape[0], logits3.shape[1]
-    assert logits3.dtype == torch.float32 and logits3.dim() == 3 and logits3.stride(2) == 1
-    rows = clips * frames
-    if labels is not None:
-        assert labels.dtype == torch.int64 and labels.numel() == rows and labels.is_contiguous()
-    if soft is not None:
-        assert soft.dtype == torch.float32 and soft.shape[0] == rows
-    if keep is not None:
-        assert keep.dtype == torch.uint8 and keep.numel() == rows
-    if dlogits3 is not None:
-        assert dlogits3.dim() == 3 and dlogits3.shape[:2] == logits3.shape[:2] and dlogits3.stride(2) == 1
-    _ce_weight(weight, C_, logits3)
-    gamma = _ce_focal(adjust, gamma, C_, logits3)
-    L.check(L.lib().afft_softmax_ce_frames_focal(_p(logits3), logits3.stride(0), logits3.stride(1), clips, frames, C_, _p(labels),
-                                                 _p(soft), _rowmajor(soft, "soft") if soft is not None else 0, _p(keep), 1.0, _p(row_g),
-                                                 _p(dlogits3), dlogits3.stride(0) if dlogits3 is not None else 0,
-                                                 dlogits3.stride(1) if dlogits3 is not None else 0,
-                                                 _dt(dlogits3) if dlogits3 is not None else 0, _p(row_loss), _p(weight), float(smoothing),
-                                                 _p(adjust), gamma, _stream()), "softmax_ce_frames_focal")
+    _softmax_ce("softmax_ce_frames_focal", logits3, C_, labels, soft, keep, 1.0, row_g, None, dlogits3, row_loss, weight, smoothing,
+                adjust, gamma)
 
 
 def loss_reduce(vals, weights, means: Optional[Tensor], total: Tensor):

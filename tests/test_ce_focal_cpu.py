@@ -12,6 +12,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(__file__))
+import ce_cases  # noqa: E402
 import ce_double  # noqa: E402
 import focal_double  # noqa: E402
 
@@ -191,55 +192,9 @@ def test_logit_adjustment():
 
 
 # ----------------------------------------------------------------------------- the calls into afft_amd.ops
-class Recorder:
-    """stands in for the focal wrappers of afft_amd.ops: notes every call and computes by the float64 double; the four older wrappers
-    only note their calls (their results are not looked at here)"""
-
-    def __init__(self):
-        self.calls = []
-
-    def _run(self, x2, C_, kw, d2):
-        got = focal_double.focal(x2[:, :C_], labels=kw.get("labels"), soft=kw.get("soft"), keep=kw.get("keep"), weight=kw.get("weight"),
-                                 eps=kw.get("smoothing", 0.0), adjust=kw.get("adjust"), gamma=kw.get("gamma", 0.0),
-                                 gscale=kw.get("gscale", 1.0), row_g=kw.get("row_g"))
-        if kw.get("row_loss") is not None:
-            kw["row_loss"].copy_(got["loss"])
-        if d2 is not None:
-            d2.zero_()
-            d2[:, :C_].copy_(got["grad"])
-
-    def softmax_ce_focal(self, logits, C_, **kw):
-        self.calls.append(("softmax_ce_focal", (logits, C_), kw))
-        with torch.no_grad():
-            self._run(logits, C_, kw, kw.get("dlogits"))
-
-    def softmax_ce_frames_focal(self, logits3, C_, **kw):
-        self.calls.append(("softmax_ce_frames_focal", (logits3, C_), kw))
-        with torch.no_grad():
-            d3 = kw.get("dlogits3")
-            d2 = None if d3 is None else torch.zeros(d3.shape[0] * d3.shape[1], d3.shape[2])
-            self._run(logits3.reshape(-1, logits3.shape[2]), C_, kw, d2)
-            if d3 is not None:
-                d3.copy_(d2.view(d3.shape))
-
-    def other(self, name):
-        def call(logits, C_, **kw):
-            self.calls.append((name, (logits, C_), kw))
-            for k in ("row_loss", "dlogits", "dlogits3"):
-                if kw.get(k) is not None:
-                    kw[k].zero_()
-        return call
-
-
 @pytest.fixture
 def rec(monkeypatch):
-    from afft_amd import ops
-    r = Recorder()
-    for n in ("softmax_ce_focal", "softmax_ce_frames_focal"):
-        monkeypatch.setattr(ops, n, getattr(r, n))
-    for n in ("softmax_ce", "softmax_ce_frames", "softmax_ce_w", "softmax_ce_frames_w"):
-        monkeypatch.setattr(ops, n, r.other(n))
-    return r
+    return ce_cases.Recorder(monkeypatch)
 
 
 @pytest.mark.parametrize("three_d", [False, True])

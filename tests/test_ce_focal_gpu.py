@@ -29,11 +29,10 @@ import torch
 
 sys.path.insert(0, os.path.dirname(__file__))
 import focal_double  # noqa: E402
+from ce_cases import SENT, U, dev, framed, launch, make_inputs, ratios, to_dev, up  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -24
-SENT = 512.0
 CS = [1, 2, 255, 256, 257, 513, 3806]
 ROWS = [1, 5]
 GAMMAS = [0.0, 0.5, 2.0, 5.0]
@@ -52,88 +51,6 @@ MEASURED = {
 C_BAR = {k: 2.0 ** math.ceil(math.log2(v)) for k, v in MEASURED["focal"].items()}
 assert C_BAR == dict(loss_hard=4.0, loss_soft=2.0, grad_hard=2.0, grad_soft=2.0)
 W_BAR = 4.0
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def up(n, m):
-    return (n + m - 1) // m * m
-
-
-def make_inputs(rows, C, kind, wmode, adj, seed):
-    """CPU tensors of one case.  Hard: every fourth row is ignored.  zeros: every third class (and class 0) has weight 0; row 1's label
-    (hard) or whole support (soft) lies in that set, so with smoothing 0 its A is 0."""
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(rows, C, generator=g) * 3.0
-    w = None
-    if wmode == "zeros":
-        w = torch.rand(C, generator=g) * 2.0 + 0.1
-        w[::3] = 0.0
-    b = -8.0 * torch.rand(C, generator=g) if adj else None
-    labels = soft = keep = None
-    if kind == "hard":
-        labels = torch.randint(0, C, (rows,), generator=g)
-        labels[2::4] = -1
-        if rows > 1:
-            labels[1] = 0
-    else:
-        soft = torch.softmax(torch.randn(rows, C, generator=g), 1) * (torch.rand(rows, C, generator=g) < 0.6)
-        soft = soft / soft.sum(1, keepdim=True).clamp(min=1e-3)
-        if rows > 1:
-            soft[1] = 0.0
-            soft[1, 0] = 1.0
-        if kind == "soft_keep":
-            keep = (torch.rand(rows, generator=g) < 0.7).to(torch.uint8)
-            if rows > 1:
-                keep[1] = 1
-    return x, labels, soft, keep, w, b
-
-
-def framed(t, ld, fill=float("nan")):
-    """the CPU matrix t on the device as the first columns of a [rows, ld] buffer (the rest: fill)"""
-    buf = torch.full((t.shape[0], ld), fill, dtype=torch.float32, device=dev())
-    buf[:, :t.shape[1]] = t.to(dev())
-    return buf[:, :t.shape[1]]
-
-
-def to_dev(t):
-    return None if t is None else t.to(dev())
-
-
-def launch(fn, x, C, labels, soft, keep, ld, bf16, gscale, row_g, **opts):
-    """forward (row_loss) and gradient launches of `fn`.  Returns loss [rows], the [rows, ld] gradient block and whether the sentinel
-    rows around it survived."""
-    rows = x.shape[0]
-    xd = framed(x, ld)
-    kw = dict(labels=to_dev(labels), soft=to_dev(soft), keep=to_dev(keep), **opts)
-    rl = torch.full((rows,), SENT, device=dev())
-    fn(xd, C, row_loss=rl, **kw)
-    dbuf = torch.full((rows + 2, ld), SENT, dtype=torch.bfloat16 if bf16 else torch.float32, device=dev())
-    fn(xd, C, dlogits=dbuf[1:rows + 1], gscale=gscale, row_g=to_dev(row_g), **kw)
-    border = bool((dbuf[0] == SENT).all()) and bool((dbuf[-1] == SENT).all())
-    return rl.cpu(), dbuf[1:rows + 1].float().cpu(), border
-
-
-def ratios(loss, dblock, ref, C, bf16):
-    """worst |got - ref| / (u S) of the loss and of the gradient over the rows where S > 0; asserts the exact properties: rows of
-    S == 0 (ignored, or A == 0) are exactly 0, the pad columns are exactly 0, nothing is NaN"""
-    zero = (ref["s_loss"] == 0) | ~ref["kept"]
-    assert bool((loss[zero] == 0).all()) and bool((dblock[zero] == 0).all()), "a row that is ignored or whose A is 0 must be exactly 0"
-    assert bool((dblock[:, C:] == 0).all()), "pad columns"
-    assert bool(torch.isfinite(loss).all()) and bool(torch.isfinite(dblock).all())
-    live = ~zero
-    if not bool(live.any()):
-        return 0.0, 0.0
-    r_loss = float(((loss.double() - ref["loss"]).abs()[live] / (U * ref["s_loss"][live])).max())
-    err = (dblock[:, :C].double() - ref["grad"]).abs()
-    if bf16:
-        err = (err - 2.0 ** -8 * ref["grad"].abs()).clamp(min=0)
-    g_live = ref["s_grad"] > 0
-    assert bool((err[~g_live] == 0).all())
-    r_grad = float((err[g_live] / (U * ref["s_grad"][g_live, None])).max()) if bool(g_live.any()) else 0.0
-    return r_loss, r_grad
 
 
 def grid(C):
@@ -160,7 +77,7 @@ def test_focal_ce_against_float64(C):
     worst = {"focal": {}, "w": {}}
     fails = []
     for c in grid(C):
-        x, labels, soft, keep, w, b = make_inputs(c["rows"], C, c["kind"], c["wmode"], c["adj"], c["seed"])
+        x, labels, soft, keep, w, b = make_inputs(c["rows"], C, c["kind"], c["wmode"], c["seed"], adj=c["adj"])
         ld = up(C, 64) if c["pad"] else C
         gscale, row_g = 0.37, torch.randn(c["rows"], generator=torch.Generator().manual_seed(c["seed"])) + 0.2
         ref = focal_double.focal(x, labels=labels, soft=soft, keep=keep, weight=w, eps=EPS32[c["eps"]], adjust=b, gamma=c["gamma"],
@@ -287,7 +204,7 @@ def test_label_far_below_the_maximum_is_finite(C, gamma):
 def test_out_of_range_labels_poison_their_rows_only(eps):
     from afft_amd import ops
     rows, C = 9, 257
-    x, labels, _, _, w, b = make_inputs(rows, C, "hard", "zeros", True, 77)
+    x, labels, _, _, w, b = make_inputs(rows, C, "hard", "zeros", 77, adj=True)
     bad = labels.clone()
     bad[0], bad[3], bad[5], bad[8] = C, -2, C + 5, 1 << 40
     out = {}
@@ -306,7 +223,7 @@ def test_out_of_range_labels_poison_their_rows_only(eps):
 @pytest.mark.parametrize("rows,C,kind", [(5, 3806, "hard"), (5, 257, "soft_keep"), (5, 513, "soft")])
 def test_two_runs_give_equal_bits(rows, C, kind):
     from afft_amd import ops
-    x, labels, soft, keep, w, b = make_inputs(rows, C, kind, "zeros", True, 5)
+    x, labels, soft, keep, w, b = make_inputs(rows, C, kind, "zeros", 5, adj=True)
     row_g = torch.randn(rows, generator=torch.Generator().manual_seed(6))
     opts = dict(weight=to_dev(w), smoothing=0.1 if kind != "hard" else 0.0, adjust=to_dev(b), gamma=2.0)
     runs = [launch(ops.softmax_ce_focal, x, C, labels, soft, keep, up(C, 64), False, 0.5, row_g, **opts) for _ in range(2)]
@@ -325,7 +242,7 @@ def test_two_runs_give_equal_bits(rows, C, kind):
 def test_argument_errors_raise_and_launch_nothing():
     from afft_amd import ops
     rows, C = 5, 63
-    x, labels, _, _, _, b = make_inputs(rows, C, "hard", "none", True, 3)
+    x, labels, _, _, _, b = make_inputs(rows, C, "hard", "none", 3, adj=True)
     xd, lb, bd = framed(x, C), labels.to(dev()), b.to(dev())
     rl = torch.full((rows,), SENT, device=dev())
     d = torch.full((rows, C), SENT, device=dev())

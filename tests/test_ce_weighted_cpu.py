@@ -12,8 +12,8 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(__file__))
+import ce_cases  # noqa: E402
 import ce_double  # noqa: E402
-import cpu_ops  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "c0_weighted_ce.npz")
@@ -106,54 +106,9 @@ def test_double_matches_the_reference_fixture(golden):
 
 
 # ----------------------------------------------------------------------------- the calls into afft_amd.ops
-class Recorder:
-    """stands in for the four cross-entropy wrappers of afft_amd.ops: notes every call; the plain ones compute by tests/cpu_ops.py,
-    the _w ones by the float64 double"""
-
-    def __init__(self):
-        self.calls = []
-
-    def _w(self, name, x2, C_, kw, d2):
-        got = ce_double.ce(x2[:, :C_], labels=kw.get("labels"), soft=kw.get("soft"), keep=kw.get("keep"), weight=kw.get("weight"),
-                           eps=kw.get("smoothing", 0.0), gscale=kw.get("gscale", 1.0), row_g=kw.get("row_g"))
-        if kw.get("row_loss") is not None:
-            kw["row_loss"].copy_(got["loss"])
-        if kw.get("loss_sum") is not None:
-            kw["loss_sum"] += got["loss"].sum()
-        if d2 is not None:
-            d2.zero_()
-            d2[:, :C_].copy_(got["grad"])
-
-    def softmax_ce(self, logits, C_, **kw):
-        self.calls.append(("softmax_ce", (logits, C_), kw))
-        cpu_ops.softmax_ce(logits, C_, **kw)
-
-    def softmax_ce_frames(self, logits3, C_, **kw):
-        self.calls.append(("softmax_ce_frames", (logits3, C_), kw))
-        cpu_ops.softmax_ce_frames(logits3, C_, **kw)
-
-    def softmax_ce_w(self, logits, C_, **kw):
-        self.calls.append(("softmax_ce_w", (logits, C_), kw))
-        with torch.no_grad():
-            self._w("softmax_ce_w", logits, C_, kw, kw.get("dlogits"))
-
-    def softmax_ce_frames_w(self, logits3, C_, **kw):
-        self.calls.append(("softmax_ce_frames_w", (logits3, C_), kw))
-        with torch.no_grad():
-            d3 = kw.get("dlogits3")
-            d2 = None if d3 is None else torch.zeros(d3.shape[0] * d3.shape[1], d3.shape[2])
-            self._w("softmax_ce_frames_w", logits3.reshape(-1, logits3.shape[2]), C_, kw, d2)
-            if d3 is not None:
-                d3.copy_(d2.view(d3.shape))
-
-
 @pytest.fixture
 def rec(monkeypatch):
-    from afft_amd import ops
-    r = Recorder()
-    for n in ("softmax_ce", "softmax_ce_frames", "softmax_ce_w", "softmax_ce_frames_w"):
-        monkeypatch.setattr(ops, n, getattr(r, n))
-    return r
+    return ce_cases.Recorder(monkeypatch)
 
 
 def _leaf(x, three_d):
