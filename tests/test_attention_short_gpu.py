@@ -1,7 +1,7 @@
 """Every case of tests/attention_cases.py -- every instantiation of the short attention kernels (L <= 128: attention.hip,
 attention_mfma.hip) -- ELEMENTWISE against float64, with every operand in a NaN frame of its own and every result in a sentinel frame.
 
-Reference (reference()): float64 scores, mask, softmax, the dropout mask of the integer replica (kernel_doubles.drop_keep at index
+Reference (attention_double.reference()): float64 scores, mask, softmax, the dropout mask of the integer replica (kernel_doubles.drop_keep at index
 ((seq * H + h) * L + i) * L + j, scaled by 1 / (1 - p)), P'V, and the backward products written out.  Beside every output element it
 forms the magnitude sum S: the same expression with absolute values at every product and sum (for probs, which is all positive, the
 first-order image of the score's magnitude sum A = scale * sum |q| |k| through the softmax: S = p * (1 + A_ij + sum_j p_ij A_ij)).
@@ -27,13 +27,13 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(__file__))
-import kernel_doubles as kd  # noqa: E402
-from attention_cases import BLOCK, CASES, CAUSAL, DIAG, frame_cols  # noqa: E402
+from attention_cases import CASES, frame_cols  # noqa: E402
+from attention_double import (KEY, PAD_ROWS, SENTINEL, dev, flat_framed, flat_untouched, frame_untouched, framed, heads,  # noqa: E402
+                              banned_pairs, keep_scale, reference, rows, worst_ratio)
 from helpers import rel_l2  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-PAD_ROWS, PAD_FLAT, SENTINEL, KEY = 2, 64, 512.0, 0x9E3779B9
 U = {"f32": 2.0 ** -24, "bf16": 2.0 ** -9, "planes": 2.0 ** -21, "hi": 2.0 ** -11}
 
 # worst |got - ref| / (u S) over the table, MI355X: path -> kind -> value
@@ -58,10 +58,6 @@ L2 = {"f32": dict(out=2e-5, probs=2e-5, grads=3e-5), "bf16": dict(out=1e-2, prob
       "split": dict(out=2e-5, probs=2e-5, copy=4e-3, hi=5e-4)}
 
 
-def dev():
-    return torch.device("cuda:0")
-
-
 def rnd(*shape, seed):
     return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
 
@@ -76,90 +72,6 @@ def path_of(c, kind):
     if kind[:2] in ("dq", "dk", "dv"):
         return "sliced_bwd" if "_sliced_" in c.bwd or kind.endswith("/twin") else "mfma_bwd"
     return "mfma_fwd"
-
-
-def framed(R, C_, fill, dtype, pad_cols, planes=1):
-    """[planes] buffers of (R + 2 PAD_ROWS) x (C_ + pad_cols) filled with `fill`; the [R, C_] view of plane 0; elements between planes"""
-    buf = torch.full((planes, R + 2 * PAD_ROWS, C_ + pad_cols), fill, dtype=dtype, device=dev())
-    return buf, buf[0, PAD_ROWS:PAD_ROWS + R, :C_], (R + 2 * PAD_ROWS) * (C_ + pad_cols)
-
-
-def frame_untouched(buf, R, C_):
-    b = buf.float().cpu()
-    edge = torch.cat([b[:, :PAD_ROWS].flatten(), b[:, PAD_ROWS + R:].flatten(), b[:, PAD_ROWS:PAD_ROWS + R, C_:].flatten()])
-    return bool((edge == SENTINEL).all())
-
-
-def flat_framed(n, fill=SENTINEL):
-    buf = torch.full((n + 2 * PAD_FLAT,), fill, device=dev())
-    return buf, buf[PAD_FLAT:PAD_FLAT + n]
-
-
-def flat_untouched(buf):
-    b = buf.cpu()
-    return bool((b[:PAD_FLAT] == SENTINEL).all()) and bool((b[-PAD_FLAT:] == SENTINEL).all())
-
-
-def banned_pairs(L, mask, period):
-    """bool [L, L]: (query i, key j) pairs the mask removes.  Block-causal with period 1 IS no mask and with period L IS the causal mask:
-    those two are written that way, not through the modulo rule"""
-    i, j = np.arange(L)[:, None], np.arange(L)[None, :]
-    if mask == DIAG:
-        return i == j
-    if mask == CAUSAL or (mask == BLOCK and period == L):
-        return j > i
-    if mask == BLOCK and period > 1:
-        return (j % period) > (i % period)
-    return np.zeros((L, L), dtype=bool)
-
-
-def keep_scale(nseq, H, L, p, key):
-    """float64 [nseq, H, L, L]: 0 or 1 / (1 - p) by the replica mask (p as the C float the kernels get)"""
-    if p <= 0:
-        return np.ones((nseq, H, L, L)), None
-    idx = np.arange(nseq * H * L * L, dtype=np.uint64).reshape(nseq, H, L, L)      # ((seq * H + h) * L + i) * L + j
-    keep = kd.drop_keep(key, idx, p)
-    return np.where(keep, 1.0 / (1.0 - float(np.float32(p))), 0.0), keep
-
-
-def reference(q, k, v, do, scale, banned, ks):
-    """float64 [nseq, H, L, hd] operands -> {kind: (value, magnitude sum S)}"""
-    T = lambda x: np.swapaxes(x, -1, -2)      # noqa: E731
-    aq, ak, av, ado = np.abs(q), np.abs(k), np.abs(v), np.abs(do)
-    s = np.where(banned, -np.inf, scale * (q @ T(k)))
-    A = scale * (aq @ T(ak))
-    e = np.exp(s - s.max(-1, keepdims=True))
-    p = e / e.sum(-1, keepdims=True)
-    r = {"probs": (p, p * (1.0 + A + (p * A).sum(-1, keepdims=True)))}
-    pd = p * ks                                # P': after dropout
-    r["out"] = (pd @ v, pd @ av)
-    r["dv"] = (T(pd) @ do, T(pd) @ ado)
-    dp, dpm = (do @ T(v)) * ks, (ado @ T(av)) * ks
-    dot, dotm = (p * dp).sum(-1, keepdims=True), (p * dpm).sum(-1, keepdims=True)
-    ds, dsm = p * (dp - dot) * scale, p * (dpm + dotm) * scale
-    r["dq"] = (ds @ k, dsm @ ak)
-    r["dk"] = (T(ds) @ q, T(dsm) @ aq)
-    return r
-
-
-def rows(x):
-    """[nseq, H, L, hd] -> the [nseq * L, H * hd] layout of the operands"""
-    n, H, L, hd = x.shape
-    return np.ascontiguousarray(x.transpose(0, 2, 1, 3)).reshape(n * L, H * hd)
-
-
-def heads(x, nseq, L, H, hd):
-    return x.reshape(nseq, L, H, hd).transpose(0, 2, 1, 3)
-
-
-def worst_ratio(got, ref, S, u, floor=0.0):
-    """max (|got - ref| - floor) / (u S); where S is 0 the result must be the reference exactly (to the floor)"""
-    got = got.detach().double().cpu().numpy().reshape(ref.shape)
-    err = np.maximum(np.abs(got - ref) - floor, 0.0)
-    if not np.isfinite(got).all() or bool((err[S == 0] != 0).any()):
-        return math.inf
-    nz = S > 0
-    return float((err[nz] / (u * S[nz])).max()) if nz.any() else 0.0
 
 
 def run_case(c):
