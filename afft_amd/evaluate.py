@@ -80,12 +80,17 @@ def evaluate_scores(model, class_mappings, data_loader: Iterable, device, to_pro
 
 
 @torch.no_grad()
-def evaluate(model, dataset, data_loader: Iterable, device, precision: Optional[str] = None) -> Dict[str, float]:
+def evaluate(model, dataset, data_loader: Iterable, device, precision: Optional[str] = None, ema=None) -> Dict[str, float]:
     """test.py:64-98: the verb / noun / action performance overall, on the many-shot classes, on unseen participants and on the tail
     classes.  collect_logits, then challenge.marginalize_scores (to_prob=True), then challenge.device_accuracies_epic with
     compute_manyshot_unseen_tail=True, then print_accuracies_epic; returns the accuracies dict (the reference prints it only).  Nothing
-    of width N x C leaves the device: what comes back per space is 2 C + 3 integer counters per row group."""
+    of width N x C leaves the device: what comes back per space is 2 C + 3 integer counters per row group.
+    ema (an afft_amd.optim.WeightEMA over the model's parameters): the whole evaluation runs inside ema.applied(), on the averaged
+    weights; the live weights and their images are back, bit for bit, when it returns."""
     from . import challenge  # noqa: PLC0415
+    if ema is not None:
+        with ema.applied():
+            return evaluate(model, dataset, data_loader, device, precision=precision)
     _, logits = collect_logits(model, data_loader, device, precision=precision)
     verb, noun, action = marginalize_scores(logits, dataset.class_mappings, to_prob=True)
     accuracies = challenge.device_accuracies_epic([verb, noun, action], dataset, compute_manyshot_unseen_tail=True)

@@ -831,6 +831,22 @@ def adam_runs(p: Tensor, g: Tensor, m: Tensor, v: Tensor, runs: Tensor, lr: floa
                                    beta2, eps, wd, gscale, _p(step), L.ADAM_DECOUPLED if decoupled else 0, _p(ok), _stream()), "adam_runs")
 
 
+def ema(ema_: Tensor, p: Tensor, w: float, ok: Optional[Tensor] = None):
+    """ema_ += w * (p - ema_) over two flat fp32 buffers (w = 1 - decay in [0, 1]; one subtraction and one fma per element, an element
+    equal to its parameter keeps its bits); ok as in sgd_nesterov: on 0 nothing is written"""
+    assert ema_.is_contiguous() and p.is_contiguous()
+    assert ema_.dtype == p.dtype == torch.float32 and ema_.numel() == p.numel() and ema_.device == p.device
+    assert ok is None or (ok.dtype == torch.float32 and ok.device == p.device)
+    L.check(L.lib().afft_ema(_p(ema_), _p(p), p.numel(), w, _p(ok), _stream()), "ema")
+
+
+def swap_f32(a: Tensor, b: Tensor):
+    """a <-> b, bit for bit, over two flat fp32 buffers that do not overlap"""
+    assert a.is_contiguous() and b.is_contiguous()
+    assert a.dtype == b.dtype == torch.float32 and a.numel() == b.numel() and a.device == b.device
+    L.check(L.lib().afft_swap_f32(_p(a), _p(b), a.numel(), _stream()), "swap_f32")
+
+
 def pack_weight(w: Tensor, dst: Tensor) -> Tensor:
     """fp32 weight [rows, cols] (row stride free; rows % 16 == 0, cols % 32 == 0) -> its fragment-packed bf16 image `dst`
     (rows * cols elements, contiguous): include/afft_hip.h afft_pack_weight"""

@@ -46,7 +46,8 @@ import torch
 import torch.distributed as dist
 
 from . import ops, runtime as rt
-from .parallel import FlatParams, FusedAdam, FusedSGD, GradReducer, _FusedEpilogue
+from .parallel import (FlatParams, FusedAdam, FusedSGD, GradReducer, WeightEMA, _FusedEpilogue, check_ema_decay,   # noqa: F401
+                       refuse_step_on_averaged)      # WeightEMA: public here
 
 Tensor = torch.Tensor
 
@@ -105,6 +106,16 @@ class _FlatOptimizer(torch.optim.Optimizer, _FusedEpilogue):
         if self.reducer.world > 1 and self.reducer.comm:
             self.sync_parameters(group)
         _ENGINES.append(weakref.ref(self))
+        # ema_decay / ema_warmup (keyword arguments of every subclass; Hydra: +opt.optimizer.ema_decay=0.9998): a WeightEMA of the
+        # parameters as self.ema, updated at the end of step().  None (the default): no average, no buffer, no launch
+        decay, warmup = self._ema_args
+        self.ema: Optional[WeightEMA] = WeightEMA(self, decay, warmup) if decay is not None else None
+
+    def _take_ema_args(self, ema_decay: Optional[float], ema_warmup: bool):
+        """called first in a subclass's __init__: a bad ema_decay is a ValueError before any parameter is re-homed"""
+        if ema_decay is not None:
+            check_ema_decay(ema_decay, self._what)
+        self._ema_args = (ema_decay, ema_warmup)
 
     def _make_engine(self):
         raise NotImplementedError
@@ -159,6 +170,7 @@ class _FlatOptimizer(torch.optim.Optimizer, _FusedEpilogue):
     # ------------------------------------------------------------------ the torch.optim.Optimizer interface
     def zero_grad(self, set_to_none: bool = True):
         """Start of a backward pass (module docstring).  set_to_none is ignored: the gradients live in the flat buffer."""
+        refuse_step_on_averaged(self.flat, f"{self._what}.zero_grad()")      # the update it arms runs inside backward()
         if self._armed:
             self._disarm()
         if rt.grad_mode() != "sink":
@@ -226,6 +238,7 @@ class _FlatOptimizer(torch.optim.Optimizer, _FusedEpilogue):
         loss = None
         if closure is not None:
             raise NotImplementedError(f"{self._what}.step: closures are not supported (the update runs inside backward())")
+        refuse_step_on_averaged(self.flat, f"{self._what}.step()")
         if self._armed:
             done = getattr(self, "_finished_in_backward", False)
             try:
@@ -252,6 +265,8 @@ class _FlatOptimizer(torch.optim.Optimizer, _FusedEpilogue):
             self._sync_hyper()
             self.opt.step(self.flat.flat_g, 1.0, grad_clip=self.grad_clip)
         self._publish_state()
+        if self.ema is not None:
+            self.ema.update()
         return loss
 
     def add_param_group(self, param_group):
@@ -265,12 +280,15 @@ class SGD(_FlatOptimizer):
     Extra keyword arguments: comm_dtype ('fp32' | 'bf16' gradient payload), comm_algo ('allreduce' | 'rs_ag' | 'sharded': the
     update of the GEMM weights in 1 / N slices with an all-gather of their 16-bit images, parallel.GradReducer), bucket_elems,
     group, in_backward (update inside the backward pass; default on), grad_clip (clip by global norm inside step(), on the
-    device, instead of the loop's clip_grad_norm_ call)."""
+    device, instead of the loop's clip_grad_norm_ call), ema_decay / ema_warmup (a WeightEMA of the parameters as self.ema, updated
+    at the end of step(); default off)."""
 
     def __init__(self, params, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
                  nesterov: bool = False, *, maximize: bool = False, foreach=None, differentiable: bool = False, fused=None,
                  comm_dtype: Optional[str] = None, comm_algo: Optional[str] = None, bucket_elems: int = 32 * 1024 * 1024,
-                 group=None, in_backward: Optional[bool] = None, grad_clip: Optional[float] = None):
+                 group=None, in_backward: Optional[bool] = None, grad_clip: Optional[float] = None, ema_decay: Optional[float] = None,
+                 ema_warmup: bool = True):
+        self._take_ema_args(ema_decay, ema_warmup)
         if lr < 0.0 or momentum < 0.0 or weight_decay < 0.0:
             raise ValueError("afft_amd.optim.SGD: negative lr / momentum / weight_decay")
         if nesterov and (momentum <= 0 or dampening != 0):
@@ -326,7 +344,7 @@ class SGD(_FlatOptimizer):
 
 class Adam(_FlatOptimizer):
     """torch.optim.Adam(params, lr, betas, eps, weight_decay, decoupled_weight_decay) on the flat path (module docstring), with the
-    extra keyword arguments of SGD (comm_dtype, comm_algo, bucket_elems, group, in_backward, grad_clip).  decoupled_weight_decay=True
+    extra keyword arguments of SGD (comm_dtype, comm_algo, bucket_elems, group, in_backward, grad_clip, ema_decay, ema_warmup).  decoupled_weight_decay=True
     is AdamW (as in torch).  lr and weight_decay may differ per group (schedulers drive them); betas and eps must be the same in
     every group.  Never fused into the weight-gradient GEMM epilogues: on one GPU the update runs per bucket on the side stream
     inside backward.  state[p] holds 'exp_avg' and 'exp_avg_sq' (views of the flat moment buffers) and 'step' (the device step
@@ -339,7 +357,8 @@ class Adam(_FlatOptimizer):
                  amsgrad: bool = False, *, foreach=None, maximize: bool = False, capturable: bool = False, differentiable: bool = False,
                  fused=None, decoupled_weight_decay: Optional[bool] = None, comm_dtype: Optional[str] = None,
                  comm_algo: Optional[str] = None, bucket_elems: int = 32 * 1024 * 1024, group=None, in_backward: Optional[bool] = None,
-                 grad_clip: Optional[float] = None):
+                 grad_clip: Optional[float] = None, ema_decay: Optional[float] = None, ema_warmup: bool = True):
+        self._take_ema_args(ema_decay, ema_warmup)
         decoupled = self._DECOUPLED if decoupled_weight_decay is None else bool(decoupled_weight_decay)
         if weight_decay is None:
             weight_decay = 1e-2 if decoupled else 0.0

@@ -18,6 +18,7 @@ from __future__ import annotations
 
 from typing import Callable, Dict, List, Optional
 
+import contextlib
 import os
 import torch
 import torch.distributed as dist
@@ -96,6 +97,7 @@ class FlatParams:
         # time a step runs in that precision (ensure_f16) and from then on written by every optimizer kernel beside the bf16 ones
         self.flat_h16: Optional[Tensor] = None
         self.flat_p8: Optional[Tensor] = None      # e4m3(2^8 p) byte images (the fp8 lo pass of 'fp16x2': runtime.lo8), allocated with flat_h16
+        self.averaged = False      # inside WeightEMA.applied(): flat_p holds the averaged weights, and nothing may update them
         with torch.no_grad():
             for p, o in zip(self.params, self.offsets):
                 n = p.numel()
@@ -628,6 +630,137 @@ class FusedAdam(_FlatUpdate):
         super().end_step()
 
 
+def check_ema_decay(decay, what: str) -> float:
+    if not (isinstance(decay, (int, float)) and 0.0 < float(decay) < 1.0):
+        raise ValueError(f"{what}: ema_decay must lie in (0, 1), got {decay!r}")
+    return float(decay)
+
+
+class WeightEMA:
+    """Exponential moving average of the weights over the flat parameter buffer (public name: ``afft_amd.optim.WeightEMA``): one
+    fp32 shadow buffer shaped like ``flat_p``, blended with it once per step by ONE launch (ops.ema, 12 B per parameter),
+
+        ema += w * (p - ema),    w = float32(1 - decay_eff),    decay_eff = min(decay, (1 + t) / (10 + t)) with `warmup`, else decay
+
+    (t = the number of earlier update() calls: the timm / TF rule, so the average follows the first steps closely instead of
+    remembering the initialisation for 1 / (1 - decay) steps).
+
+    owner: anything with a FlatParams as ``.flat`` -- an afft_amd.optim.SGD / Adam / AdamW, a parallel.Trainer -- or a FlatParams
+    itself.  The owner's "step is finite" flag (_FlatUpdate.ok) is picked up when it has one: a step the optimizer skipped does not
+    move the average.  `t` is a host counter and advances on such a step all the same (reading the flag back would cost the
+    device sync the flag exists to avoid): after a skipped step the warm-up is one step ahead of the average, which only matters
+    during the first few dozen steps.
+
+    Data parallelism: with all-reduce replicas the parameters are bitwise equal on every rank, and so are the averages -- nothing is
+    exchanged.  Under the sharded update (comm_algo = 'sharded', more than one rank) the fp32 masters of the other ranks' slices
+    are stale between sync_masters() calls, so a per-step average of flat_p would average stale values: refused at construction."""
+
+    def __init__(self, owner, decay: float = 0.9998, warmup: bool = True):
+        self.decay = check_ema_decay(decay, "WeightEMA")
+        self.warmup = bool(warmup)
+        flat = owner if isinstance(owner, FlatParams) else getattr(owner, "flat", None)
+        if not isinstance(flat, FlatParams):
+            raise TypeError("WeightEMA: owner must be a FlatParams or have one as .flat (afft_amd.optim.SGD / Adam / AdamW, parallel.Trainer)")
+        red = getattr(owner, "reducer", None)
+        world = red.world if red is not None else (dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1)
+        sharded = red.comm_algo == "sharded" if red is not None else flat.sharded_layout
+        if sharded and world > 1:
+            raise NotImplementedError("WeightEMA: comm_algo='sharded' on more than one rank is not supported: the fp32 masters of the "
+                                      "other ranks' slices are stale between sync_masters() calls, and the average is taken of the masters")
+        self.flat = flat
+        self.ok: Optional[Tensor] = getattr(getattr(owner, "opt", None), "ok", None)
+        self.num_updates = 0
+        self.ema = flat.flat_p.detach().clone()
+        self._applied = False
+        self.names = self._names_of(owner)
+
+    def _names_of(self, owner) -> List[str]:
+        """one name per parameter of the flat buffers, in their order: the optimizer's groups' `name` (common.scheduler.prepare_params),
+        the model's parameter names for a Trainer, else -- or where those are missing or repeat -- the position"""
+        by_id: Dict[int, str] = {}
+        if hasattr(owner, "param_groups"):
+            by_id = {id(p): g["name"] for g in owner.param_groups if isinstance(g.get("name"), str) for p in g["params"] if len(g["params"]) == 1}
+        elif isinstance(getattr(owner, "model", None), torch.nn.Module):
+            by_id = {id(p): n for n, p in owner.model.named_parameters()}
+        names = [by_id.get(id(p)) for p in self.flat.params]
+        if any(n is None for n in names) or len(set(names)) != len(names):
+            names = [str(i) for i in range(len(self.flat.params))]
+        return names
+
+    def decay_at(self, t: int) -> float:
+        """the decay the update after `t` earlier ones uses"""
+        return min(self.decay, (1.0 + t) / (10.0 + t)) if self.warmup else self.decay
+
+    @torch.no_grad()
+    def update(self):
+        """one launch on the current stream; call it after optimizer.step(), which has joined the streams the update ran on"""
+        if self._applied:
+            raise RuntimeError("WeightEMA.update() inside applied(): flat_p holds the averaged weights")
+        w = L_.f32(1.0 - self.decay_at(self.num_updates)).value      # 1 - decay in double, rounded once to the kernel's fp32
+        ops.ema(self.ema, self.flat.flat_p, w, ok=self.ok)
+        self.num_updates += 1
+
+    def _exchange(self):
+        with torch.no_grad():
+            ops.swap_f32(self.flat.flat_p, self.ema)
+            self.flat.refresh_images()
+
+    @contextlib.contextmanager
+    def applied(self):
+        """Inside the block the model computes with the averaged weights: flat_p and the average are exchanged exactly (ops.swap_f32)
+        and every weight image -- bf16, fp16, e4m3, fragment-packed, the padded cast images of odd shapes -- is re-derived
+        (FlatParams.refresh_images); on leaving, the same again, so flat_p, the average and every image are bit for bit what they
+        were.  Not re-entrant; update() and optimizer steps inside the block raise RuntimeError."""
+        if self._applied or self.flat.averaged:
+            raise RuntimeError("WeightEMA.applied() is not re-entrant")
+        self._exchange()
+        self._applied = self.flat.averaged = True
+        try:
+            yield self
+        finally:
+            self._exchange()
+            self._applied = self.flat.averaged = False
+
+    def _slices(self):
+        for name, p, o in zip(self.names, self.flat.params, self.flat.offsets):
+            yield name, p, self.ema[o:o + p.numel()].view(p.shape)
+
+    def averaged_state_dict(self, module: torch.nn.Module) -> Dict[str, Tensor]:
+        """module.state_dict() with every parameter of the flat buffers replaced by a clone of its average; buffers and parameters
+        outside the flat buffers (frozen ones) are copied as they are.  Loads into the reference's model with load_state_dict."""
+        if self._applied:
+            raise RuntimeError("WeightEMA.averaged_state_dict() inside applied(): the buffers are exchanged")
+        avg = {id(p): v for _, p, v in self._slices()}
+        return type(module.state_dict())((k, avg.get(id(t), t).detach().clone()) for k, t in module.state_dict(keep_vars=True).items())
+
+    def state_dict(self) -> dict:
+        """decay, warmup, num_updates and the average as per-parameter tensors under `names` (views of the flat average, as an
+        optimizer's state_dict() hands out its state: torch.save copies).  Saved BESIDE the optimizer's state_dict, which stays
+        interchangeable with torch's."""
+        if self._applied:
+            raise RuntimeError("WeightEMA.state_dict() inside applied(): the buffers are exchanged")
+        return {"decay": self.decay, "warmup": self.warmup, "num_updates": self.num_updates, "ema": {n: v for n, _, v in self._slices()}}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd: dict):
+        if self._applied:
+            raise RuntimeError("WeightEMA.load_state_dict() inside applied(): the buffers are exchanged")
+        if set(sd["ema"]) != set(self.names):
+            raise ValueError(f"WeightEMA.load_state_dict: parameter names differ ({sorted(set(sd['ema']) ^ set(self.names))[:4]} ...)")
+        for n, p, v in self._slices():
+            if sd["ema"][n].shape != p.shape:
+                raise ValueError(f"WeightEMA.load_state_dict: {n}: shape {tuple(sd['ema'][n].shape)}, parameter {tuple(p.shape)}")
+        self.decay, self.warmup = check_ema_decay(sd["decay"], "WeightEMA.load_state_dict"), bool(sd["warmup"])
+        self.num_updates = int(sd["num_updates"])
+        for n, _, v in self._slices():
+            v.copy_(sd["ema"][n])
+
+
+def refuse_step_on_averaged(flat: FlatParams, what: str):
+    if flat.averaged:
+        raise RuntimeError(f"{what} inside WeightEMA.applied(): flat_p holds the averaged weights")
+
+
 class _FusedEpilogue:
     """The optimizer fused into the weight-gradient GEMM epilogues (single GPU), shared by Trainer and afft_amd.optim.SGD.
     Needs: self.flat (FlatParams), self.opt (FusedSGD), self.reducer (GradReducer), self.grad_clip, self._fused (None until
@@ -754,10 +887,16 @@ class Trainer(_FusedEpilogue):
                  comm_dtype: str = "fp32", bucket_elems: int = 32 * 1024 * 1024, group=None,
                  overlap_optimizer: bool = True, force_comm: bool = False, grad_clip: Optional[float] = None,
                  comm_algo: str = "allreduce", cls_weight: Optional[Dict[str, Tensor]] = None, label_smoothing: float = 0.0,
-                 focal_gamma: float = 0.0, logit_adjust: Optional[Dict[str, Tensor]] = None):
+                 focal_gamma: float = 0.0, logit_adjust: Optional[Dict[str, Tensor]] = None, ema_decay: Optional[float] = None,
+                 ema_warmup: bool = True):
         """cls_weight / label_smoothing / focal_gamma / logit_adjust: class weights per target type, label smoothing, the focal exponent
         and the logit adjustment per target type of the classification terms, as common.runner.Runner takes them; the defaults leave
-        the loss as it was."""
+        the loss as it was.
+        ema_decay (default None: no average, no buffer, no launch): keep a WeightEMA of the parameters as `self.ema`; step() ends
+        with its update() whenever it updated the parameters.  With a captured graph the EMA launch goes AFTER the replay, not
+        into the capture: its weight changes from step to step during the warm-up, and a captured launch would freeze it."""
+        if ema_decay is not None:
+            check_ema_decay(ema_decay, "Trainer")
         from .common.runner import BasicLossAccuracy, Runner
         self.model = model
         self.flat = FlatParams(model, sharded_layout=(comm_algo == "sharded"))
@@ -779,6 +918,7 @@ class Trainer(_FusedEpilogue):
         self.grad_clip = grad_clip     # opt.grad_clip of the reference's config; needs the whole gradient first
         self.overlap_optimizer = overlap_optimizer and grad_clip is None and (self.flat.flat_p.is_cuda or comm_algo == "sharded")
         self._fused: Optional[Dict[int, object]] = None    # id(weight) -> _lib.SgdFused, once learned (see _enable_fused)
+        self.ema: Optional[WeightEMA] = WeightEMA(self, ema_decay, ema_warmup) if ema_decay is not None else None
 
     def sync_masters(self):
         """sharded update: whole fp32 masters and momentum on every rank (a collective: every rank calls it)"""
@@ -813,6 +953,7 @@ class Trainer(_FusedEpilogue):
         """mixup_fn / mixup_backbone: as in Runner.__call__ (common/runner.py:238-249; expts/01 trains with
         train.use_mixup=true, train.mixup_backbone=true): MixUp inside BaseModel.forward after the backbones, or on the
         features before the model; the losses then take soft targets and the ignore mask MixUp returns."""
+        refuse_step_on_averaged(self.flat, "Trainer.forward_backward()")
         self.reducer.on_bucket = self.opt.step_range if optimize_in_backward else None
         if not optimize_in_backward and self.reducer.masters_stale:
             self.reducer.sync_masters()      # a replicated whole-buffer update follows: it must not start from stale masters / momentum
@@ -939,7 +1080,10 @@ class Trainer(_FusedEpilogue):
              mixup_backbone: bool = True):
         g = getattr(self, "_graph", None)
         if g is not None and optimize and mixup_fn is None and self._feed_graph(feats, target, target_subclips):
+            refuse_step_on_averaged(self.flat, "Trainer.step()")
             g.replay()
+            if self.ema is not None:
+                self.ema.update()
             return self._graph_io
         fused = optimize and self.overlap_optimizer
         loss, parts = self.forward_backward(feats, target, target_subclips, optimize_in_backward=fused, mixup_fn=mixup_fn,
@@ -947,6 +1091,8 @@ class Trainer(_FusedEpilogue):
         if optimize and not fused:
             g, scale = self.reducer.grad_for_optimizer()
             self.opt.step(g, scale, grad_clip=self.grad_clip)
+        if optimize and self.ema is not None:
+            self.ema.update()
         return loss, parts
 
 

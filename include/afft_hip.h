@@ -203,7 +203,8 @@ int afft_gemm_plan_for(const afft_gemm_t* g, afft_gemm_trace_rec_t* out);
  * open every afft_attention_fwd / _bwd and afft_layernorm_fwd / _bwd call -- from any entry point, the composite ones included --
  * is bracketed by a HIP event pair on its stream.  bytes = the algorithmic HBM bytes of the call (every operand read once, every
  * result written once), flops = its MFMA-shaped work (attention only).  One trace at a time, process-wide. */
-enum { AFFT_K_ATTN_FWD = 1, AFFT_K_ATTN_BWD = 2, AFFT_K_LN_FWD = 3, AFFT_K_LN_BWD = 4 };
+enum { AFFT_K_ATTN_FWD = 1, AFFT_K_ATTN_BWD = 2, AFFT_K_LN_FWD = 3, AFFT_K_LN_BWD = 4,
+       AFFT_K_EMA = 5, AFFT_K_SWAP_F32 = 6 };   /* afft_ema, afft_swap_f32: rows = n, width = 1 */
 typedef struct {
   int32_t kind, rows, width, reserved;
   int64_t bytes, flops;
@@ -732,6 +733,18 @@ int afft_adam(float* p, const void* g, int32_t g_dtype, float* m, float* v, void
 int afft_adam_runs(float* p, const float* g, float* m, float* v, void* p_bf16, void* p_f16, void* p_f8,
                    const int64_t* runs, int32_t nruns, float lr, float beta1, float beta2, float eps, float wd,
                    float gscale, const float* step_dev, int32_t flags, const float* ok, void* stream);
+/* Exponential moving average of the weights over one flat fp32 buffer (the shadow copy evaluated and checkpointed in place of the
+ * live weights: timm ModelEma / torch.optim.swa_utils.AveragedModel, here one launch over parallel.FlatParams.flat_p):
+ *   ema[i] = fma(w, p[i] - ema[i], ema[i]),  w = 1 - decay in [0, 1]
+ *   one rounding of the difference, one of the fma, pinned; an element with p[i] == ema[i] keeps its bits, and w = 0 keeps the
+ *   whole buffer (no launch).  ok: see afft_sgd_fused_t.ok -- on 0 nothing at all is written (a step the optimizer skipped does
+ *   not move the average).  n >= 0 elements (0: no launch); ema and p any 4-byte aligned, non-overlapping addresses: 16-byte
+ *   accesses when both are 16-byte aligned, element accesses otherwise, the same bits either way.  12 B per element of HBM
+ *   traffic; no atomics, no scratch: the same inputs give the same bits. */
+int afft_ema(float* ema, const float* p, int64_t n, float w, const float* ok, void* stream);
+/* a[i] <-> b[i] for n fp32 elements, bit for bit (NaN payloads and signed zeros included), one pass, 16 B per element: the
+ * averaged weights into the parameters' place and back.  a and b must not overlap; addresses and n as in afft_ema. */
+int afft_swap_f32(float* a, float* b, int64_t n, void* stream);
 /* Gradient clipping by global norm (train.py:254-260, torch.nn.utils.clip_grad_norm_), without a host sync:
  *   afft_sumsq: *out += scale * sum x[i]^2 over a flat fp32/bf16 buffer (scale = gscale^2 of the optimizer), ordered
  *   through the stream's workspace (see afft_mse) - the clipping coefficient is bit-reproducible;
