@@ -39,6 +39,22 @@ def marginalize_scores(res_action: torch.Tensor, class_mappings: Dict[Tuple[str,
     return [out[0], out[1], res_action]
 
 
+def group_of_from_mapping(M) -> torch.Tensor:
+    """int64 [A] group (verb, noun) of every action class from a one-hot [A, G] class mapping (the dataset's
+    class_mappings[('verb', 'action')], as marginalize_scores takes it): the column of the row's non-zero entry; a row that is all zero
+    gives -1 (the class is in no group); a row with more than one non-zero entry is no partition and raises ValueError.  The form
+    common.runner.MarginalCrossEntropy and ops.group_csr take."""
+    M = torch.as_tensor(M)
+    if M.dim() != 2:
+        raise ValueError(f"group_of_from_mapping: a class mapping is a matrix [A, G], got {tuple(M.shape)}")
+    hot = M != 0
+    per_row = hot.sum(1)
+    if bool((per_row > 1).any()):
+        row = int(torch.nonzero(per_row > 1)[0])
+        raise ValueError(f"group_of_from_mapping: class {row} maps to {int(per_row[row])} groups; a marginal needs at most one")
+    return torch.where(per_row == 1, hot.to(torch.int64).argmax(1), -1)
+
+
 EPIC100_VERSION = 0.2       # datasets/epic_kitchens.py: the dataset object's `version` for EPIC-KITCHENS-100
 
 

@@ -109,18 +109,81 @@ class MultiDimCrossEntropy(nn.Module):
         return row_loss
 
 
+class MarginalCrossEntropy(nn.Module):
+    """Per-row cross entropy on a MARGINAL of the softmax over the action classes: -log sum_{a in group} softmax(x)_a, the quantity
+    challenge.marginalize_scores ranks verbs and nouns by, from the action logits alone (no second classifier head).
+    group_of ([A], an integer type; challenge.group_of_from_mapping makes it from a class mapping): the group (verb, noun) of every
+    action class, -1: in none.  num_groups: the number of groups (default: the largest entry + 1).  A plain attribute, no buffer: it
+    is no part of the state dict; its device form (ops.group_csr) is built once per device, at first use.
+    forward takes ACTION targets, as MultiDimCrossEntropy does on the same logits: a hard label a becomes group_of[a] (-1 stays -1,
+    and an action in no group is ignored like it), a soft (MixUp) target [rows, A] is summed into [rows, G] group by group (mass on
+    ungrouped actions is left out); the row filter and its kept-row renormalisation are MultiDimCrossEntropy's."""
+
+    def __init__(self, group_of: torch.Tensor, num_groups: Optional[int] = None):
+        super().__init__()
+        group_of = torch.as_tensor(group_of)
+        assert group_of.dim() == 1 and not group_of.dtype.is_floating_point, "group_of: one integer entry per action class"
+        self.group_of = group_of.to(torch.int64)
+        top = int(self.group_of.max()) + 1 if self.group_of.numel() else 0
+        self.num_groups = top if num_groups is None else int(num_groups)
+        self._device_form = {}      # device -> (the ops.group_csr triple, group_of int64, group_of with -1 as num_groups)
+
+    def _on(self, device):
+        if device not in self._device_form:
+            from .. import ops
+            go = self.group_of.to(device)
+            self._device_form[device] = (ops.group_csr(self.group_of, self.num_groups, device=device), go,
+                                         torch.where(go < 0, self.num_groups, go))
+        return self._device_form[device]
+
+    def group_targets(self, tgt, A: int, one_hot: bool, device):
+        """the GROUP targets of action targets: int64 [rows] labels, or a fp32 [rows, G] view (row pitch G + 1) of soft targets"""
+        _, go, go_pad = self._on(device)
+        G = self.num_groups
+        if not one_hot:
+            labels = tgt.reshape(-1).to(torch.int64)
+            inside = (labels >= 0) & (labels < A)
+            # an action label outside [-1, A) becomes the group label G: out of range there as well, the row comes out NaN
+            return torch.where(inside, go[labels.clamp(0, A - 1)], torch.where(labels == -1, labels, G)).contiguous()
+        soft = tgt.reshape(-1, A).to(torch.float32)
+        return torch.zeros(soft.shape[0], G + 1, dtype=torch.float32, device=device).index_add_(1, go_pad, soft)[:, :G]
+
+    def forward(self, inp, tgt, one_hot: bool = False, ignore_index: Union[torch.Tensor, None] = None):
+        A = inp.size(-1)
+        assert A == self.group_of.numel(), f"group_of has {self.group_of.numel()} entries, the logits {A} classes"
+        groups = self._on(inp.device)[0]
+        inp2 = inp if (inp.dim() == 3 and inp.stride(2) == 1 and inp.dtype == torch.float32) else inp.reshape(-1, A)
+        rows = inp.numel() // A
+        if not one_hot:
+            return F_.SoftmaxCEGroups.apply(inp2, groups, self.group_targets(tgt, A, False, inp.device), None, None)
+        keep = None
+        if ignore_index is not None:
+            keep = (~ignore_index.reshape(-1)).to(torch.uint8).contiguous()
+        row_loss = F_.SoftmaxCEGroups.apply(inp2, groups, None, self.group_targets(tgt, A, True, inp.device), keep)
+        if keep is not None:
+            row_loss = row_loss * (float(rows) / keep.sum().clamp(min=1).to(torch.float32))
+        return row_loss
+
+
 class BasicLossAccuracy(nn.Module):
     """acc1 / acc5 / mt5r inputs and the three loss terms."""
 
     def __init__(self, compute_metrics: bool = True, lazy_host: bool = False, device_metrics: bool = False,
                  cls_weight: Optional[Dict[str, torch.Tensor]] = None, label_smoothing: float = 0.0,
-                 focal_gamma: float = 0.0, logit_adjust: Optional[Dict[str, torch.Tensor]] = None):
+                 focal_gamma: float = 0.0, logit_adjust: Optional[Dict[str, torch.Tensor]] = None,
+                 marginal: Optional[Dict[str, torch.Tensor]] = None):
         """cls_weight: target type ('action', 'verb', ...) -> [C] class weights (common.class_weights.class_weights makes them from
         counts); a type that is missing has none.  logit_adjust: target type -> [C] logit adjustment (common.class_weights.
         logit_adjustment), likewise; it enters the loss only, the metrics below see the raw logits.  label_smoothing and focal_gamma
         apply to every type.  One criterion per target type serves its future and its past term; cls_criterion (no weights, no
-        adjustment) serves the types neither dictionary names."""
+        adjustment) serves the types neither dictionary names.
+        marginal: space name ('verb', 'noun') -> group_of [A] of the ACTION classes (challenge.group_of_from_mapping): for each space
+        the marginal cross-entropy (MarginalCrossEntropy) of target type 'action' is added as marg_{space}_action_{modk}, and as
+        past_marg_{space}_action_{modk} where past logits exist; loss_wts must name them.  None: nothing is added or launched."""
         super().__init__()
+        self.marginal = None
+        if marginal:
+            self.marginal = nn.ModuleDict({space: MarginalCrossEntropy(g) for space, g in marginal.items()})
         cls_weight = {t: w for t, w in (cls_weight or {}).items() if w is not None}
         logit_adjust = {t: b for t, b in (logit_adjust or {}).items() if b is not None}
         self.cls_criterion = MultiDimCrossEntropy(ignore_index=-1, reduction='none', label_smoothing=label_smoothing,
@@ -146,6 +209,10 @@ class BasicLossAccuracy(nn.Module):
 
     def criterion_for(self, tgt_type: Optional[str]):
         return self.cls_criteria[tgt_type] if tgt_type in self.cls_criteria else self.cls_criterion
+
+    def _marginals(self, tgt_type):
+        """(space, criterion) of the marginal terms of a target type: they are defined on the action classes alone"""
+        return self.marginal.items() if self.marginal is not None and tgt_type == 'action' else ()
 
     def forward_future_action(self, logits, tgt_val, mixup_enable, losses, metrics, acc1_key, acc5_key, mt5r_key,
                               loss_key, key_suffix='', tgt_type: Optional[str] = None):
@@ -208,8 +275,8 @@ class BasicLossAccuracy(nn.Module):
         metrics[acc5_key] = acc[1]
 
     def forward_past_action(self, past_logits, past_target, mixup_enable, losses, loss_key,
-                            past_target_ignore_index=None, key_suffix='', tgt_type: Optional[str] = None):
-        criterion = self.criterion_for(tgt_type)
+                            past_target_ignore_index=None, key_suffix='', tgt_type: Optional[str] = None, criterion=None):
+        criterion = self.criterion_for(tgt_type) if criterion is None else criterion
         if mixup_enable:
             assert past_logits.shape == past_target.shape
             assert past_target_ignore_index is not None
@@ -230,12 +297,17 @@ class BasicLossAccuracy(nn.Module):
                 self.forward_future_action(logits, tgt_val, mixup_enable, losses, metrics,
                                            f'acc1_{tgt_type}_{modk}', f'acc5_{tgt_type}_{modk}',
                                            f'mt5r_{tgt_type}_{modk}', f'cls_{tgt_type}_{modk}', tgt_type=tgt_type)
+                for space, criterion in self._marginals(tgt_type):
+                    losses[f'marg_{space}_{tgt_type}_{modk}'] = criterion(logits, tgt_val, one_hot=mixup_enable)
             past_key = f'{PAST_LOGITS_PREFIX}logits/{tgt_type}'
             if past_key in outputs and target_subclips is not None:
                 for modk in outputs[past_key]:
                     ign = None if target_subclips_ignore_index is None else target_subclips_ignore_index[tgt_type]
                     self.forward_past_action(outputs[past_key][modk], target_subclips[tgt_type], mixup_enable,
                                              losses, f'past_cls_{tgt_type}_{modk}', ign, tgt_type=tgt_type)
+                    for space, criterion in self._marginals(tgt_type):
+                        self.forward_past_action(outputs[past_key][modk], target_subclips[tgt_type], mixup_enable, losses,
+                                                 f'past_marg_{space}_{tgt_type}_{modk}', ign, criterion=criterion)
             if 'orig_past' in outputs and 'past_futures' in outputs:
                 for modk, upd in outputs['past_futures'].items():
                     if modk not in outputs['orig_past']:
@@ -437,11 +509,15 @@ class Runner:
     cls_weight ({target type: [C] class weights}) / label_smoothing: nn.CrossEntropyLoss's weight= and label_smoothing= for the future
       and past classification terms (BasicLossAccuracy); the defaults leave the loss and its kernel calls as they were.
     focal_gamma / logit_adjust ({target type: [C] adjustment}): the focal exponent and the logit adjustment of the same terms; the
-      adjustment enters the loss only -- the returned logits, the metrics and evaluation see raw logits.  Defaults: as they were."""
+      adjustment enters the loss only -- the returned logits, the metrics and evaluation see raw logits.  Defaults: as they were.
+    marginal ({space: group_of [A] of the action classes}, e.g. 'verb' / 'noun' from challenge.group_of_from_mapping): the marginal
+      cross-entropy terms marg_{space}_action_{modk} / past_marg_{space}_action_{modk} (BasicLossAccuracy); loss_wts must carry a
+      weight for them ('marg_verb', 'past_marg_verb', ...: found by prefix, like every other key).  None: as it was."""
 
     def __init__(self, model, device, loss_wts, compute_metrics: bool = True, async_metrics=None, device_metrics=None,
                  cls_weight: Optional[Dict[str, torch.Tensor]] = None, label_smoothing: float = 0.0,
-                 focal_gamma: float = 0.0, logit_adjust: Optional[Dict[str, torch.Tensor]] = None):
+                 focal_gamma: float = 0.0, logit_adjust: Optional[Dict[str, torch.Tensor]] = None,
+                 marginal: Optional[Dict[str, torch.Tensor]] = None):
         import os
         if async_metrics is None:
             async_metrics = False if os.environ.get("AFFT_RUNNER_SYNC", "0") == "1" else "lazy"
@@ -453,7 +529,7 @@ class Runner:
         self.device_metrics = bool(device_metrics)
         self.loss_acc_fn = BasicLossAccuracy(compute_metrics, lazy_host=bool(async_metrics), device_metrics=self.device_metrics,
                                              cls_weight=cls_weight, label_smoothing=label_smoothing, focal_gamma=focal_gamma,
-                                             logit_adjust=logit_adjust)
+                                             logit_adjust=logit_adjust, marginal=marginal)
         self.loss_wts = loss_wts
         self.async_metrics = async_metrics
 

@@ -260,6 +260,96 @@ __global__ __launch_bounds__(256) void softmax_ce_focal_kernel(const float* __re
   }
 }
 
+// Marginal cross-entropy over class groups (include/afft_hip.h): the classes of a row belong to G groups (group_of; -1: none), the
+// target is a group, loss = T lse - sum_g t_g lse_g, dlogits[c] = T p_c - t_g(c) exp(x_c - m_g(c)) / s_g(c) with m_g the group's OWN
+// maximum and s_g = sum_{c in g} exp(x_c - m_g): a group far below the row's top logit keeps its full precision.
+// Passes: row max, row sum (as softmax_ce_kernel); the groups, strided over the four waves, each group's members (CSR: offs, members)
+// strided over the wave's lanes, wave_max / wave_sum -- lane 0 leaves m_g and t_g / s_g in LDS and every wave keeps the sum of its own
+// t_g lse_g, groups front to back; the four sums and T in fixed order; the gradient.  A hard label is the soft target [g == y] and
+// visits group y alone (by the wave that a full walk gives it to).  Groups with t_g == 0 are not visited and may be empty.
+__global__ __launch_bounds__(256) void softmax_ce_groups_kernel(const float* __restrict__ logits, int64_t ldl, int C, int G,
+                                                                const int32_t* __restrict__ group_of,
+                                                                const int32_t* __restrict__ members,
+                                                                const int32_t* __restrict__ offs,
+                                                                const int64_t* __restrict__ glabels,
+                                                                const float* __restrict__ gsoft, int64_t ldgs,
+                                                                const uint8_t* __restrict__ keep, float gscale,
+                                                                const float* __restrict__ row_g, void* __restrict__ dlogits,
+                                                                int64_t ldd, int d_dtype, float* __restrict__ row_loss,
+                                                                int period, int64_t lgs, int64_t dgs) {
+  __shared__ float sh[4];
+  __shared__ float sh_m[AFFT_CE_GROUPS_MAX], sh_c[AFFT_CE_GROUPS_MAX];      // m_g and t_g / s_g (0: the group takes no part)
+  __shared__ int sh_empty;                                                  // a targeted group without members: the row is bad
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int clip = row / period, frame = row - clip * period;
+  const float* x = logits + (int64_t)clip * lgs + (int64_t)frame * ldl;
+  const int64_t drow = (int64_t)clip * dgs + (int64_t)frame * ldd;
+  bool kept = true;
+  int64_t lab = -1;
+  if (glabels) { lab = glabels[row]; kept = lab != -1; }
+  bool bad = glabels && (lab >= G || lab < -1);      // as in softmax_ce_kernel: nothing is read at `lab`, the row comes out NaN
+  if (keep) kept = kept && keep[row] != 0;
+  if (!kept) {  // uniform per block
+    if (dlogits) for (int c = tid; c < ldd; c += 256) st_any(dlogits, drow + c, d_dtype, 0.f);
+    if (row_loss && tid == 0) row_loss[row] = 0.f;
+    return;
+  }
+  if (tid == 0) sh_empty = 0;      // the barriers of the two block reductions below stand between this and the waves' own stores
+  float m = -INFINITY;
+  for (int c = tid; c < C; c += 256) m = fmaxf(m, x[c]);
+  m = block_reduce(m, sh, true);
+  float se = 0.f;
+  for (int c = tid; c < C; c += 256) se += expf(x[c] - m);
+  se = block_reduce(se, sh, false);
+  const float lse = m + logf(se);
+  const float* t = gsoft ? gsoft + (int64_t)row * ldgs : nullptr;
+  const int g0 = t ? 0 : (bad ? 0 : (int)lab), g1 = t ? G : (bad ? 0 : (int)lab + 1);
+  float part = 0.f;      // this wave's sum of t_g lse_g: the same value in all of its lanes
+  for (int g = g0 + wave; g < g1; g += 4) {      // everything in this loop is uniform per wave
+    const float tg = t ? t[g] : 1.f;
+    const int beg = offs[g], end = offs[g + 1];
+    if (tg == 0.f || end <= beg) {
+      if (lane == 0) { sh_c[g] = 0.f; if (tg != 0.f) sh_empty = 1; }
+      continue;
+    }
+    float mg = -INFINITY;
+    for (int i = beg + lane; i < end; i += 64) mg = fmaxf(mg, x[members[i]]);
+    mg = wave_max(mg);
+    float sg = 0.f;
+    for (int i = beg + lane; i < end; i += 64) sg += expf(x[members[i]] - mg);
+    sg = wave_sum(sg);
+    part += tg * (mg + logf(sg));
+    if (lane == 0) { sh_m[g] = mg; sh_c[g] = tg / sg; }
+  }
+  float tsum = 1.f;
+  if (t) {
+    tsum = 0.f;
+    for (int g = tid; g < G; g += 256) tsum += t[g];
+    tsum = block_reduce(tsum, sh, false);
+  }
+  const float tl = block_reduce(lane == 0 ? part : 0.f, sh, false);      // sh[0] + sh[1] + sh[2] + sh[3]; its barrier publishes sh_m / sh_c
+  bad = bad || sh_empty != 0;
+  if (tid == 0 && row_loss) row_loss[row] = bad ? NAN : lse * tsum - tl;
+  if (dlogits) {
+    const float inv = 1.0f / se;
+    if (row_g) gscale *= row_g[row];
+    for (int c = tid; c < ldd; c += 256) {
+      float g = 0.f;
+      if (c < C) {
+        const float p = expf(x[c] - m) * inv;
+        const int gi = group_of[c];
+        float q = 0.f;
+        if (!bad && gi >= 0 && (t || gi == lab)) {
+          const float coef = sh_c[gi];
+          if (coef != 0.f) q = coef * expf(x[c] - sh_m[gi]);
+        }
+        g = bad ? NAN : gscale * (p * tsum - q);
+      }
+      st_any(dlogits, drow + c, d_dtype, g);
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void mse_kernel(const float* __restrict__ a, int64_t lda, const float* __restrict__ b,
                                                   int64_t ldb, int rows, int d, float gscale,
                                                   const float* __restrict__ g_dev, float lscale,
@@ -478,6 +568,60 @@ extern "C" int afft_softmax_ce_frames_focal(const float* logits, int64_t clip_st
                                             void* stream_) {
   return ce_launch({logits, clip_stride, ldl, clips * frames, frames, C, labels, soft, lds, keep, gscale, row_g, dlogits, d_clip_stride,
                     ldd, d_dtype, row_loss, weight, smoothing, adjust, gamma, nullptr, true, stream_});
+}
+
+// One marginal cross-entropy call, from either of its two entry points (as CeCall / ce_launch above).
+struct CeGroupsCall {
+  const float* logits; int64_t lgs, ldl;
+  int32_t rows, period, C, G;
+  const int32_t* group_of; const int32_t* members; const int32_t* offs;
+  const int64_t* glabels; const float* gsoft; int64_t ldgs; const uint8_t* keep; float gscale; const float* row_g;
+  void* dlogits; int64_t dgs, ldd; int32_t d_dtype; float* row_loss;
+  float* loss_sum;
+  bool frames;
+  void* stream;
+};
+
+static int ce_groups_launch(const CeGroupsCall& c) {
+  hipStream_t stream = (hipStream_t)c.stream;
+  const char* name = c.frames ? "softmax_ce_frames_groups" : "softmax_ce_groups";
+  AFFT_CHECK(c.G >= 1 && c.G <= AFFT_CE_GROUPS_MAX, "%s: the number of groups G must lie in [1, %d] (got %d)", name, AFFT_CE_GROUPS_MAX, c.G);
+  AFFT_CHECK(c.logits, "%s: null logits", name);
+  AFFT_CHECK((c.glabels != nullptr) != (c.gsoft != nullptr), "%s: give exactly one of group labels / soft group targets", name);
+  AFFT_CHECK(c.C > 0 && c.ldl >= c.C && (!c.dlogits || c.ldd >= c.C) && (!c.gsoft || c.ldgs >= c.G) && (!c.frames || c.period > 0),
+             "%s: bad sizes", name);
+  // members may be null: no class is in any group (every offset is 0, nothing is read through it)
+  AFFT_CHECK(c.group_of && c.offs, "%s: null group_of / offs", name);
+  AFFT_CHECK((((uintptr_t)c.group_of | (uintptr_t)c.members | (uintptr_t)c.offs) & 3) == 0,
+             "%s: group_of, members and offs must be 4-byte aligned", name);
+  AFFT_CHECK(!c.loss_sum || c.row_loss, "%s: loss_sum is the ordered sum of row_loss: give row_loss as well", name);
+  if (c.rows == 0) return 0;
+  hipLaunchKernelGGL(softmax_ce_groups_kernel, dim3(c.rows), dim3(256), 0, stream, c.logits, c.ldl, c.C, c.G, c.group_of, c.members,
+                     c.offs, c.glabels, c.gsoft, c.ldgs, c.keep, c.gscale, c.row_g, c.dlogits, c.ldd, c.d_dtype, c.row_loss, c.period,
+                     c.lgs, c.dgs);
+  AFFT_LAUNCH_CHECK();
+  if (c.loss_sum) {
+    hipLaunchKernelGGL(ordered_sum_kernel, dim3(1), dim3(256), 0, stream, c.row_loss, (int64_t)c.rows, 1.0f, c.loss_sum, 1);
+    AFFT_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+extern "C" int afft_softmax_ce_groups(const float* logits, int64_t ldl, int32_t rows, int32_t C, int32_t G, const int32_t* group_of,
+                                      const int32_t* members, const int32_t* offs, const int64_t* glabels, const float* gsoft,
+                                      int64_t ldgs, const uint8_t* keep, float gscale, const float* row_g, float* loss_sum,
+                                      void* dlogits, int64_t ldd, int32_t d_dtype, float* row_loss, void* stream_) {
+  return ce_groups_launch({logits, 0, ldl, rows, rows, C, G, group_of, members, offs, glabels, gsoft, ldgs, keep, gscale, row_g,
+                           dlogits, 0, ldd, d_dtype, row_loss, loss_sum, false, stream_});
+}
+
+extern "C" int afft_softmax_ce_frames_groups(const float* logits, int64_t clip_stride, int64_t ldl, int32_t clips, int32_t frames,
+                                             int32_t C, int32_t G, const int32_t* group_of, const int32_t* members,
+                                             const int32_t* offs, const int64_t* glabels, const float* gsoft, int64_t ldgs,
+                                             const uint8_t* keep, float gscale, const float* row_g, void* dlogits,
+                                             int64_t d_clip_stride, int64_t ldd, int32_t d_dtype, float* row_loss, void* stream_) {
+  return ce_groups_launch({logits, clip_stride, ldl, clips * frames, frames, C, G, group_of, members, offs, glabels, gsoft, ldgs, keep,
+                           gscale, row_g, dlogits, d_clip_stride, ldd, d_dtype, row_loss, nullptr, true, stream_});
 }
 
 extern "C" int afft_mse_frames_bwd(const float* a, int64_t a_clip_stride, int32_t a_off, int32_t a_len, const float* b,

@@ -1971,6 +1971,37 @@ class SoftmaxCE(torch.autograd.Function):
         return (d,) + none
 
 
+class SoftmaxCEGroups(torch.autograd.Function):
+    """Per-row marginal cross-entropy over class groups (ops.softmax_ce_groups; reduction='none'; ignored rows give 0).
+    logits: [rows, C], or a (clips, frames, C) view with contiguous classes, walked in place.  groups: ops.group_csr(...) on the
+    logits' device.  glabels / gsoft: GROUP labels int64 [rows] or group targets fp32 [rows, G]; keep uint8 [rows].
+    The launch that computes the loss leaves the gradient of every row as well (when the logits want one); backward scales its rows
+    by the incoming gradient and hands autograd that fresh tensor -- no landing record: the action term owns it."""
+
+    @staticmethod
+    def forward(ctx, logits, groups, glabels, gsoft, keep):
+        if logits.dim() == 3:
+            assert logits.stride(2) == 1
+            lg = logits
+        else:
+            assert logits.dim() == 2
+            lg = logits if logits.stride(1) == 1 else logits.contiguous()
+        row_loss = torch.empty(lg.shape[:-1].numel(), dtype=torch.float32, device=lg.device)
+        d = torch.empty(lg.shape, dtype=torch.float32, device=lg.device) if ctx.needs_input_grad[0] else None
+        if lg.dim() == 3:
+            ops.softmax_ce_frames_groups(lg, lg.shape[-1], groups, glabels=glabels, gsoft=gsoft, keep=keep, dlogits3=d, row_loss=row_loss)
+        else:
+            ops.softmax_ce_groups(lg, lg.shape[-1], groups, glabels=glabels, gsoft=gsoft, keep=keep, dlogits=d, row_loss=row_loss)
+        ctx.d = d
+        return row_loss
+
+    @staticmethod
+    def backward(ctx, g_rows):
+        d = ctx.d
+        flush_ready()
+        return d * g_rows.reshape(d.shape[:-1] + (1,)), None, None, None, None
+
+
 class MSE(torch.autograd.Function):
     """mean((a-b)^2), gradient to both sides (common/runner.py:164-166).
     a, b: 2-D [rows, d], or -- `a_lo` given -- 3-D (B, Ta, C) / (B, Tb, C) of which the frames a[:, a_lo : a_lo + nt] and

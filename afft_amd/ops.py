@@ -654,6 +654,85 @@ def softmax_ce_frames_focal(logits3: Tensor, C_: int, *, labels: Optional[Tensor
                 adjust, gamma)
 
 
+def group_csr(group_of: Tensor, num_groups: Optional[int] = None, device=None) -> Tuple[Tensor, Tensor, Tensor]:
+    """The group description of softmax_ce_groups from a class -> group map: group_of [C] of an integer type, a value in [0, G) or -1
+    (the class is in no group); G = num_groups, or the largest value + 1.  Returns (group_of int32 [C], members int32 [grouped
+    classes]: group by group, ascending inside a group, offs int32 [G + 1]: offsets into members) on `device` (default: group_of's).
+    Built once per map: the check of the values reads them on the host."""
+    if group_of.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8) or group_of.dim() != 1:
+        raise ValueError(f"afft_amd: group_of must be a vector of an integer type, got {group_of.dtype} {tuple(group_of.shape)}")
+    device = group_of.device if device is None else device
+    go = group_of.detach().to("cpu", torch.int64)
+    top = int(go.max()) if go.numel() else -1
+    G = top + 1 if num_groups is None else int(num_groups)
+    if go.numel() and (int(go.min()) < -1 or top >= G):
+        raise ValueError(f"afft_amd: group_of must hold values in [-1, {G}), got [{int(go.min())}, {top}]")
+    members = torch.argsort(torch.where(go < 0, G, go), stable=True)[:int((go >= 0).sum())]      # stable: ascending inside a group
+    offs = torch.zeros(G + 1, dtype=torch.int64)
+    if G > 0:
+        offs[1:] = torch.cumsum(torch.bincount(go[go >= 0], minlength=G), 0)
+    return tuple(v.to(torch.int32).contiguous().to(device) for v in (go, members, offs))
+
+
+def _softmax_ce_groups(name: str, logits: Tensor, C_: int, groups, glabels, gsoft, keep, gscale, row_g, loss_sum, dlogits, row_loss):
+    """the body of the two wrappers below: the checks of the tensors, then the C symbol afft_<name>, as _softmax_ce.  The limits on G
+    and the choice between the two targets are the library's to refuse."""
+    frames = "frames" in name
+    if frames:
+        clips, per_clip = logits.shape[0], logits.shape[1]
+        assert logits.dtype == torch.float32 and logits.dim() == 3 and logits.stride(2) == 1
+        rows = clips * per_clip
+    else:
+        rows = logits.shape[0]
+        assert logits.dtype == torch.float32
+    group_of, members, offs = groups
+    for what, v in (("group_of", group_of), ("members", members), ("offs", offs)):
+        if v.dtype != torch.int32 or v.dim() != 1 or not v.is_contiguous() or v.device != logits.device:
+            raise ValueError(f"afft_amd: {what} must be a contiguous int32 vector on {logits.device} (ops.group_csr makes it), got "
+                             f"{v.dtype} {tuple(v.shape)} on {v.device}")
+    G = offs.numel() - 1
+    if group_of.numel() != C_ or members.numel() > C_ or G < 0:
+        raise ValueError(f"afft_amd: the group description does not fit {C_} classes: group_of {group_of.numel()}, members "
+                         f"{members.numel()}, offs {offs.numel()}")
+    if glabels is not None:
+        assert glabels.dtype == torch.int64 and glabels.numel() == rows and glabels.is_contiguous()
+    if gsoft is not None:
+        assert gsoft.dtype == torch.float32 and gsoft.dim() == 2 and gsoft.shape == (rows, G)
+    if keep is not None:
+        assert keep.dtype == torch.uint8 and keep.numel() == rows
+    if frames and dlogits is not None:
+        assert dlogits.dim() == 3 and dlogits.shape[:2] == logits.shape[:2] and dlogits.stride(2) == 1
+    fn = getattr(L.lib(), "afft_" + name)
+    if frames:
+        args = [_p(logits), logits.stride(0), logits.stride(1), clips, per_clip, C_]
+    else:
+        args = [_p(logits), _rowmajor(logits, "logits"), rows, C_]
+    args += [G, _p(group_of), _p(members), _p(offs), _p(glabels), _p(gsoft), _rowmajor(gsoft, "gsoft") if gsoft is not None else 0,
+             _p(keep), gscale, _p(row_g)]
+    if frames:
+        args += [_p(dlogits), dlogits.stride(0) if dlogits is not None else 0, dlogits.stride(1) if dlogits is not None else 0]
+    else:
+        args += [_p(loss_sum), _p(dlogits), _rowmajor(dlogits, "dlogits") if dlogits is not None else 0]
+    args += [_dt(dlogits) if dlogits is not None else 0, _p(row_loss)]
+    L.check(fn(*args, _stream()), name)
+
+
+def softmax_ce_groups(logits: Tensor, C_: int, groups, *, glabels: Optional[Tensor] = None, gsoft: Optional[Tensor] = None,
+                      keep: Optional[Tensor] = None, gscale: float = 1.0, row_g: Optional[Tensor] = None,
+                      loss_sum: Optional[Tensor] = None, dlogits: Optional[Tensor] = None, row_loss: Optional[Tensor] = None):
+    """marginal cross-entropy over class groups (afft_softmax_ce_groups: the formulas are in include/afft_hip.h): logits fp32
+    [rows, >= C] view, groups = ops.group_csr(class -> group map) on the logits' device; glabels int64 [rows] GROUP labels (-1 ignored)
+    or gsoft fp32 [rows, G] (a view with its own row pitch) group targets; everything else as softmax_ce."""
+    _softmax_ce_groups("softmax_ce_groups", logits, C_, groups, glabels, gsoft, keep, gscale, row_g, loss_sum, dlogits, row_loss)
+
+
+def softmax_ce_frames_groups(logits3: Tensor, C_: int, groups, *, glabels: Optional[Tensor] = None, gsoft: Optional[Tensor] = None,
+                             keep: Optional[Tensor] = None, row_g: Optional[Tensor] = None, dlogits3: Optional[Tensor] = None,
+                             row_loss: Optional[Tensor] = None):
+    """softmax_ce_groups on a (clips, frames, >= C) VIEW (afft_softmax_ce_frames_groups), as softmax_ce_frames"""
+    _softmax_ce_groups("softmax_ce_frames_groups", logits3, C_, groups, glabels, gsoft, keep, 1.0, row_g, None, dlogits3, row_loss)
+
+
 def loss_reduce(vals, weights, means: Optional[Tensor], total: Tensor):
     """means[i] = mean(vals[i]), total[0] = sum_i weights[i] * means[i]: Runner._reduce_loss in one launch (afft_loss_reduce)"""
     n = len(vals)

@@ -481,6 +481,40 @@ int afft_softmax_ce_frames_focal(const float* logits, int64_t clip_stride, int64
                                  const int64_t* labels, const float* soft, int64_t lds, const uint8_t* keep, float gscale,
                                  const float* row_g, void* dlogits, int64_t d_clip_stride, int64_t ldd, int32_t d_dtype, float* row_loss,
                                  const float* weight, float smoothing, const float* adjust, float gamma, void* stream);
+/* Marginal cross-entropy over class groups: the loss on a marginal of the softmax (EPIC-KITCHENS: the verb or the noun of an action
+ * class; the quantity challenge.marginalize_scores ranks by), forward and gradient in one launch.  The C classes of a row belong to
+ * G groups, 1 <= G <= AFFT_CE_GROUPS_MAX, stated twice, both int32, 4-byte aligned, on the device (anything else is a host error
+ * before any launch):
+ *   group_of [C]:  a class's group in [0, G), or -1: in no group -- it counts in lse and gets no target term;
+ *   offs [G + 1], members [offs[G] <= C]:  a CSR of the same map, members[offs[g] .. offs[g + 1]) = the classes of group g, ascending.
+ * The kernel trusts the two to agree and to stay in range (afft_amd.ops.group_csr builds and checks them; members may be NULL when
+ * offs[G] == 0).  The target is over GROUPS: glabels int64 [rows] (-1 = ignored row), or gsoft fp32 [rows, G] with row pitch
+ * ldgs >= G; exactly one of the two.  With x a row of logits, lse = logsumexp_c x_c, p = softmax(x), and for a group g
+ *   m_g = max_{c in g} x_c,   s_g = sum_{c in g} exp(x_c - m_g),   lse_g = m_g + log s_g
+ * -- the group's OWN maximum, not the row's: a group whose members all lie 100 below the row's top logit keeps a finite, accurate
+ * lse_g --,
+ *   hard label y:   row_loss = lse - lse_y                          (= -log sum_{c in y} p_c)
+ *                   dlogits[c] = gscale * row_g * (p_c - [group_of[c] == y] exp(x_c - lse_y))
+ *   soft target t:  T = sum_g t_g,  row_loss = T lse - sum_{g: t_g != 0} t_g lse_g
+ *                   dlogits[c] = gscale * row_g * (T p_c - t_g(c) exp(x_c - lse_g(c)))        (the second term 0 for an ungrouped class)
+ * where exp(x_c - lse_g) is evaluated as exp(x_c - m_g) / s_g.  Groups with t_g == 0 are not visited and may be empty.
+ * Ignored rows (glabels == -1, keep == 0) give loss 0 and a zero gradient row.  A bad row -- a hard label outside [-1, G), a hard
+ * label that names an empty group, a soft target with t_g != 0 on an empty group -- gives NaN in that row's loss and gradient, reads
+ * nothing out of bounds and leaves the other rows untouched.  Row addressing (both forms), keep, gscale, row_g, row_loss, loss_sum,
+ * d_dtype and the zeroed columns C..ldd-1 are afft_softmax_ce's.
+ * Order: one 256-thread workgroup per row; row max and row sum as afft_softmax_ce; group g by wave g % 4, its members strided over
+ * the 64 lanes, then the wave's max / sum tree; each wave adds its t_g lse_g front to back, the four waves' sums and T are added in
+ * wave order.  No atomics: same inputs, same bits. */
+#define AFFT_CE_GROUPS_MAX 1024      /* m_g and t_g / s_g of every group of a row sit in LDS: 8 KiB */
+int afft_softmax_ce_groups(const float* logits, int64_t ldl, int32_t rows, int32_t C, int32_t G, const int32_t* group_of,
+                           const int32_t* members, const int32_t* offs, const int64_t* glabels, const float* gsoft, int64_t ldgs,
+                           const uint8_t* keep, float gscale, const float* row_g, float* loss_sum, void* dlogits, int64_t ldd,
+                           int32_t d_dtype, float* row_loss, void* stream);
+int afft_softmax_ce_frames_groups(const float* logits, int64_t clip_stride, int64_t ldl, int32_t clips, int32_t frames, int32_t C,
+                                  int32_t G, const int32_t* group_of, const int32_t* members, const int32_t* offs,
+                                  const int64_t* glabels, const float* gsoft, int64_t ldgs, const uint8_t* keep, float gscale,
+                                  const float* row_g, void* dlogits, int64_t d_clip_stride, int64_t ldd, int32_t d_dtype,
+                                  float* row_loss, void* stream);
 /* Runner._reduce_loss (common/runner.py:198-213) in one launch: term i = n[i] fp32 per-row losses at x[i] (HOST arrays of nterms <= 8
  * device pointers / counts / weights); means[i] = mean(x[i]) (may be NULL), total[0] = sum_i w[i] * means[i], in a fixed order (bit-stable).
  * afft_loss_reduce_bwd: g[i][0 .. n[i]) = g_total[0] * w[i] / n[i] (g_total NULL = 1; g[i] NULL skips a term): the upstream
