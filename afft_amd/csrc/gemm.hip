@@ -624,9 +624,12 @@ static int prepare_gemm(const afft_gemm_t* d, GemmPrep& q) {
     return (ld % 4 == 0) && ((((uintptr_t)p) & (align - 1)) == 0);
   };
   auto ok8 = [](const void* p, int64_t ld) { return !p || ((ld % 8 == 0) && ((((uintptr_t)p) & 15) == 0)); };
+  // the e4m3 byte image of a fused update goes out as one 8-byte (4-byte) word per 8 (4) parameters; the packed image is 16-byte
+  // aligned (checked above) and its 4-wide pieces start at elements 0 and 4 of a fragment
+  const bool p8_ok8 = (((uintptr_t)e.sgd.p8) & 7) == 0, p8_ok4 = (((uintptr_t)e.sgd.p8) & 3) == 0;
   e.vec8 = ok8(d->out, d->ldo) && ok8(d->out2, d->ldo2) && ok8(d->pre, d->ldpre) && ok8(d->aux, d->ldaux) &&
-           ok8(d->residual, d->ldres) && ok8(d->bias, 8) && ok8(e.sgd.p, d->ldo) && ok8(e.sgd.buf, d->ldo) && ok8(e.sgd.p16, d->ldo) && ok8(e.sgd.p16h, d->ldo);
-  e.vec4 = ok4(e.sgd.p, d->ldo, AFFT_F32) && ok4(e.sgd.buf, d->ldo, AFFT_F32) && ok4(e.sgd.p16, d->ldo, AFFT_BF16) && ok4(e.sgd.p16h, d->ldo, AFFT_BF16) &&
+           ok8(d->residual, d->ldres) && ok8(d->bias, 8) && ok8(e.sgd.p, d->ldo) && ok8(e.sgd.buf, d->ldo) && ok8(e.sgd.p16, d->ldo) && ok8(e.sgd.p16h, d->ldo) && p8_ok8;
+  e.vec4 = ok4(e.sgd.p, d->ldo, AFFT_F32) && ok4(e.sgd.buf, d->ldo, AFFT_F32) && ok4(e.sgd.p16, d->ldo, AFFT_BF16) && ok4(e.sgd.p16h, d->ldo, AFFT_BF16) && p8_ok4 &&
            ok4(d->out, d->ldo, d->out_dtype) && ok4(d->out2, d->ldo2, d->out2_dtype) &&
            ok4(d->pre, d->ldpre, d->pre_dtype) && ok4(d->aux, d->ldaux, d->aux_dtype) &&
            ok4(d->residual, d->ldres, AFFT_F32) && ok4(d->bias, 4, AFFT_F32);

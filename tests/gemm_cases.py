@@ -17,6 +17,11 @@ epi:    alpha (float), bias, rowscale, residual, accumulate (bools), act (AFFT_A
         out ("f32", "bf16" or "f16"; default f32), out_lo / out_lo8 (bools: fp16 plane outputs), packed (B also as the
         fragment-packed image: afft_gemm_t.b_packed), ldo (row pitch of every output-shaped view), col0 (element offset of those
         views inside their rows: 0 -> 16-byte aligned), a_off (A's base one element off 16-byte alignment).
+        sgd: the product is the gradient of a weight and is consumed by the fused momentum-SGD update (afft_gemm_t.sgd) instead of
+        being stored; no other stage beside it.  A dict: flags (AFFT_SGD_* word), images (which of the weight's images the update
+        keeps: bf16, f16, f8 row-major, pk fragment-packed: M % 16 == 0 and ldo % 32 == 0), ok (None: no flag, 1 / 0: the device flag
+        that lets the update happen / makes it a no-op) and optionally alpha, ldo, col0 with the meaning above: p, buf and the
+        row-major images all have the output's geometry.
 ld:     leading dimension of both k-strided operands (0 = a small padding past the logical width): the 32-bit walk cases.
 amp, sh: operand values are integers in [-amp, amp] times 2^-sh (exact in every operand format; see the GPU test)."""
 from __future__ import annotations
@@ -81,6 +86,19 @@ F32_FLOAT = "gemm_f32_kernel<float>"
 F32_BF16 = "gemm_f32_kernel<unsigned short>"
 
 NT, NN, TN = (False, False), (False, True), (True, True)
+
+# AFFT_SGD_* flag words (include/afft_hip.h)
+NESTEROV, FIRST, PLAIN = 0, 1, 2
+
+
+def _sgd(flags, images, ok=None, **geometry):
+    """the epilogue of a case whose product is consumed by the fused optimizer update: see `sgd` in the module docstring"""
+    return dict(sgd=dict(flags=flags, images=tuple(images.split()), ok=ok, **geometry))
+
+
+# the kernel families a weight gradient can reach: each is the expected kernel of at least one `sgd` case (test_gemm_coverage_cpu.py)
+SGD_FAMILIES = [gen(*TN), gen(*TN, splitk=True), g2(*TN), g2(*TN, splitk=True), pp(*TN), pp2(*TN), gen(*TN, x3=1), pp(*TN, 1), pp2(*TN, 1),
+                gen(*TN, stages=4), F32_FLOAT, F32_BF16]
 
 # plane-output operands: values with more significant bits than fp16 holds, so that the lo plane is not zero
 _LO = dict(amp=16, sh=3)
@@ -226,6 +244,27 @@ CASES = [
     _c("bf16_fallback_k100_tn", "tn", 65, 33, 100, F32_BF16, epi=dict(accumulate=True)),
     _c("bf16_fallback_tt", "tt", 33, 65, 128, F32_BF16),
     _c("bf16_fallback_a_off", "nn", 130, 200, 128, F32_BF16, epi=dict(a_off=1, out="bf16")),
+    # ---- the fused momentum-SGD update as the epilogue (afft_gemm_t.sgd) of every kernel family a weight gradient can reach: the four
+    #      flag words, alpha, ok, the 8-wide / 4-wide / scalar accesses, every image; a first step enters with a NaN momentum buffer
+    _c("sgd_gen_tn", "tn", 256, 256, 64, gen(*TN), epi=_sgd(NESTEROV, "bf16 f16 f8 pk", ldo=288)),
+    _c("sgd_gen_tn_n254_pk", "tn", 256, 254, 64, gen(*TN), epi=_sgd(PLAIN, "bf16 f16 f8 pk", ok=1, alpha=-2.0, ldo=256)),      # a row ends 8-wide, 4-wide, scalar
+    _c("sgd_gen_tn_n250_col4_pk", "tn", 256, 250, 64, gen(*TN), epi=_sgd(NESTEROV, "bf16 pk", alpha=0.5, ldo=256, col0=4)),    # 4-wide pieces at n % 8 == 4
+    _c("sgd_gen_tn_splitk4_pk", "tn", 256, 254, 768, gen(*TN, splitk=True), splitk=4, epi=_sgd(FIRST, "bf16 f8 pk", alpha=0.5, ldo=256)),
+    _c("sgd_g2_tn", "tn", 256, 256, 128, g2(*TN), epi=_sgd(FIRST | PLAIN, "f16 f8", ok=1, alpha=0.5)),
+    _c("sgd_g2_tn_splitk4", "tn", 256, 256, 512, g2(*TN, splitk=True), splitk=4, epi=_sgd(NESTEROV, "bf16 pk", alpha=-2.0, ldo=288)),
+    _c("sgd_g2_tn_splitk4_ok0", "tn", 256, 256, 512, g2(*TN, splitk=True), splitk=4, epi=_sgd(NESTEROV, "bf16 f16 f8 pk", ok=0, ldo=288)),
+    _c("sgd_pp_tn_tails_ld4", "tn", 129, 257, 256, pp(*TN), variant=3, epi=_sgd(PLAIN, "bf16 f16 f8", ldo=260)),
+    _c("sgd_pp2_tn", "tn", 256, 512, 256, pp2(*TN), variant=3, epi=_sgd(FIRST, "bf16 f16 f8 pk", alpha=-2.0, ldo=544)),
+    _c("sgd_x3_tn_general", "tn", 256, 130, 512, gen(*TN, x3=1), mode="bf16x3", epi=_sgd(NESTEROV, "bf16 f8 pk", ok=1, ldo=160)),
+    _c("sgd_x3_tn_pp", "tn", 512, 264, 704, pp(*TN, 1), mode="bf16x3", variant=3, epi=_sgd(FIRST | PLAIN, "f16", alpha=0.5)),
+    _c("sgd_x3_tn_pp2", "tn", 512, 256, 640, pp2(*TN, 1), mode="bf16x3", variant=3, epi=_sgd(PLAIN, "bf16 f8")),
+    _c("sgd_v4_tn_scalar", "tn", 130, 257, 192, gen(*TN, stages=4), variant=4, epi=_sgd(NESTEROV, "bf16 f16 f8", ok=1, alpha=-2.0, col0=1)),
+    _c("sgd_v4_tn_scalar_ok0", "tn", 130, 257, 192, gen(*TN, stages=4), variant=4, epi=_sgd(PLAIN, "bf16 f16 f8", ok=0, col0=1)),
+    _c("sgd_f32_tn_k63", "tn", 66, 70, 63, F32_FLOAT, mode="f32", epi=_sgd(FIRST, "bf16 f16 f8", alpha=0.5)),
+    _c("sgd_f32_tn_k63_ok0", "tn", 66, 70, 63, F32_FLOAT, mode="f32", epi=_sgd(NESTEROV, "bf16 f16 f8", ok=0)),
+    _c("sgd_bf16_fallback_k100_tn", "tn", 65, 33, 100, F32_BF16, epi=_sgd(PLAIN, "bf16 f16 f8", ok=1, alpha=-2.0)),
+    _c("sgd_g2_nt_f8_col4", "nt", 256, 256, 128, g2(*NT), epi=_sgd(NESTEROV, "f8", ldo=264, col0=4)),      # p / buf 16-byte aligned, the byte image 4
+    _c("sgd_gen_nn", "nn", 256, 256, 192, gen(*NN), epi=_sgd(FIRST | PLAIN, "bf16 f16 f8 pk", ldo=256)),
 ]
 
 assert len({c.name for c in CASES}) == len(CASES), "case names must be unique"

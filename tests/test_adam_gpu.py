@@ -35,13 +35,9 @@ def _restate(p, g, m, v, lr, wd, gscale, t_prev, decoupled):
 
 
 def _e4m3_of(p):
-    """the e4m3 image afft_sgd_nesterov2 writes for p (lr = wd = 0 leaves p as it is)"""
-    from afft_amd import ops
-    q = p.clone()
-    out = torch.zeros(p.numel(), dtype=torch.uint8, device=p.device)
-    ops.sgd_nesterov(q, torch.zeros_like(q), torch.zeros_like(q), 0.0, 0.0, 0.0, 1.0, 1, p_f8=out)
-    assert torch.equal(q, p)
-    return out
+    """the e4m3 image of p by the rounding rule itself (tests/sgd_double.py): (256 p) clamped to +-448, rounded once; no kernel"""
+    from sgd_double import e4m3_image
+    return e4m3_image(p)
 
 
 @pytest.mark.parametrize("gdtype", [torch.float32, torch.bfloat16])

@@ -10,7 +10,7 @@ import subprocess
 
 import pytest
 
-from gemm_cases import CASES, _traced_symbol, dispatch_fields, gemm_fields
+from gemm_cases import CASES, SGD_FAMILIES, _traced_symbol, dispatch_fields, gemm_fields
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _KERNEL = re.compile(r"\b(gemm_[a-z0-9_]+_kernel<[^()]*>)\(")
@@ -57,6 +57,30 @@ def test_case_table_is_well_formed():
         assert c.variant in (0, 1, 3, 4, 7, 8, 9, 10) and c.splitk in (0, 1, 2, 4), c.name
         assert not (c.epi.get("accumulate") and c.epi.get("out", "f32") != "f32"), c.name
         assert not ((c.epi.get("out_lo") or c.epi.get("out_lo8")) and c.epi.get("out") != "f16"), c.name
+        s = c.epi.get("sgd")
+        if s is not None:
+            assert set(c.epi) == {"sgd"}, c.name      # the fused update takes the plain product: alpha, ldo, col0 live in its dict
+            assert set(s) <= {"flags", "images", "ok", "alpha", "ldo", "col0"} and s["flags"] in (0, 1, 2, 3) and s["ok"] in (None, 0, 1), c.name
+            assert set(s["images"]) <= {"bf16", "f16", "f8", "pk"} and len(set(s["images"])) == len(s["images"]), c.name
+            assert "pk" not in s["images"] or (c.M % 16 == 0 and s.get("ldo", 0) % 32 == 0 and s.get("ldo", 0) >= s.get("col0", 0) + c.N), c.name
+
+
+def test_every_weight_gradient_kernel_family_carries_the_fused_update():
+    """every kernel family a weight gradient can reach ends in the fused SGD update in at least one case, and the cases together
+    cover what the update's code branches on"""
+    sgd = [c for c in CASES if "sgd" in c.epi]
+    carried = {c.kernel for c in sgd}
+    for k in SGD_FAMILIES:
+        assert k in carried, f"no `sgd` case of tests/gemm_cases.py runs on {k}"
+    tn_families = {c.kernel.split("<")[0] for c in CASES if c.layout == "tn"}
+    assert tn_families == {k.split("<")[0] for k in SGD_FAMILIES}, tn_families      # a new family with a tn case: add it to SGD_FAMILIES
+    assert {c.layout for c in sgd} >= {"tn", "nt", "nn"}
+    s = [c.epi["sgd"] for c in sgd]
+    assert {x["flags"] for x in s} == {0, 1, 2, 3} and {x["ok"] for x in s} == {None, 0, 1}
+    assert {x.get("alpha", 1.0) for x in s} >= {0.5, -2.0, 1.0}
+    assert any(c.splitk > 1 and "pk" in c.epi["sgd"]["images"] for c in sgd)
+    widths = {(x.get("ldo", 0) % 8, x.get("col0", 0) % 4) for x in s}
+    assert {(0, 0), (4, 0), (0, 1)} <= widths, widths
 
 
 def _plan_for(_lib, fields):

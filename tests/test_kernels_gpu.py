@@ -1414,18 +1414,122 @@ def _run_traced(c, a, b, out, **kw):
         buf = (_lib.GemmTraceRec * 8)()
         n = _lib.lib().afft_gemm_trace_end(buf, 8)
     torch.cuda.synchronize()
-    return [_traced_symbol(buf[i]) for i in range(n)]
+    return [(_traced_symbol(buf[i]), int(buf[i].fused_update)) for i in range(n)]
 
 
 def _check_kernel(c, ran):
+    """ran: (kernel symbol, fused_update) of every traced launch: the case's kernel, carrying the optimizer update iff the case asks"""
     if c.fast:
-        assert ran == [c.kernel], f"{c.name}: ran {ran}, the case is written for {c.kernel}"
+        assert ran == [(c.kernel, int("sgd" in c.epi))], f"{c.name}: ran {ran}, the case is written for {c.kernel}"
     else:
         assert ran == [], f"{c.name}: the exact-fp32 kernel was expected, the fast path ran {ran}"
 
 
+def _first_diff(name, got, want, what):
+    if not torch.equal(got, want):
+        bad = (got != want).nonzero()
+        at = tuple(int(x) for x in bad[0])
+        raise AssertionError(f"{name}: {what} differs in {bad.shape[0]} of {got.numel()} elements, first at {list(at)}: "
+                             f"{float(got[at])} instead of {float(want[at])}")
+
+
+class _SgdStage:
+    """The fused momentum-SGD update (afft_gemm_t.sgd) as the last stage of a GEMM case: the parameters p, the momentum buffer buf and
+    the row-major images the case asks for, each an [M, N] view of the output's geometry in a _Fenced buffer (sentinels around and,
+    for the images, inside: p and buf are NaN outside their views, the fp32 sentinel being one), the fragment-packed image in a flat
+    sentinel-filled buffer with 64 spare elements either side.  Reference: tests/sgd_double.py on the float64 gradient.
+    exact: power-of-two hyperparameters and dyadic p / buf such that wd p, g', buf, the Nesterov sum and the new p are all fp32
+    numbers (`stages`: the caller asserts it), so p, buf and every image must equal the reference bit for bit.  p starts on
+    multiples of 2^-4 in [-1.5, 1.5] and lr is the power of two that makes the rms step 0.25 .. 0.5: the new p has some 16
+    significant bits (bf16, fp16 and e4m3 all round it), and |256 p| passes 448, where the byte image saturates, in some elements
+    and stays below in most.  Otherwise: normal p / buf and the recipes' hyperparameters, compared within sgd_double.sgd_bound."""
+
+    def __init__(self, c, M, N, ldo, col0, gen, grad, exact):
+        import sgd_double as sd
+        from afft_amd import _lib
+        s = c.epi["sgd"]
+        self.c, self.M, self.N, self.ldo, self.flags, self.ok, self.grad = c, M, N, ldo, s["flags"], s["ok"], grad
+        first = bool(self.flags & sd.FIRST_STEP)
+        if exact:
+            p0, b0 = _ints((M, N), 24, 4, gen), _ints((M, N), 4096, 9, gen)
+            mom, wd, gs = 0.5, 2.0 ** -6, 0.5
+            unit = sd.sgd_stages(p0, b0, grad, 1.0, mom, wd, gs, self.flags)["step"]
+            lr = 2.0 ** -math.ceil(math.log2(2.0 * float(unit.pow(2).mean().sqrt())))
+        else:
+            p0 = torch.randn(M, N, generator=gen, device=dev(), dtype=torch.float64).float().double()
+            b0 = torch.randn(M, N, generator=gen, device=dev(), dtype=torch.float64).float().double()
+            lr, mom, wd, gs = (sd.f32(x) for x in (0.05, 0.9, 1e-3, 0.5))
+        self.hyper = (lr, mom, wd, gs)
+        self.p0, self.b0 = p0, b0
+        self.p, self.buf = _Fenced(M, N, torch.float32, ldo, col0), _Fenced(M, N, torch.float32, ldo, col0)
+        self.p.v.copy_(p0)
+        self.buf.v.copy_(torch.full_like(b0, float("nan")) if first else b0)      # a first step must not depend on what buf holds
+        self.img = {k: _Fenced(M, N, {"bf16": torch.bfloat16, "f16": torch.float16, "f8": torch.uint8}[k], ldo, col0)
+                    for k in s["images"] if k != "pk"}
+        self.pk = None
+        if "pk" in s["images"]:
+            self.pk = torch.empty(M * ldo + 128, dtype=torch.bfloat16, device=dev())
+            self.pk.view(torch.int16).fill_(_SENTINEL[torch.bfloat16][1])
+        self.ok_dev = None if self.ok is None else torch.full((1,), float(self.ok), device=dev())
+        self.before = [t.clone() for t in self._buffers()]
+        st = sd.sgd_stages(p0, b0, grad, lr, mom, wd, gs, self.flags)
+        self.stages = [st[k] for k in ("wdp", "g1", "buf", "step", "p")]
+        self.want_p, self.want_buf = st["p"], st["buf"]
+        d = self.desc = _lib.SgdFused()
+        d.p, d.buf, d.lr, d.mom, d.wd, d.gscale, d.first_step = self.p.v.data_ptr(), self.buf.v.data_ptr(), lr, mom, wd, gs, self.flags
+        for k, f in (("bf16", "p_bf16"), ("f16", "p_f16"), ("f8", "p_f8")):
+            if k in self.img:
+                setattr(d, f, self.img[k].v.data_ptr())
+        if self.pk is not None:
+            d.p_pk16 = self.pk[64:].data_ptr()
+        if self.ok_dev is not None:
+            d.ok = self.ok_dev.data_ptr()
+        if exact and "f8" in self.img and self.ok != 0:      # the inputs do exercise rounding and saturation of every image
+            sat = int((self.want_p.abs() * 256.0 > 448.0).sum())
+            assert 0 < sat < M * N // 2, (c.name, sat)
+            assert float((self.want_p.float().half().double() != self.want_p).double().mean()) > 0.5, c.name
+
+    def _buffers(self):
+        return [self.p.buf, self.buf.buf] + [f.buf for f in self.img.values()] + ([] if self.pk is None else [self.pk])
+
+    def check(self, dgrad=None):
+        """dgrad None: p, buf and the images are the reference, bitwise; else the elementwise bound of the gradient's error: p and buf
+        within sgd_bound, the images the independent roundings of the kernel's own p"""
+        import sgd_double as sd
+        name = self.c.name
+        if self.ok == 0:      # a no-op: every bit of every buffer as it was (p, buf and the images' sentinels, views included)
+            for t, t0 in zip(self._buffers(), self.before):
+                it = torch.int32 if t.dtype == torch.float32 else torch.uint8 if t.dtype == torch.uint8 else torch.int16
+                assert torch.equal(t.view(it), t0.view(it)), f"{name}: ok = 0, and the update wrote something"
+            return
+        p, buf = self.p.v, self.buf.v
+        assert self.p.intact() and self.buf.intact() and all(f.intact() for f in self.img.values()), f"{name}: a store outside the weight's views"
+        assert not torch.isnan(p).any() and not torch.isnan(buf).any(), f"{name}: NaN in p or buf (a read outside the problem, or of buf on a first step)"
+        if dgrad is None:
+            _first_diff(name, p, self.want_p.float(), "p")
+            _first_diff(name, buf, self.want_buf.float(), "buf")
+        else:
+            ep, eb = sd.sgd_bound(self.p0, self.b0, self.grad, *self.hyper, self.flags, dg=dgrad)
+            for got, want, bound, what in ((p, self.want_p, ep, "p"), (buf, self.want_buf, eb, "buf")):
+                bad = ~((got.double() - want).abs() <= bound)
+                if bool(bad.any()):
+                    i, j = (int(x) for x in bad.nonzero()[0])
+                    raise AssertionError(f"{name}: {int(bad.sum())} elements of {what} outside the derived bound, first [{i}, {j}]: "
+                                         f"{float(got[i, j])} vs {float(want[i, j])} (bound {float(bound[i, j]):.3g})")
+        src = p if dgrad is not None else self.want_p.float()      # exact pass: p equals the reference, the images follow from either
+        for k, f in self.img.items():
+            want = {"bf16": sd.bf16_image, "f16": sd.f16_image, "f8": sd.e4m3_image}[k](src)
+            _first_diff(name, f.v, want, f"the {k} image")
+        if self.pk is not None:
+            idt, sentinel = _SENTINEL[torch.bfloat16]
+            want = torch.full_like(self.pk.view(idt), sentinel)      # the padding columns N .. ldo of the packed image keep the sentinel
+            want[64 + sd.packed_frag(self.M, self.ldo, device=dev())[:, :self.N].reshape(-1)] = sd.bf16_image(src).contiguous().view(idt).reshape(-1)
+            _first_diff(name, self.pk.view(idt), want, "the fragment-packed image (as int16, with its fences)")
+
+
 def _exact_pass(c):
-    ep = c.epi
+    ep = dict(c.epi)
+    ep.update({k: v for k, v in ep.get("sgd", {}).items() if k in ("alpha", "ldo", "col0")})      # a fused update's geometry lives in its dict
     gen = torch.Generator(device=dev()).manual_seed(zlib.crc32(c.name.encode()))
     M, N, K = c.M, c.N, c.K
     A, Bm = _ints((M, K), c.amp, c.sh, gen), _ints((K, N), c.amp, c.sh, gen)
@@ -1441,6 +1545,11 @@ def _exact_pass(c):
     alpha = ep.get("alpha", 1.0)
     stages = [alpha * prod]
     v = stages[-1]
+    fused = None
+    if ep.get("sgd"):      # the product is a gradient: consumed by the update, never stored (out keeps its sentinel, view included)
+        fused = _SgdStage(c, M, N, ldo, col0, gen, v, exact=True)
+        stages += fused.stages
+        kw["sgd"] = fused.desc
     if ep.get("bias"):
         bias_buf = torch.full((col0 + N + 8,), float("nan"), device=dev())
         kw["bias"] = bias_buf[col0:col0 + N]
@@ -1503,13 +1612,14 @@ def _exact_pass(c):
     if odt == torch.float16:
         assert float(ref.abs().max()) < 65504.0
     _check_kernel(c, _run_traced(c, a, b, out.v, **kw))
+    if fused is not None:
+        idt, sentinel = _SENTINEL[odt]
+        assert bool((out.buf.view(idt) == sentinel).all()), f"{c.name}: the fused update stored something to out"
+        fused.check()
+        return
 
     def same(got, want, what):
-        if not torch.equal(got, want):
-            bad = (got != want).nonzero()
-            i, j = (int(x) for x in bad[0])
-            raise AssertionError(f"{c.name}: {what} differs in {bad.shape[0]} of {got.numel()} elements, first at [{i}, {j}]: "
-                                 f"{float(got[i, j])} instead of {float(want[i, j])}")
+        _first_diff(c.name, got, want, what)
 
     def close(got, what):      # activated output: the activation's own error (scaled by what follows it) + the output rounding
         tol = _ACT_TOL[act] * (pre_ref.abs().clamp_min(1.0) if act in (GELU_ERF, GELU_TANH) else
@@ -1551,6 +1661,8 @@ def _realistic_pass(c):
     else:
         A, Bm = A.float().double(), Bm.float().double()
     a, b, kw, ref, absprod = _operands(c, A, Bm, gen, exact=False)
+    if c.epi.get("sgd"):
+        return _realistic_sgd(c, a, b, kw, ref, absprod, gen)
     odt = torch.float32 if c.epi.get("out", "f32") == "f16" else _TDT[c.epi.get("out", "f32")]
     out = torch.full((c.M, c.N), float("nan"), dtype=odt, device=dev())
     _check_kernel(c, _run_traced(c, a, b, out, **kw))
@@ -1563,11 +1675,35 @@ def _realistic_pass(c):
                              f"{float(out[i, j])} vs {float(ref[i, j])} (bound {float(tol[i, j]):.3g})")
 
 
+def _realistic_sgd(c, a, b, kw, ref, absprod, gen):
+    """The realistic pass of a case whose product feeds the fused update: normal p and buf, the recipes' hyperparameters (lr 0.05,
+    momentum 0.9, weight decay 1e-3, gscale 0.5), p and buf elementwise against tests/sgd_double.py on the float64 product.
+    The bound, derived, not tuned: the kernel's gradient alpha * acc is off by at most dg = |alpha| 2 K 2^-24 (|A| |B|)_ij (fp32
+    accumulation in any order; alpha is a power of two, its product exact).  sgd_update is differentiable in g with dg' / dg = gscale,
+    dbuf / dg = gscale, dstep / dg = gscale (1 + mom) (Nesterov) or gscale (plain momentum), dp / dg = lr dstep / dg; to that come
+    the five roundings of sgd_update itself (wd p, g', buf, the Nesterov sum, p), each at most 2^-24 of its result and propagated
+    the same way: sgd_double.sgd_bound, whose docstring carries the recurrence.  The images are functions of the kernel's own p: they
+    must be its independent roundings (sgd_double), element for element."""
+    s = c.epi["sgd"]
+    alpha, col0 = s.get("alpha", 1.0), s.get("col0", 0)
+    ldo = s.get("ldo") or padded_pitch(c.N, col0)
+    out = _Fenced(c.M, c.N, torch.float32, ldo, col0)
+    fused = _SgdStage(c, c.M, c.N, ldo, col0, gen, alpha * ref, exact=False)
+    if alpha != 1.0:
+        kw["alpha"] = alpha
+    _check_kernel(c, _run_traced(c, a, b, out.v, sgd=fused.desc, **kw))
+    idt, sentinel = _SENTINEL[torch.float32]
+    assert bool((out.buf.view(idt) == sentinel).all()), f"{c.name}: the fused update stored something to out"
+    fused.check(dgrad=abs(alpha) * 2.0 * c.K * 2.0 ** -24 * absprod)
+
+
 @pytest.mark.parametrize("case", GEMM_TABLE, ids=lambda c: c.name)
 def test_gemm_instantiation_exact(case):
     """One case of tests/gemm_cases.py: the launch ran the case's kernel (GEMM trace), the result on exact operands equals float64
     (fp32 outputs bitwise; 16-bit outputs and planes = float64 rounded once; activations within their established bounds), nothing
-    outside M x N x K was read or outside the output views written; plain bf16 / fp32 kernels also on realistic operands."""
+    outside M x N x K was read or outside the output views written; plain bf16 / fp32 kernels also on realistic operands.
+    `sgd` cases: the product is consumed by the fused optimizer update (_SgdStage): p, buf and the weight's images bitwise on exact
+    inputs, within the derived bound on realistic ones, and the trace record says the launch carried the update."""
     from afft_amd import _lib
     _lib.check(_lib.lib().afft_set_gemm_variant(case.variant))
     _lib.check(_lib.lib().afft_set_gemm_splitk(case.splitk))
