@@ -38,7 +38,7 @@ def test_export_exists_and_parses():
 
 @pytest.mark.parametrize("dtype", [_lib.F32, _lib.BF16])
 def test_step_plan_is_the_stated_rule(dtype):
-    grid = itertools.product((1, 2, 16, 32), (1, 17, 128, 129, 512, 513), (24, 64, 512), (1, 0))
+    grid = itertools.product((1, 2, 16, 32), (1, 17, 128, 129, 512, 513), (1, 8, 24, 64, 512, 520, 1021, 1024), (1, 0))
     bad = [(a, asked(dtype, *a), expected(dtype, *a)) for a in grid if asked(dtype, *a) != expected(dtype, *a)]
     assert not bad, bad[:5]
     assert asked(dtype, 1, 19, 1025, 1) is None and asked(dtype, 0, 4, 64, 1) is None
